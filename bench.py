@@ -16,7 +16,13 @@ hipGraph per batch; what is left of K after whole rotations always runs as per-b
 decode side of batch i on two HIP streams -- measured no faster).  `value` = all pixels of the K
 steps / wall time between two barrier + synchronize brackets, max over ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, ...).  `--full` adds everything else this script measures or checks, outside the
+timed region: parity of the timed batches with the oracle, the per-stage / roofline / saturated-queue figures, the extra
+configurations (8-bit content, ratio sweep, DIV2K, B=1, mixed stream), the CPU baseline, the side file of extras, and at
+N = 1 the one-rank communicator and at N > 1 the all-reduce probe.  `--dump-outputs DIR`: what the last timed step handed
+its caller, one DIR/<name>.npy per array (float32 / float64), for comparing two builds output for output.
 N > 1: one rank per GPU.  Under torch.distributed.run the ranks come from the environment; launched plainly
 (`python bench.py --gpus N`) the script spawns the N ranks itself.  Images shard across ranks with no data-path
 collective; ONE RCCL all-reduce of the int64[1024] usage histogram per run.  Rank 0 prints one JSON line.
@@ -1194,6 +1200,81 @@ def device_identity(dev):
     return bus, ver
 
 
+DUMP_BUDGET = 63 << 20           # --dump-outputs: data bytes in all (the .npy headers stay under 64 MiB next to it)
+
+
+def _arrays_of(name, obj, out):
+    """the arrays a caller finds in `obj` -- tensors, numbers, the streams of a CompressedBatch; dicts, lists and tuples
+    walked -- into `out` under `name` (parts joined by '_')"""
+    if obj is None:
+        return
+    if isinstance(obj, torch.Tensor):
+        out[name] = obj.detach().cpu().numpy()
+    elif isinstance(obj, (np.ndarray, np.number, bool, int, float)):
+        out[name] = np.asarray(obj)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _arrays_of(f"{name}_{k}", v, out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _arrays_of(f"{name}_{i}", v, out)
+    elif hasattr(obj, "to_host") and hasattr(obj, "nbytes"):
+        # CompressedBatch: every stream as to_host() hands it out -- its bytes, zero past its length (the rest of the slot
+        # is scratch no kernel promises anything about; -1 = a stream the mode does not write) -- and the lengths
+        nb = obj.nbytes.cpu().numpy()
+        top = max(int(nb.max()), 0)
+        data = obj.data[:, :, :top].cpu().numpy().copy()
+        data[np.arange(top)[None, None, :] >= nb[:, :, None]] = 0
+        out[name + "_streams"], out[name + "_nbytes"], out[name + "_mode"] = data, nb, np.asarray(obj.mode)
+    else:
+        log(f"bench.py: --dump-outputs: {name} ({type(obj).__name__}) has no array form, not written")
+
+
+def last_step_outputs(stream, hist):
+    """{name: array} of what the timed path handed its caller in the LAST timed step: that step's encode outputs and decode
+    tuple (batch workload; mixed: every chain's), plus the usage histogram the K timed steps accumulated"""
+    out, slot = {}, None
+    if isinstance(stream, MixedStream):
+        for i, (_, _, _, box) in enumerate(stream.chains):
+            _arrays_of(f"chain{i}", box, out)
+    elif hasattr(stream, "lanes"):                       # LaneStream: step t on lane t % lanes, a lane's slots in rotation
+        lane = stream.lanes[(stream._t - 1) % len(stream.lanes)]
+        slot = lane["slots"][(lane["pos"] - 1) % len(lane["slots"])]
+    elif hasattr(stream, "slots"):                       # experimental.BatchStream: slots in rotation
+        slot = stream.slots[(stream._next - 1) % len(stream.slots)]
+    if slot is not None:
+        for k, v in slot.enc.items():
+            if k != "dec":
+                _arrays_of(k, v, out)
+        _arrays_of("dec", dict(zip(("ind", "mask", "z_q", "status"), slot.dec)), out)
+    _arrays_of("usage_histogram", hist, out)
+    return out
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """every array as <path>/<name>.npy: floating point as float32 (float64 stays float64), 8/16-bit integers and bools as
+    float32, wider integers as float64 (exact).  Past `budget` bytes in all, the largest arrays are cut to a fixed sample of
+    their flattened elements (positions seeded by the name: the same in every run with the same arguments)"""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, v in arrays.items():
+        wide = v.dtype == np.float64 or (v.dtype.kind in "iu" and v.dtype.itemsize > 2)
+        conv[name] = v.astype(np.float64 if wide else np.float32)
+    left, order = budget, sorted(conv, key=lambda k: (conv[k].nbytes, k))
+    for i, name in enumerate(order):
+        v = conv[name]
+        share = left // (len(order) - i)
+        if v.nbytes > share:
+            k = max(1, share // v.itemsize)
+            pick = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(v.size, k, replace=False))
+            log(f"bench.py: --dump-outputs: {name} {tuple(v.shape)} written as a fixed sample of {k} of its {v.size} elements")
+            v = v.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), v)
+        left -= v.nbytes
+    log(f"bench.py: {len(order)} outputs of the last timed step written to {path} ({(budget - left) / 2**20:.1f} MiB)")
+
+
 def run_rank(a, rank, world, local):
     stub = bool(a.stub)
     dist = None
@@ -1206,9 +1287,10 @@ def run_rank(a, rank, world, local):
         dev = torch.device("cuda", local)
     ranks_seen = None
     dist_note = None
-    # N = 1 goes through the same code as N > 1: a one-rank communicator (RCCL on the GPU, gloo for the CPU stub), so that
-    # `rccl_ranks` is read back from a communicator and the histogram all-reduce is the same call at every N
-    if world > 1 or "RANK" in os.environ or not a.no_dist:
+    # --full: N = 1 goes through the same code as N > 1: a one-rank communicator (RCCL on the GPU, gloo for the CPU stub), so that
+    # `rccl_ranks` is read back from a communicator and the histogram all-reduce is the same call at every N.  A plain N = 1 run
+    # has no collective to make (none lies inside its timed region) and creates none.
+    if world > 1 or "RANK" in os.environ or (a.full and not a.no_dist):
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if "MASTER_PORT" not in os.environ:
@@ -1380,6 +1462,7 @@ def run_rank(a, rank, world, local):
         per_rank = [float(v[0].item()) for v in every]
         per_rank_dev = [float(v[1].item()) for v in every]
         dt = max(per_rank)                                  # the job is as slow as its slowest rank
+    if dist is not None and a.full:
         # the path's only collective by itself (outside the timed region, communicator warm): int64[1024] SUM
         probe = torch.zeros(1024, dtype=torch.int64, device=dev)
         best = 1e9
@@ -1394,9 +1477,11 @@ def run_rank(a, rank, world, local):
     want_total = a.steps * vec_all if mixed else world * a.steps * B * h * w
     if hist_total != want_total:
         raise SystemExit(f"bench.py: usage histogram lost counts ({hist_total} != {want_total})")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_step_outputs(stream, hist))
     if mixed:
         if rank == 0:
-            ok = True if stub else stream.round_trip_ok()
+            ok = None if not a.full else True if stub else stream.round_trip_ok()
             pix = [mixed_share(sizes, r, world)[2] for r in range(world)]
             res = {
                 "metric": "encode+decode MPixels/s at fixed granularity ratio; bpp match vs reference",
@@ -1450,7 +1535,7 @@ def run_rank(a, rank, world, local):
         }
         if dist_note:
             res["config"]["distributed"] = dist_note
-        if not stub and not a.no_report:
+        if a.full and not stub and not a.no_report:
             line, extras = report(a, dev, world, stream, slots_np, vq, codec, ratio, res["value"], res["ms_per_step"])
             res.update(line)
             try:
@@ -1689,7 +1774,16 @@ def parse_args(argv=None):
                     help="N=1 only: run the single rank in a SPAWNED child process (torch.multiprocessing.spawn + init_process_group('nccl', device_id=...)), "
                          "exactly as the ranks of --gpus N>1 are started, instead of in this process")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)      # CPU test of the launcher only (gloo, no kernels)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything next to the headline (parity with the oracle, stage / roofline figures, extra configurations, CPU "
+                         "baseline, side file of extras, the one-rank communicator at N=1, the all-reduce probe at N>1); "
+                         "--no-report / --no-extra / --no-cpu-baseline / --no-dist trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def main(argv=None):

@@ -47,6 +47,16 @@ def check(cond, msg):
         raise SystemExit("MISMATCH: " + msg)
 
 
+def cpu_vendor():
+    """the CPU vendor of this host (/proc/cpuinfo vendor_id; "" elsewhere): torch's vectorised CPU exp / log round alike on one
+    vendor's cores, not necessarily on another's"""
+    try:
+        with open("/proc/cpuinfo") as f:
+            return next((ln.split(":", 1)[1].strip() for ln in f if ln.startswith("vendor_id")), "")
+    except OSError:
+        return ""
+
+
 def main():
     out = {"torch_version": np.array(torch.__version__), "machine": np.array(platform.machine())}
     # 1. the restatement == the real class, bit for bit, on full-size images of every family, 1 and 8 threads
@@ -106,6 +116,9 @@ def main():
     path = os.path.join(HERE, "ties.npz")
     np.savez_compressed(path, **out)
     print(f"  wrote ties.npz ({os.path.getsize(path)} bytes)")
+    # the host whose torch build made (and reproduced) the maps above: the test's bit-for-bit branch runs on the same vendor only
+    np.savez_compressed(os.path.join(HERE, "ties_host.npz"), cpu_vendor=np.array(cpu_vendor()))
+    print(f"  wrote ties_host.npz (cpu_vendor {cpu_vendor()!r})")
 
 
 if __name__ == "__main__":

@@ -138,7 +138,7 @@ def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` without torch.distributed.run starts 2 ranks itself (here: the CPU stub of the hot
     path over gloo), rank 0 prints ONE JSON line with n_gpus == rccl_ranks == 2 and the whole-job value"""
     import json
-    r = _bench(["--gpus", "2", "--stub", "--steps", "3", "--warmup", "1"])
+    r = _bench(["--gpus", "2", "--stub", "--steps", "3", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -151,10 +151,10 @@ def test_bench_spawns_its_own_ranks():
     # intercepting torch.distributed while the region runs; every rank's own K steps by its own clock are on the line as well
     assert d["timed_collectives"] == 1 and len(d["per_rank_MPixels/s_device_events"]) == 2
     # N = 1 takes the same path: a one-rank communicator, `rccl_ranks` read back from it
-    one = json.loads(_bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1"]).stdout.strip())
+    one = json.loads(_bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--full"]).stdout.strip())
     assert one["n_gpus"] == 1 and one["rccl_ranks"] == 1 and len(one["per_rank_MPixels/s"]) == 1 and one["histogram_allreduce_us"] is not None
     assert one["timed_collectives"] == 0                         # one rank: nothing to exchange inside the region
-    solo = json.loads(_bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--no-dist"]).stdout.strip())
+    solo = json.loads(_bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--no-dist", "--full"]).stdout.strip())
     assert solo["rccl_ranks"] is None and solo["histogram_allreduce_us"] is None
 
 
@@ -173,7 +173,7 @@ def test_bench_mixed_workload_shards_the_stream():
         assert sum(v[0] for v in sh) == 24 and sum(v[1] for v in sh) == 8 and max(v[2] for v in sh) <= 1.35 * min(v[2] for v in sh)
     assert bench.mixed_share(sizes, 0, 1)[3] == 24 * 128 * 192 + 8 * 340 * 512          # latent vectors (DIV2K padded to 1360 x 2048)
     for gpus in (1, 2):
-        r = _bench(["--gpus", str(gpus), "--stub", "--workload", "mixed", "--steps", "3", "--warmup", "1"])
+        r = _bench(["--gpus", str(gpus), "--stub", "--workload", "mixed", "--steps", "3", "--warmup", "1", "--full"])
         assert r.returncode == 0, r.stdout + r.stderr
         lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
         assert len(lines) == 1, r.stdout
@@ -259,7 +259,7 @@ def test_bench_dry_nccl_spawns_the_single_rank_like_n_ranks():
     MASTER_* set by the parent -- the code path of `--gpus N` for N > 1 -- instead of in the calling process (here over gloo with
     the CPU stand-in for the kernels; the GPU form of this test is below)"""
     import json
-    r = _bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--dry-nccl"])
+    r = _bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--dry-nccl", "--full"])
     assert r.returncode == 0, r.stdout + r.stderr
     d = json.loads(r.stdout.strip())
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["spawned_ranks"] is True and d["timed_collectives"] == 0
@@ -271,7 +271,7 @@ def test_bench_dry_nccl_on_the_gpu():
     the ranks of an N > 1 run are started, exercised at N = 1 on whatever box runs the GPU tests; the line names the rank's PCI bus
     id and the RCCL version"""
     import json
-    r = _bench(["--gpus", "1", "--dry-nccl", "--steps", "6", "--warmup", "2", "--no-extra", "--no-cpu-baseline"], timeout=240)
+    r = _bench(["--gpus", "1", "--dry-nccl", "--steps", "6", "--warmup", "2", "--full", "--no-extra", "--no-cpu-baseline"], timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["spawned_ranks"] is True and d["bpp_match"] is True
@@ -287,8 +287,68 @@ def test_bench_two_gpus_for_real(workload):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible")
-    r = _bench(["--gpus", "2", "--workload", workload, "--steps", "6", "--warmup", "2", "--no-extra", "--no-cpu-baseline"], timeout=400)
+    r = _bench(["--gpus", "2", "--workload", workload, "--steps", "6", "--warmup", "2", "--full", "--no-extra", "--no-cpu-baseline"], timeout=400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["timed_collectives"] == 1
     assert len(set(d["rank_pci_bus_ids"])) == 2 and len(d["per_rank_MPixels/s"]) == 2
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) prints the headline fields and nothing it would need extra work for: no one-rank communicator,
+    no all-reduce probe; --dump-outputs writes the timed path's arrays (the CPU stand-in's: the usage histogram of the K steps)"""
+    import json
+    r = _bench(["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = json.loads(r.stdout.strip())
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["steps"] == 3
+    assert d["rccl_ranks"] is None and d["histogram_allreduce_us"] is None and "bpp_match" not in d and "extras_file" not in d
+    hist = np.load(tmp_path / "out" / "usage_histogram.npy")
+    assert hist.dtype == np.float64 and hist.shape == (1024,) and hist[7] == 3 * 64 * 64 * 64 and hist.sum() == hist[7]
+    assert _bench(["--gpus", "1", "--stub", "--steps", "0"]).returncode != 0
+
+
+def test_dump_outputs_keeps_to_its_budget(tmp_path):
+    """bench.dump_outputs: float32 / float64 only; past the budget the largest arrays become a fixed sample of their elements"""
+    import bench
+    arrays = {"big": np.arange(1 << 20, dtype=np.int64), "small": np.arange(6, dtype=np.int32).reshape(2, 3),
+              "bytes": np.arange(256, dtype=np.uint8), "f": np.linspace(0, 1, 1000, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, budget=1 << 20)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=1 << 20)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert sum(v.nbytes for v in got.values()) <= 1 << 20
+    assert got["small"].dtype == np.float64 and np.array_equal(got["small"], arrays["small"])
+    assert got["bytes"].dtype == np.float32 and np.array_equal(got["bytes"], arrays["bytes"])
+    assert got["f"].dtype == np.float32 and np.array_equal(got["f"], arrays["f"])
+    big = got["big"]
+    assert big.dtype == np.float64 and 0 < big.size < arrays["big"].size and np.all(np.diff(big) > 0)      # a sorted sample of the values
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))                              # the same sample every run
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_on_the_gpu(tmp_path, orc):
+    """--dump-outputs of the real timed path: the same arguments give the same arrays, and they are the LAST timed step's -- the
+    entropy maps of the slot that step ran on (two slots on two lanes: an odd and an even number of steps end on different ones)"""
+    import json
+    import bench
+    B, S = 8, 64
+    args = ["--gpus", "1", "--batch", str(B), "--size", str(S), "--slots", "2", "--warmup", "2"]
+    runs = {}
+    for tag, steps in (("a", 5), ("b", 5), ("c", 6)):
+        r = _bench(args + ["--steps", str(steps), "--dump-outputs", str(tmp_path / tag)], timeout=240)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and "bpp_match" not in d
+        runs[tag] = {f[:-4]: np.load(tmp_path / tag / f) for f in sorted(os.listdir(tmp_path / tag))}
+    a = runs["a"]
+    for k in ("e8", "e16", "mask_0", "mask_1", "mask_2", "mode", "z_q", "loss", "ind", "comp_streams", "comp_nbytes", "dec_ind",
+              "dec_mask_2", "dec_z_q", "dec_status", "usage_histogram"):
+        assert k in a, sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert set(runs["b"]) == set(a) and all(np.array_equal(a[k], runs["b"][k]) for k in a)
+    assert a["usage_histogram"].sum() == 5 * B * (S // 4) ** 2 and not a["dec_status"].any()
+    # steps 2 + 5 end on lane 0 (slot 0: bench.make_inputs seed 1000), 2 + 6 on lane 1 (slot 1: seed 1001)
+    for tag, seed in (("a", 1000), ("c", 1001)):
+        x = bench.make_inputs(B, S, S, seed)[0]
+        assert np.abs(runs[tag]["e8"] - orc.entropy(x, 8)).max() < 2e-6 and np.abs(runs[tag]["e16"] - orc.entropy(x, 16)).max() < 2e-6

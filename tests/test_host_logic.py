@@ -134,8 +134,19 @@ def test_argument_validation_happens_before_any_launch():
     # router refinement (round 4): the kernel recomputes torch.linspace(-1, 1, 32) itself, so the caller's bins must be THE
     # linspace to the bit (numpy's differs from torch's in the second half); segments that do not fit the LDS are refused
     tb = _lib.linspace_bins()
-    px = _lib.Pixels(16, 0, tb, 32, 0.01, None)
-    assert l.cgic_router_f32(one, one, 1, 4, 4, 0.1, 0.8, 1, one, one, one, None, None, ctypes.byref(px), None) in (_lib.ERR_HIP, _lib.OK)  # passes validation (no GPU here: the launch fails)
+    # the two calls that pass validation go on to launch: where a device exists they get real buffers (maps, masks, pixels of
+    # one 64x64 image) -- a launch on made-up addresses would read and write them on the GPU; without one the launch fails
+    if torch.cuda.is_available():
+        dev = torch.device("cuda", 0)
+        bufs = [torch.rand(1, 4, 4, device=dev), torch.rand(1, 8, 8, device=dev)] + \
+               [torch.zeros(1, n, n, dtype=torch.int32, device=dev) for n in (4, 8, 16)] + [torch.rand(1, 3, 64, 64, device=dev)]
+        e16, e8, mc, mm, mf = (ctypes.c_void_p(b.data_ptr()) for b in bufs[:5])
+        x, launched = bufs[5].data_ptr(), (_lib.OK,)
+    else:
+        e16 = e8 = mc = mm = mf = one
+        x, launched = 16, (_lib.ERR_HIP, _lib.OK)
+    px = _lib.Pixels(x, 0, tb, 32, 0.01, None)
+    assert l.cgic_router_f32(e16, e8, 1, 4, 4, 0.1, 0.8, 1, mc, mm, mf, None, None, ctypes.byref(px), None) in launched  # passes validation
     bad = (ctypes.c_float * 32)(*[v + (1e-7 if i == 20 else 0.0) for i, v in enumerate(tb)])
     assert l.cgic_router_f32(one, one, 1, 4, 4, 0.1, 0.8, 1, one, one, one, None, None, ctypes.byref(_lib.Pixels(16, 0, bad, 32, 0.01, None)), None) == _lib.ERR_UNSUPPORTED
     assert b"linspace" in l.cgic_last_error()
@@ -148,7 +159,9 @@ def test_argument_validation_happens_before_any_launch():
     assert l.cgic_router_refine_in_lds(64, 16, 16, 1) == 1 and l.cgic_router_refine_in_lds(8, 48, 48, 1) == 1 and l.cgic_router_refine_in_lds(8, 16, 16, 0) == 1
     assert l.cgic_router_refine_in_lds(64, 16, 16, 0) == 0 and l.cgic_router_refine_in_lds(1, 128, 85, 1) == 0
     assert l.cgic_router_refine_scratch_bytes(64, 16, 16, 0) == 20 * 64 * 256 + 16 + 64
-    assert l.cgic_router_f32(one, one, 1, 4, 4, 1.0, 0.0, 1, one, one, one, None, None, ctypes.byref(_lib.Pixels(16, 0, bad, 32, 0.01, None)), None) in (_lib.ERR_HIP, _lib.OK)  # mode 4 compares nothing: pixels ignored
+    assert l.cgic_router_f32(e16, e8, 1, 4, 4, 1.0, 0.0, 1, mc, mm, mf, None, None, ctypes.byref(_lib.Pixels(x, 0, bad, 32, 0.01, None)), None) in launched  # mode 4 compares nothing: pixels ignored
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
     assert l.cgic_entropy_maps_f32(one, 1, 24, 32, bins, 32, 0.01, one, one, None, None) == _lib.ERR_INVALID
     assert l.cgic_entropy_maps_f32(one, 1, 32, 32, bins, 32, 0.05, one, one, None, None) == _lib.ERR_UNSUPPORTED
 
