@@ -8,7 +8,11 @@ it requires that oracle/entropy_torch.py -- the torch-CPU restatement the GPU te
 arithmetic" on the GPU box -- reproduces the real class BIT FOR BIT (1 and 8 threads), on these images and on 256x256
 ones, and that the oracle's router reproduces the real router's masks from those maps.
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_ties.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_ties.py            # ties.npz, ties_host.npz, ties_batch.npz
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_ties.py batch      # ties_batch.npz only
+
+ties_batch.npz: batches of B = 16 images of 256x256 -- one flattened segment beyond a router workgroup's LDS, so the GPU's
+batch-global routing goes through router_big -- with the real router's masks over the flattened batch and per image.
 """
 import os
 import platform
@@ -121,5 +125,74 @@ def main():
     print(f"  wrote ties_host.npz (cpu_vendor {cpu_vendor()!r})")
 
 
+BATCH_SETS = ("flat_edges", "blocky8")          # (smooth8 does not compress below the 1 MiB a committed file may have)
+BATCH_RATIOS = ((0.1, 0.8), (0.0, 0.4))
+
+
+def near_threshold(e16, e8, c, m):
+    """entropies within 4e-6 of the threshold(s) the router draws at ratios (c, m) over the maps as given (RouterTriple.py:15-60)"""
+    e16, e8 = e16.astype(np.float64), e8.astype(np.float64)
+    near = 0
+    keep8 = np.ones_like(e8)
+    if c > 0:
+        v = np.sort(e16.ravel())
+        k = round(v.size * c)
+        t = v[k - 1 if k else 0]
+        near += int((np.abs(e16 - t) < 4e-6).sum())
+        keep8 = 1.0 - np.repeat(np.repeat((e16 < t).astype(np.float64), 2, -2), 2, -1)
+    if m > 0:
+        v = np.sort((e8 * keep8).ravel())
+        k = round(4 * e16.size * c + e8.size * m) if c > 0 else round(e8.size * m)
+        t = v[k - 1 if k else 0]
+        near += int((np.abs(e8 - t) < 4e-6).sum())
+    return near
+
+
+def batch_fixture():
+    """4. (B = 16) the flattened batch beyond one workgroup's LDS: per set, 16 images of 256x256 (uint8), and for each ratio the REAL
+    router's masks on the REAL Entropy maps over the flattened batch (the reference's encode(): RouterTriple.py:21,40,52,63) and
+    per image, as packed bits of the whole [B,1,h,w] mask.  The oracle (entropy_ref -> router) must give the same masks, and every
+    set must have entropies within 4e-6 of a threshold (the band decides something)."""
+    router = {r: TripleGrainFixedEntropyRouter(*r) for r in BATCH_RATIOS}
+    out = {"ratios": np.array(BATCH_RATIOS, np.float64), "sets": np.array(BATCH_SETS)}
+    fam = families(n=16, H=256, W=256, seed=47)
+    for name in BATCH_SETS:
+        x = fam[name]
+        u8 = np.round(x * 255.0).astype(np.uint8)
+        check(np.array_equal(u8.astype(np.float32) / 255.0, x), f"{name}: not exactly 8-bit")
+        xt = torch.from_numpy(x)
+        e8, e16 = Entropy(8)(xt), Entropy(16)(xt)
+        a8, a16 = orc.entropy_ref(x, 8), orc.entropy_ref(x, 16)
+        out[name + "_u8"] = u8
+        near = 0
+        for ri, (c, m) in enumerate(BATCH_RATIOS):
+            near_b = near_threshold(e16.numpy(), e8.numpy(), c, m)
+            near_i = sum(near_threshold(e16[b].numpy(), e8[b].numpy(), c, m) for b in range(16))
+            near += near_b + near_i
+            for how in ("batch", "per"):
+                sls = [slice(0, 16)] if how == "batch" else [slice(b, b + 1) for b in range(16)]
+                ref, orac = [[], [], []], [[], [], []]
+                for sl in sls:
+                    mask, _, _, mode = router[(c, m)](e16[sl], e8[sl])
+                    o = orc.router(a16[sl], a8[sl], c, m)
+                    check(o[4] == mode, f"{name} {how} ({c}, {m}): mode")
+                    for k in range(3):
+                        ref[k].append(mask[k].numpy())
+                        orac[k].append(o[k])
+                for k, g in enumerate("cmf"):
+                    r = np.concatenate(ref[k])
+                    check(np.array_equal(r, np.concatenate(orac[k])),
+                          f"{name} {how} ({c}, {m}) m{g}: the oracle's masks differ from the real router's on the real maps")
+                    out[f"{name}_r{ri}_{how}_m{g}"] = np.packbits(r.astype(np.uint8).reshape(-1))
+            out[f"{name}_r{ri}_mode"] = np.array(mode)
+            print(f"  {name} ({c}, {m}): within 4e-6 of a threshold: {near_b} batch-global, {near_i} per image")
+        check(near > 0, f"{name}: no entropy within 4e-6 of a threshold")
+    path = os.path.join(HERE, "ties_batch.npz")
+    np.savez_compressed(path, **out)
+    print(f"  wrote ties_batch.npz ({os.path.getsize(path)} bytes)")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] != ["batch"]:
+        main()
+    batch_fixture()

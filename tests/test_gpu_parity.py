@@ -327,6 +327,65 @@ def _tie_sets(n=64, flat=16):
     return sets
 
 
+_ORACLE_MAPS = {}
+
+
+def _oracle_maps(x):
+    """orc.entropy_ref(x, 8), orc.entropy_ref(x, 16) of float32 x [B,3,H,W] (numpy or a tensor), image by image: cached per image
+    (keyed on its shape and a hash of its bytes -- the maps do not depend on the ratios, and the tests reuse the same families) and
+    computed on a pool of at most 16 threads (the oracle is a ctypes library: its calls release the GIL)"""
+    import hashlib
+    from concurrent.futures import ThreadPoolExecutor
+    from oracle import cgic_oracle as orc
+    x = np.ascontiguousarray(x.cpu().numpy() if torch.is_tensor(x) else x, np.float32)
+    keys = [(x.shape[1:], hashlib.sha1(x[b].tobytes()).hexdigest()) for b in range(x.shape[0])]
+    todo = {}
+    for b, k in enumerate(keys):
+        if k not in _ORACLE_MAPS:
+            todo.setdefault(k, b)
+    if todo:
+        orc.lib()
+        one = lambda b: (orc.entropy_ref(x[b:b + 1], 8), orc.entropy_ref(x[b:b + 1], 16))
+        with ThreadPoolExecutor(max_workers=min(16, len(todo))) as pool:
+            for k, maps in zip(todo, pool.map(one, todo.values())):
+                _ORACLE_MAPS[k] = maps
+    return (np.concatenate([_ORACLE_MAPS[k][0] for k in keys]), np.concatenate([_ORACLE_MAPS[k][1] for k in keys]))
+
+
+def _oracle_route(x, c, m, per_image):
+    """the expected masks from PIXELS, by the CPU oracle alone (no GPU path): entropy maps in the reference's arithmetic
+    (cgic_oracle_entropy_ref) -> oracle router -> ([mask_c, mask_m, mask_f] int32 shaped like the GPU's, mode, (map8, map16))"""
+    from oracle import cgic_oracle as orc
+    o8, o16 = _oracle_maps(x)
+    mc, mm, mf, _, mode = orc.router(o16, o8, c, m, per_image=per_image, want_gate=False)
+    return [mc, mm, mf], mode, (o8, o16)
+
+
+def _diff(got, want):
+    """differing elements per mask (coarse, medium, fine) between GPU masks and oracle masks"""
+    return [int((g.cpu().numpy() != w).sum()) for g, w in zip(got, want)]
+
+
+def _same_maps(r8, r16, omaps):
+    """reference-order maps of the GPU == the oracle's, bit for bit"""
+    return (np.array_equal(r8.cpu().numpy().view(np.int32), omaps[0].view(np.int32))
+            and np.array_equal(r16.cpu().numpy().view(np.int32), omaps[1].view(np.int32)))
+
+
+def _unrefined_diff(e16, e8, r16, r8, want, c, m, per_image):
+    """mask elements routed differently from the oracle WITHOUT the refinement, from the default maps and from the reference-order
+    maps moved by up to +-0.95 of the default kernel's error bound by value (refine_delta: maps the refinement has to accept) --
+    what the threshold band decides on this content (the non-vacuity count of the refinement tests): (default, perturbed)"""
+    plain = cg.TripleGrainFixedEntropyRouter(c, m, per_image=per_image)
+    plain.refine = False
+    g = torch.Generator(device=DEV).manual_seed(5)
+    dl = lambda r: torch.clamp(7e-7 + 0.01 * torch.clamp(r - 1e-4, min=0.0), max=2e-6)
+    p8 = r8 + (torch.rand(r8.shape, device=DEV, generator=g) - 0.5) * 1.9 * dl(r8)
+    p16 = r16 + (torch.rand(r16.shape, device=DEV, generator=g) - 0.5) * 1.9 * dl(r16)
+    return (sum(_diff(plain(e16.clone(), e8.clone(), want_gate=False)[0], want)),
+            sum(_diff(plain(p16, p8, want_gate=False)[0], want)))
+
+
 def test_mask_flips_on_tie_heavy_content(orc):
     """pixels -> masks on 8-bit / smooth / flat / blocky content + two 768x768 tiles, DEFAULT path (entropy_maps -> router with the
     pixels: the threshold-band refinement) against the reference's own torch-CPU arithmetic (oracle/entropy_torch.py, pinned bit
@@ -378,35 +437,46 @@ def test_refined_router_equals_router_on_reference_arithmetic_maps(ratio):
     every patch within the band of a threshold is re-evaluated with the arithmetic of cgic_entropy_maps_ref_f32, everything
     outside the band keeps its side.  All four modes that compare (0, 1, 2, 3), stand-alone and VQ-fused launch, fp32 pixels and
     uint8 frames, images and 768x768 tiles (several workgroups per image), plus maps perturbed by +-0.95 of the kernel's error
-    bound by value (refine_delta: what the band is made of): the masks must not move."""
+    bound by value (refine_delta: what the band is made of): the masks must not move.  Every form also equals the CPU oracle's
+    masks from the same pixels (_oracle_route), and the reference-order maps equal the oracle's maps bit for bit."""
     from control_gic_amd.quantize import vq_forward_route
     c, m = ratio
     router = cg.TripleGrainFixedEntropyRouter(c, m, per_image=True)
     rng = np.random.default_rng(int(1000 * c + 10 * m))
     w = _t(rng.standard_normal((1024, 4), dtype=np.float32))
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     for name, x in _tie_sets(n=24, flat=6).items():
         xd = torch.from_numpy(x).to(DEV)
         B, _, H, W = xd.shape
         e8, e16 = cg.entropy_maps(xd)
         r8, r16 = cg.entropy_maps(xd, reference_order=True)
         want, _, _, mode = router(r16, r8, want_gate=False)
+        owant, omode, omaps = _oracle_route(x, c, m, per_image=True)
+        assert _same_maps(r8, r16, omaps), (name, "reference-order maps vs oracle entropy_ref")
+        assert mode == omode and _diff(want, owant) == [0, 0, 0], (name, ratio, "reference-order maps", _diff(want, owant))
+        unrefined += _unrefined_diff(e16, e8, r16, r8, owant, c, m, True)
         got = router(e16, e8, want_gate=False, pixels=xd)[0]
         assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, [int((a != b).sum()) for a, b in zip(got, want)])
+        assert _diff(got, owant) == [0, 0, 0], (name, ratio, "oracle", _diff(got, owant))
         z = _t(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32))
         fused = vq_forward_route(z, w, 0.25, True, e16, e8, c, m, per_image=True, pixels=xd)[3]
         assert all(torch.equal(a, b) for a, b in zip(fused, want)), (name, ratio, "fused")
+        assert _diff(fused, owant) == [0, 0, 0], (name, ratio, "fused vs oracle", _diff(fused, owant))
         # the maps may sit anywhere within the kernel's error bound (by value: refine_delta) of the reference arithmetic
         dl = lambda r: torch.clamp(7e-7 + 0.01 * torch.clamp(r - 1e-4, min=0.0), max=2e-6)
         n8 = (torch.rand(e8.shape, device=DEV) - 0.5) * 1.9 * dl(r8)
         n16 = (torch.rand(e16.shape, device=DEV) - 0.5) * 1.9 * dl(r16)
         got = router(r16 + n16, r8 + n8, want_gate=False, pixels=xd)[0]
         assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, "perturbed")
+        assert _diff(got, owant) == [0, 0, 0], (name, ratio, "perturbed vs oracle", _diff(got, owant))
         if name in ("smooth8", "tiles_768"):
             frames = (xd * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
             x2, f8, f16 = cg.entropy_maps_u8(frames)
             assert torch.equal(x2, xd) and torch.equal(f8, e8) and torch.equal(f16, e16)
             got = router(f16, f8, want_gate=False, pixels=frames)[0]
             assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, "uint8 frames")
+            assert _diff(got, owant) == [0, 0, 0], (name, ratio, "uint8 frames vs oracle", _diff(got, owant))
+    assert unrefined.sum() > 0, (ratio, unrefined)       # (the band decides something: default maps, or maps within the error bound, flip elements)
 
 
 TIES_SMALL = ["noise8", "smooth8", "flat_edges", "blocky8"]
@@ -453,6 +523,11 @@ def test_pixels_to_masks_equal_the_reference_routers_own_masks(golden, name):
     z = _t(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32))
     same(vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True, pixels=xd)[3], ref, "fused launch, fp32 pixels")
     same(vq_forward_route(z, w, 0.25, True, f16, f8, 0.1, 0.8, per_image=True, pixels=frames)[3], ref, "fused launch, uint8 frames")
+    for q in (True, False):             # both variants of the fused launch, whatever _lib.REFINE_FUSED_QUEUES defaults to
+        same(vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True, pixels=xd, refine_queues=q)[3], ref,
+             f"fused launch, fp32 pixels, refine_queues={q}")
+        same(vq_forward_route(z, w, 0.25, True, f16, f8, 0.1, 0.8, per_image=True, pixels=frames, refine_queues=q)[3], ref,
+             f"fused launch, uint8 frames, refine_queues={q}")
     # reference-order maps decide by themselves
     r8, r16 = cg.entropy_maps(xd, reference_order=True)
     plain = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=True)
@@ -473,7 +548,9 @@ def test_batch_global_routing_is_refined_beyond_one_workgroups_lds(B, ratio):
     256x256 are one segment of 16 384 + 65 536 entropies -- beyond a workgroup's LDS -- and are refined through patched copies
     of the maps (cgic_router.hip: router_big): masks equal to batch-global routing on the reference-arithmetic maps, on the
     tie-heavy families, in every mode that compares, stand-alone and through the VQ + router entry point, fp32 pixels and
-    uint8 frames, and with maps perturbed within the kernel's error bound.  Also one untiled 1024x1280 image routed per image."""
+    uint8 frames, and with maps perturbed within the kernel's error bound.  Also one untiled 1024x1280 image routed per image.
+    Every form also equals the CPU oracle's batch-global masks from the same pixels (_oracle_route(per_image=False)), and the
+    reference-order maps equal the oracle's maps bit for bit."""
     from control_gic_amd.quantize import vq_forward_route
     c, m = ratio
     assert cg._lib.lib().cgic_router_refine_supported(B, 16, 16, 0) == 1 and cg._lib.lib().cgic_router_refine_in_lds(B, 16, 16, 0) == 0
@@ -481,17 +558,25 @@ def test_batch_global_routing_is_refined_beyond_one_workgroups_lds(B, ratio):
     rng = np.random.default_rng(B + int(100 * c))
     w = _t(rng.standard_normal((1024, 4), dtype=np.float32))
     sets = _tie_sets(n=B, flat=B)
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     for name in ("smooth8", "flat_edges", "noise8"):
-        xd = torch.from_numpy(np.ascontiguousarray(sets[name][:B])).to(DEV)
+        x = np.ascontiguousarray(sets[name][:B])
+        xd = torch.from_numpy(x).to(DEV)
         e8, e16 = cg.entropy_maps(xd)
         r8, r16 = cg.entropy_maps(xd, reference_order=True)
         want, _, _, mode = router(r16, r8, want_gate=False)
+        owant, omode, omaps = _oracle_route(x, c, m, per_image=False)
+        assert _same_maps(r8, r16, omaps), (name, "reference-order maps vs oracle entropy_ref")
+        assert mode == omode and _diff(want, owant) == [0, 0, 0], (name, ratio, "reference-order maps", _diff(want, owant))
+        unrefined += _unrefined_diff(e16, e8, r16, r8, owant, c, m, False)
         got, gate, _, mode2 = router(e16, e8, pixels=xd)
         assert mode == mode2 and all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, [int((a != b).sum()) for a, b in zip(got, want)])
+        assert _diff(got, owant) == [0, 0, 0], (name, ratio, "oracle", _diff(got, owant))
         assert torch.equal(gate, router(r16, r8)[1])
         z = _t(rng.standard_normal((B, 4, 64, 64), dtype=np.float32))
         zq, loss, idx, fused, _, _ = vq_forward_route(z, w, 0.25, True, e16, e8, c, m, per_image=False, pixels=xd)
         assert all(torch.equal(a, b) for a, b in zip(fused, want)), (name, ratio, "through cgic_vq_forward_route_f32")
+        assert _diff(fused, owant) == [0, 0, 0], (name, ratio, "cgic_vq_forward_route_f32 vs oracle", _diff(fused, owant))
         zq0, loss0, idx0 = cg.quantize._vq_forward(z, w, 0.25, True, None)
         assert torch.equal(idx, idx0) and torch.equal(zq, zq0) and torch.equal(loss, loss0)
         dl = lambda r: torch.clamp(7e-7 + 0.01 * torch.clamp(r - 1e-4, min=0.0), max=2e-6)
@@ -499,29 +584,38 @@ def test_batch_global_routing_is_refined_beyond_one_workgroups_lds(B, ratio):
         n16 = (torch.rand(e16.shape, device=DEV) - 0.5) * 1.9 * dl(r16)
         got = router(r16 + n16, r8 + n8, want_gate=False, pixels=xd)[0]
         assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, "perturbed")
+        assert _diff(got, owant) == [0, 0, 0], (name, ratio, "perturbed vs oracle", _diff(got, owant))
         if name == "smooth8":
             frames = (xd * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
             _, f8, f16 = cg.entropy_maps_u8(frames)
             got = router(f16, f8, want_gate=False, pixels=frames)[0]
             assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, ratio, "uint8 frames")
+            assert _diff(got, owant) == [0, 0, 0], (name, ratio, "uint8 frames vs oracle", _diff(got, owant))
     if B == 16:
         from oracle.content_families import families
-        xl = torch.from_numpy(families(n=1, H=1024, W=1280, seed=5)["smooth8"]).to(DEV)
+        xn = families(n=1, H=1024, W=1280, seed=5)["smooth8"]
+        xl = torch.from_numpy(xn).to(DEV)
         per = cg.TripleGrainFixedEntropyRouter(c, m, per_image=True)
         assert cg._lib.lib().cgic_router_refine_in_lds(1, 64, 80, 1) == 0
         e8, e16 = cg.entropy_maps(xl)
         r8, r16 = cg.entropy_maps(xl, reference_order=True)
         want = per(r16, r8, want_gate=False)[0]
+        owant, _, omaps = _oracle_route(xn, c, m, per_image=True)
+        assert _same_maps(r8, r16, omaps), ("1024x1280", "reference-order maps vs oracle entropy_ref")
+        unrefined += _unrefined_diff(e16, e8, r16, r8, owant, c, m, True)
         got = per(e16, e8, want_gate=False, pixels=xl)[0]
         assert all(torch.equal(a, b) for a, b in zip(got, want)), ("1024x1280", ratio)
+        assert _diff(got, owant) == [0, 0, 0], ("1024x1280", ratio, "oracle", _diff(got, owant))
+    assert unrefined.sum() > 0, (B, ratio, unrefined)    # (the band decides something: default maps, or maps within the error bound, flip elements)
 
 
 def test_hotcall_refines_images_beyond_768():
     """cgic_compress_image on an image routed as one segment beyond the LDS used to route from the UNREFINED maps
     without a word; it now refines through patched copies (HotCall allocates ws_refine) -- and a caller of the C entry point who
-    leaves ws_refine out is refused"""
+    leaves ws_refine out is refused.  The masks equal the CPU oracle's from the same pixels."""
     from oracle.content_families import families
-    xl = torch.from_numpy(families(n=2, H=1024, W=1024, seed=9)["smooth8"]).to(DEV)
+    xn = families(n=2, H=1024, W=1024, seed=9)["smooth8"]
+    xl = torch.from_numpy(xn).to(DEV)
     B, _, H, W = xl.shape
     rng = np.random.default_rng(0)
     vq = cg.VectorQuantizer(1024, 4, beta=0.25).to(DEV).eval()
@@ -532,6 +626,11 @@ def test_hotcall_refines_images_beyond_768():
     r8, r16 = cg.entropy_maps(xl, reference_order=True)
     want = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=True)(r16, r8, want_gate=False)[0]
     assert all(torch.equal(a, b) for a, b in zip(out["mask"], want))
+    owant, omode, omaps = _oracle_route(xn, 0.1, 0.8, per_image=True)
+    assert _same_maps(r8, r16, omaps), "reference-order maps vs oracle entropy_ref"
+    assert out["mode"] == omode and _diff(out["mask"], owant) == [0, 0, 0], _diff(out["mask"], owant)
+    e8, e16 = cg.entropy_maps(xl)
+    assert _unrefined_diff(e16, e8, r16, r8, owant, 0.1, 0.8, True)[0] > 0     # (the band decides: the default maps alone flip elements)
     hc._io.ws_refine, hc._io.ws_refine_bytes = None, 0
     with pytest.raises(cg.CgicError, match="scratch"):
         hc(xl, z)
@@ -542,33 +641,43 @@ def test_fused_launch_with_refinement_queues_gives_the_same_masks():
     refinement queues (published patch lists, the routers that are done help): masks == the plain variant's == routing on the
     reference-arithmetic maps, on every tie-heavy family, repeated launches over the same header slots, fp32 pixels and uint8
     frames; VQ outputs untouched.  HotPathPipeline(refine_queues="auto") picks the variant from a batch of the stream: the
-    smooth family (dozens of non-constant patches inside a band) takes the queues, noise does not."""
+    smooth family (dozens of non-constant patches inside a band) takes the queues, noise does not.  Every form also equals the
+    CPU oracle's masks from the same pixels, and the reference-order maps equal the oracle's maps bit for bit."""
     from control_gic_amd.quantize import vq_forward_route
     rng = np.random.default_rng(11)
     w = _t(rng.standard_normal((1024, 4), dtype=np.float32))
     vq = cg.VectorQuantizer(1024, 4, beta=0.25).to(DEV).eval()
     vq.embedding.weight.data.copy_(w)
     picks = {}
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     for name, x in _tie_sets(n=64, flat=16).items():
         xd = torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
         B, _, H, W = xd.shape
         e8, e16 = cg.entropy_maps(xd)
         r8, r16 = cg.entropy_maps(xd, reference_order=True)
         want = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=True)(r16, r8, want_gate=False)[0]
+        owant, _, omaps = _oracle_route(x, 0.1, 0.8, per_image=True)
+        assert _same_maps(r8, r16, omaps), (name, "reference-order maps vs oracle entropy_ref")
+        assert _diff(want, owant) == [0, 0, 0], (name, "reference-order maps", _diff(want, owant))
+        unrefined += _unrefined_diff(e16, e8, r16, r8, owant, 0.1, 0.8, True)
         z = _t(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32))
         plain = vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True, pixels=xd, refine_queues=False)
         for rep in range(3):
             q = vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True, pixels=xd, refine_queues=True)
             assert all(torch.equal(a, b) for a, b in zip(q[3], want)), (name, rep, [int((a != b).sum()) for a, b in zip(q[3], want)])
+            assert _diff(q[3], owant) == [0, 0, 0], (name, rep, "queues vs oracle", _diff(q[3], owant))
             assert torch.equal(q[0], plain[0]) and torch.equal(q[1], plain[1]) and torch.equal(q[2], plain[2])
         assert all(torch.equal(a, b) for a, b in zip(plain[3], want)), name
+        assert _diff(plain[3], owant) == [0, 0, 0], (name, "plain vs oracle", _diff(plain[3], owant))
         if name == "smooth8":
             frames = (xd * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
             _, f8, f16 = cg.entropy_maps_u8(frames)
             q = vq_forward_route(z, w, 0.25, True, f16, f8, 0.1, 0.8, per_image=True, pixels=frames, refine_queues=True)
             assert all(torch.equal(a, b) for a, b in zip(q[3], want)), (name, "uint8 frames")
+            assert _diff(q[3], owant) == [0, 0, 0], (name, "uint8 frames vs oracle", _diff(q[3], owant))
         picks[name] = cg.pipeline.HotPathPipeline(vq, 0.1, 0.8).decide(xd)
     assert picks["smooth8"] is True and picks["noise8"] is False and picks["flat_edges"] is False, picks
+    assert unrefined[0] > 0, unrefined                   # (the band decides: the default maps alone flip elements)
 
 
 def test_refinement_queues_change_nothing_and_survive_concurrent_launches():
@@ -576,26 +685,35 @@ def test_refinement_queues_change_nothing_and_survive_concurrent_launches():
     owner publishes its patch list; the other row bands of a tile and router workgroups that are done take patches; results as
     tagged 8-byte granules): masks identical with and without the queues and to the routing on the reference-arithmetic maps --
     batches of images, 768x768 tiles (eight row bands per tile share one select), uint8 frames, repeated launches over the same
-    header slots, and four streams at once (launches of different streams share nothing but the library's slot pools)."""
+    header slots, and four streams at once (launches of different streams share nothing but the library's slot pools).  Every form
+    also equals the CPU oracle's masks from the same pixels, and the reference-order maps equal the oracle's maps bit for bit."""
     from control_gic_amd import _lib
     router = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=True)
     sets = _tie_sets(n=32, flat=8)
     assert "tiles_768" in sets
-    want = {}
+    want, oracle = {}, {}
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     for name, x in sets.items():
         xd = torch.from_numpy(x).to(DEV)
         e8, e16 = cg.entropy_maps(xd)
         r8, r16 = cg.entropy_maps(xd, reference_order=True)
         want[name] = (xd, e8, e16, [m.clone() for m in router(r16, r8, want_gate=False, pixels=None)[0]])
+        oracle[name], _, omaps = _oracle_route(x, 0.1, 0.8, per_image=True)
+        assert _same_maps(r8, r16, omaps), (name, "reference-order maps vs oracle entropy_ref")
+        assert _diff(want[name][3], oracle[name]) == [0, 0, 0], (name, "reference-order maps", _diff(want[name][3], oracle[name]))
+        unrefined += _unrefined_diff(e16, e8, r16, r8, oracle[name], 0.1, 0.8, True)
+    assert unrefined.sum() > 0, unrefined                # (the band decides something: default maps, or maps within the error bound, flip elements)
     try:
         for name, (xd, e8, e16, ref) in want.items():
             _lib.REFINE_QUEUES = False
             plain = router(e16, e8, want_gate=False, pixels=xd)[0]
             assert all(torch.equal(a, b) for a, b in zip(plain, ref)), (name, "in-workgroup")
+            assert _diff(plain, oracle[name]) == [0, 0, 0], (name, "in-workgroup vs oracle", _diff(plain, oracle[name]))
             _lib.REFINE_QUEUES = True
             for rep in range(4):                      # (the same header slots again and again: whatever a launch leaves must read as "nothing to claim")
                 got = router(e16, e8, want_gate=False, pixels=xd)[0]
                 assert all(torch.equal(a, b) for a, b in zip(got, ref)), (name, "queues", rep, [int((a != b).sum()) for a, b in zip(got, ref)])
+                assert _diff(got, oracle[name]) == [0, 0, 0], (name, "queues vs oracle", rep, _diff(got, oracle[name]))
         # four streams, eight rounds: every stream routes every set
         streams = [torch.cuda.Stream() for _ in range(4)]
         torch.cuda.synchronize()
@@ -610,12 +728,14 @@ def test_refinement_queues_change_nothing_and_survive_concurrent_launches():
         torch.cuda.synchronize()
         for name, got in outs:
             assert all(torch.equal(a, b) for a, b in zip(got, want[name][3])), (name, "concurrent streams")
+            assert _diff(got, oracle[name]) == [0, 0, 0], (name, "concurrent streams vs oracle")
         # uint8 frames through the queues
         xd = want["smooth8"][0]
         frames = (xd * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
         _, f8, f16 = cg.entropy_maps_u8(frames)
         got = router(f16, f8, want_gate=False, pixels=frames)[0]
         assert all(torch.equal(a, b) for a, b in zip(got, want["smooth8"][3]))
+        assert _diff(got, oracle["smooth8"]) == [0, 0, 0], ("uint8 frames vs oracle", _diff(got, oracle["smooth8"]))
     finally:
         _lib.REFINE_QUEUES = True
 
@@ -653,7 +773,9 @@ def test_row_bands_split_a_band_in_the_fused_launch():
     identical to the launch without the scratch (every band evaluates everything) and to the routing on the reference-arithmetic
     maps: all four families as 768x768 tiles, other tile shapes and band counts (8, 6, 3, 2 row bands; 32 to 64 patch rows), uint8
     frames, repeated launches over the same header slots, four streams at once.  (The launch runs the router in two attempts: the
-    plain instantiation first, which leaves when a band is long, then the split one from the top: both outcomes are exercised.)"""
+    plain instantiation first, which leaves when a band is long, then the split one from the top: both outcomes are exercised.)
+    Every form also equals the CPU oracle's masks from the same pixels, and the reference-order maps equal the oracle's maps bit
+    for bit (768x768, 512x1024, 1024x512, 640x656, 512x768)."""
     from control_gic_amd import _lib
     from control_gic_amd.quantize import vq_forward_route
     from oracle.content_families import families
@@ -672,9 +794,10 @@ def test_row_bands_split_a_band_in_the_fused_launch():
     t = families(n=12, H=512, W=768, seed=15)
     cases["512x768 x24 (2 bands)"] = np.concatenate([t["smooth8"], t["flat_edges"]])
     keep = _lib.REFINE_SPLIT_MIN_PATCHES, _lib.REFINE_QUEUES
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     try:
         _lib.REFINE_SPLIT_MIN_PATCHES = 1024
-        ready = {}
+        ready, oracle = {}, {}
         for name, x in cases.items():
             xd = torch.from_numpy(x).to(DEV)
             B, _, H, W = xd.shape
@@ -682,35 +805,48 @@ def test_row_bands_split_a_band_in_the_fused_launch():
             e8, e16 = cg.entropy_maps(xd)
             r8, r16 = cg.entropy_maps(xd, reference_order=True)
             want = [m.clone() for m in router(r16, r8, want_gate=False, pixels=None)[0]]
+            oracle[name], _, omaps = _oracle_route(x, 0.1, 0.8, per_image=True)
+            assert _same_maps(r8, r16, omaps), (name, "reference-order maps vs oracle entropy_ref")
+            assert _diff(want, oracle[name]) == [0, 0, 0], (name, "reference-order maps", _diff(want, oracle[name]))
+            unrefined += _unrefined_diff(e16, e8, r16, r8, oracle[name], 0.1, 0.8, True)
             z = _t(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32))
             f = lambda z=z, e16=e16, e8=e8, xd=xd: vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True, pixels=xd)[3]
             _lib.REFINE_QUEUES = False
             plain = f()
             assert all(torch.equal(a, b) for a, b in zip(plain, want)), (name, "every band evaluates everything")
+            assert _diff(plain, oracle[name]) == [0, 0, 0], (name, "every band evaluates everything, vs oracle", _diff(plain, oracle[name]))
             _lib.REFINE_QUEUES = True
             for rep in range(4):
                 got = f()
                 assert all(torch.equal(a, b) for a, b in zip(got, want)), (name, "split", rep, [int((a != b).sum()) for a, b in zip(got, want)])
+                assert _diff(got, oracle[name]) == [0, 0, 0], (name, "split vs oracle", rep, _diff(got, oracle[name]))
             ready[name] = (f, want)
         # blocky tiles, medium grain only, the quantile among the constant blocks: hundreds of distinct grays in the band -- more than
         # the table of shared grays holds; the row bands must still agree on the member list (found by tools/stress_refine.py)
         r2 = cg.TripleGrainFixedEntropyRouter(0.0, 0.25, per_image=True)
         for seed in (21, 22):
             blocks = np.random.default_rng(seed).integers(0, 256, (7, 3, 96, 96)).astype(np.float32) / 255.0        # every 8x8 block one colour
-            xd = torch.from_numpy(np.ascontiguousarray(np.repeat(np.repeat(blocks, 8, axis=2), 8, axis=3))).to(DEV)
+            xb = np.ascontiguousarray(np.repeat(np.repeat(blocks, 8, axis=2), 8, axis=3))
+            xd = torch.from_numpy(xb).to(DEV)
             e8, e16 = cg.entropy_maps(xd)
             r8, r16 = cg.entropy_maps(xd, reference_order=True)
             want = r2(r16, r8, want_gate=False, pixels=None)[0]
+            owant, _, omaps = _oracle_route(xb, 0.0, 0.25, per_image=True)
+            assert _same_maps(r8, r16, omaps), ("blocky", seed, "reference-order maps vs oracle entropy_ref")
+            assert _diff(want, owant) == [0, 0, 0], ("blocky", seed, "reference-order maps", _diff(want, owant))
+            unrefined += _unrefined_diff(e16, e8, r16, r8, owant, 0.0, 0.25, True)
             z = _t(rng.standard_normal((7, 4, 192, 192), dtype=np.float32))
             for rep in range(3):
                 got = vq_forward_route(z, w, 0.25, True, e16, e8, 0.0, 0.25, per_image=True, pixels=xd)[3]
                 assert all(torch.equal(a, b) for a, b in zip(got, want)), ("blocky, more grays than table slots", seed, rep, [int((a != b).sum()) for a, b in zip(got, want)])
+                assert _diff(got, owant) == [0, 0, 0], ("blocky, more grays than table slots, vs oracle", seed, rep, _diff(got, owant))
         xd = torch.from_numpy(cases["768x768 x8"]).to(DEV)
         frames = (xd * 255.0).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
         _, f8, f16 = cg.entropy_maps_u8(frames)
         z = _t(rng.standard_normal((8, 4, 192, 192), dtype=np.float32))
         got = vq_forward_route(z, w, 0.25, True, f16, f8, 0.1, 0.8, per_image=True, pixels=frames)[3]
         assert all(torch.equal(a, b) for a, b in zip(got, ready["768x768 x8"][1])), "uint8 frames"
+        assert _diff(got, oracle["768x768 x8"]) == [0, 0, 0], ("uint8 frames vs oracle", _diff(got, oracle["768x768 x8"]))
         streams = [torch.cuda.Stream() for _ in range(4)]
         torch.cuda.synchronize()
         outs, names = [], list(ready)
@@ -722,8 +858,10 @@ def test_row_bands_split_a_band_in_the_fused_launch():
         torch.cuda.synchronize()
         for name, got in outs:
             assert all(torch.equal(a, b) for a, b in zip(got, ready[name][1])), (name, "concurrent streams")
+            assert _diff(got, oracle[name]) == [0, 0, 0], (name, "concurrent streams vs oracle")
     finally:
         _lib.REFINE_SPLIT_MIN_PATCHES, _lib.REFINE_QUEUES = keep
+    assert unrefined[0] > 0, unrefined                   # (the band decides: the default maps alone flip elements)
 
 
 def test_flat_map_and_constant_patch_shortcut():
@@ -748,13 +886,20 @@ def test_flat_map_and_constant_patch_shortcut():
     e8b, _ = cg.entropy_maps(x2)
     assert torch.equal(f8._cgic_flat8.nan_to_num(-1.0), e8b._cgic_flat8.nan_to_num(-1.0))
     r8, r16 = cg.entropy_maps(xd, reference_order=True)
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
     for c, m in ((0.1, 0.8), (0.5, 0.3), (0.0, 0.6), (0.2, 0.0)):
         router = cg.TripleGrainFixedEntropyRouter(c, m, per_image=True)
         want = router(r16, r8, want_gate=False)[0]
+        owant, _, omaps = _oracle_route(x, c, m, per_image=True)        # (the CPU oracle from the same pixels)
+        assert _same_maps(r8, r16, omaps), "reference-order maps vs oracle entropy_ref"
+        assert _diff(want, owant) == [0, 0, 0], (c, m, "reference-order maps", _diff(want, owant))
+        unrefined += _unrefined_diff(e16, e8, r16, r8, owant, c, m, True)
         with_flat = router(e16, e8, want_gate=False)[0]                                   # pixels + flat8 ride on the maps
         no_flat = router(e16, e8, want_gate=False, pixels=xd, flat8=torch.full_like(e8, float("nan")))[0]
         assert all(torch.equal(a, b) for a, b in zip(with_flat, want)), (c, m)
         assert all(torch.equal(a, b) for a, b in zip(no_flat, want)), (c, m)
+        assert _diff(with_flat, owant) == [0, 0, 0] and _diff(no_flat, owant) == [0, 0, 0], (c, m, "oracle")
+    assert unrefined[0] > 0, unrefined                   # (the band decides: the default maps alone flip elements)
 
 
 def test_refinement_plumbing_and_limits():
@@ -790,12 +935,120 @@ def test_refinement_plumbing_and_limits():
     a = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=False)(b16, b8)[0]
     b = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=False)(b16.clone(), b8.clone(), pixels=big)[0]
     assert all(torch.equal(p, q) for p, q in zip(a, want_big)) and all(torch.equal(p, q) for p, q in zip(b, want_big))
+    # ... and they are the CPU oracle's batch-global masks from the same pixels
+    owant, _, omaps = _oracle_route(big, 0.1, 0.8, per_image=False)
+    assert _same_maps(q8, q16, omaps), "reference-order maps vs oracle entropy_ref"
+    assert _diff(a, owant) == [0, 0, 0] and _diff(b, owant) == [0, 0, 0], (_diff(a, owant), _diff(b, owant))
+    assert sum(_unrefined_diff(b16, b8, q16, q8, owant, 0.1, 0.8, False)) > 0     # (the band decides something here)
     # NaN pixels: the NaN patches sort last in both; nothing hangs
     xn = x.clone()
     xn[0, 0, 5, 7] = float("nan")
     e8, e16 = cg.entropy_maps(xn)
     r8, r16 = cg.entropy_maps(xn, reference_order=True)
     assert all(torch.equal(p, q) for p, q in zip(router(e16, e8, pixels=xn)[0], router(r16, r8)[0]))
+
+
+@pytest.mark.parametrize("name", ["flat_edges", "blocky8"])
+def test_batch_of_sixteen_equals_the_reference_routers_own_masks(golden, name):
+    """tests/golden/ties_batch.npz (make_golden_ties.py, section 4): 16 images of 256x256 -- one flattened segment beyond a router
+    workgroup's LDS, so batch-global routing goes through router_big -- with the masks of the REAL TripleGrainFixedEntropyRouter
+    on the REAL Entropy maps, over the flattened batch (encode(): RouterTriple.py:21,40,52,63) and per image, at two ratios.
+    Every batch-global form (stand-alone router with fp32 pixels, pixels riding on the maps, uint8 frames, the VQ + router entry
+    point) and every per-image form (the same, plus the fused launch with and without refinement queues) gives exactly these."""
+    from control_gic_amd.quantize import vq_forward_route
+    assert cg._lib.lib().cgic_router_refine_in_lds(16, 16, 16, 0) == 0
+    g = golden("ties_batch")
+    u8 = g[name + "_u8"]
+    B, _, H, W = u8.shape
+    assert B == 16
+    xd = torch.from_numpy(u8.astype(np.float32) / 255.0).to(DEV)
+    frames = torch.from_numpy(np.ascontiguousarray(u8.transpose(0, 2, 3, 1))).to(DEV)
+    e8, e16 = cg.entropy_maps(xd)
+    r8, r16 = cg.entropy_maps(xd, reference_order=True)
+    x2, f8, f16 = cg.entropy_maps_u8(frames)
+    assert torch.equal(x2, xd)
+    rng = np.random.default_rng(16)
+    w = _t(rng.standard_normal((1024, 4), dtype=np.float32))
+    z = _t(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32))
+    shapes = [(H // 16, W // 16), (H // 8, W // 8), (H // 4, W // 4)]
+    unrefined = np.zeros(2, np.int64)     # elements off the oracle, routed unrefined: (default maps, perturbed maps)
+    for ri, (c, m) in enumerate(g["ratios"]):
+        c, m = float(c), float(m)
+        mode = int(g[f"{name}_r{ri}_mode"])
+        for how, per_image in (("batch", False), ("per", True)):
+            ref = [unpack_mask(g[f"{name}_r{ri}_{how}_m{k}"], (B, 1) + sh) for k, sh in zip("cmf", shapes)]
+
+            def same(out, what):
+                masks, mode_ = (out[3], out[5]) if len(out) == 6 else (out[0], out[3])
+                assert mode_ == mode and _diff(masks, ref) == [0, 0, 0], (name, (c, m), how, what, _diff(masks, ref))
+
+            router = cg.TripleGrainFixedEntropyRouter(c, m, per_image=per_image)
+            same(router(e16, e8, want_gate=False, pixels=xd), "stand-alone router, fp32 pixels")
+            same(router(e16, e8, want_gate=False), "stand-alone router, pixels riding on the maps")
+            same(router(f16, f8, want_gate=False, pixels=frames), "stand-alone router, uint8 frames")
+            if per_image:
+                for q in (True, False):
+                    same(vq_forward_route(z, w, 0.25, True, e16, e8, c, m, per_image=True, pixels=xd, refine_queues=q),
+                         f"fused launch, fp32 pixels, refine_queues={q}")
+                    same(vq_forward_route(z, w, 0.25, True, f16, f8, c, m, per_image=True, pixels=frames, refine_queues=q),
+                         f"fused launch, uint8 frames, refine_queues={q}")
+            else:
+                same(vq_forward_route(z, w, 0.25, True, e16, e8, c, m, per_image=False, pixels=xd), "VQ + router entry point")
+            unrefined += _unrefined_diff(e16, e8, r16, r8, ref, c, m, per_image)
+    assert unrefined[0] > 0, (name, unrefined)           # (the band decides: the default maps alone flip elements)
+
+
+def test_lane_stream_with_refinement_queues_equals_the_oracle_from_pixels(orc, golden):
+    """The configuration bench.py times -- LaneStream(refine_queues="auto"), four lanes, ring graphs replayed -- on tie-heavy 8-bit
+    content (three smooth slots, which make "auto" pick the fused launch's queue variant, and one of flat regions with edges),
+    pixels to bytes against the CPU oracle alone: masks == oracle entropy_ref -> router, indices == oracle VQ, every image's
+    decoded indices == the merge of the oracle's masks and indices, and on a sample the .bin bytes == oracle compress_image and the
+    oracle's decoder gives back the GPU's rows (bench.py --full: parity.timed_batch_from_pixels, as a test)."""
+    import control_gic_amd.pipeline as pl
+    from oracle.content_families import families
+    gc = golden("coders")
+    rng = np.random.default_rng(404)
+    cbk = rng.standard_normal((1024, 4)).astype(np.float32)
+    vq = _make_vq(cbk)
+    htab = orc.HuffmanTable(gc["zipf_freq"])
+    B, H, W = 64, 256, 256
+    h, w = H // 4, W // 4
+    xs = [families(n=B, seed=101)["smooth8"], families(n=B, seed=102)["smooth8"], families(n=B, seed=103)["flat_edges"],
+          families(n=B, seed=104)["smooth8"]]
+    zs = [rng.standard_normal((B, 4, h, w), dtype=np.float32) for _ in xs]
+    slots = [(_t(x), _t(z)) for x, z in zip(xs, zs)]
+    ls = pl.LaneStream(vq, 0.1, 0.8, slots, lanes=4, graph=True, ring=True, refine_queues="auto",
+                       frequency=_freq_mapping(gc["zipf_freq"], gc["zipf_order"]))
+    ls.capture()
+    assert ls.pipe._queues is True, getattr(ls.pipe, "_decide_stats", None)
+    for n in (3, 4, 1, 8, 2):           # partial and whole rotations
+        ls.submit(n)
+    ls.join()
+    torch.cuda.synchronize()
+    for k, (x, z) in enumerate(zip(xs, zs)):
+        s = ls.slots[k]
+        owant, omode, _ = _oracle_route(x, 0.1, 0.8, per_image=True)
+        assert s.enc["mode"] == omode and _diff(s.enc["mask"], owant) == [0, 0, 0], (k, _diff(s.enc["mask"], owant))
+        _, _, oidx = orc.vq(z, cbk)
+        ind = s.enc["ind"].cpu().numpy().reshape(B, h, w)
+        assert np.array_equal(ind.reshape(-1), oidx), k
+        oind = oidx.reshape(B, h, w)
+        omc, omm, omf = (mk[:, 0] for mk in owant)
+        exp = np.where(omf == 1, oind, 0)
+        exp = exp + np.repeat(np.repeat(np.where(omm == 1, oind[:, ::2, ::2], 0), 2, 1), 2, 2)
+        exp = exp + np.repeat(np.repeat(np.where(omc == 1, oind[:, ::4, ::4], 0), 4, 1), 4, 2)
+        dind, dmask, dq, status = s.dec
+        assert int(status.abs().max()) == 0
+        assert np.array_equal(dind.cpu().numpy(), exp), k
+        assert _diff(dmask, owant) == [0, 0, 0], (k, "decoded masks")
+        host = s.enc["comp"].to_host()
+        for b in (0, B // 2, B - 1):
+            ref = orc.compress_image(oind[b], omc[b], omm[b], omf[b], omode, htab)
+            assert host[b] == ref, (k, b, "bitstream differs from the oracle")
+            rind, rmc, rmm, rmf = orc.decompress_image(ref, omode, h, w, htab)
+            assert np.array_equal(rind, exp[b]) and np.array_equal(dind[b].cpu().numpy(), rind), (k, b)
+            assert np.array_equal(rmc, omc[b]) and np.array_equal(rmm, omm[b]) and np.array_equal(rmf, omf[b]), (k, b)
+            assert np.array_equal(dq[b].cpu().numpy(), orc.gather(rind, cbk)[0]), (k, b)
 
 
 def test_router_constant_map_selects_nothing():

@@ -223,3 +223,24 @@ def test_fast_division_by_sigma_is_the_ieee_quotient(orc):
     x = np.concatenate([np.float32(2.0) ** -np.arange(101, 150, dtype=np.float32), [np.float32(0.0)]]).astype(np.float32)
     q = (x * np.float32(100.0)).astype(np.float32)
     assert np.all((q * q).astype(np.float32) == 0) and np.all(((x / np.float32(0.01)) ** 2).astype(np.float32) == 0)
+
+
+@pytest.mark.parametrize("name", ["flat_edges", "blocky8"])
+def test_reference_batch_masks_beyond_one_workgroups_lds_follow_from_the_port(orc, golden, name):
+    """tests/golden/ties_batch.npz: 16 images of 256x256 per tie-heavy family (one flattened segment beyond a router workgroup's
+    LDS), masks of the REAL router on the REAL Entropy maps over the flattened batch and per image, at two ratios: the correctly
+    rounded restatement -> oracle router gives exactly these masks (what test_gpu_parity.py then demands of router_big)"""
+    g = golden("ties_batch")
+    x = g[name + "_u8"].astype(np.float32) / 255.0
+    B = x.shape[0]
+    assert B == 16 and x.shape[2:] == (256, 256)
+    a8, a16 = orc.entropy_ref(x, 8), orc.entropy_ref(x, 16)
+    for ri, (c, m) in enumerate(g["ratios"]):
+        batch = orc.router(a16, a8, float(c), float(m))
+        per = orc.router(a16, a8, float(c), float(m), per_image=True)
+        assert batch[4] == per[4] == int(g[f"{name}_r{ri}_mode"])
+        for how, o in (("batch", batch), ("per", per)):
+            for k, mk in enumerate("cmf"):
+                assert np.array_equal(o[k], unpack_mask(g[f"{name}_r{ri}_{how}_m{mk}"], o[k].shape)), (name, ri, how, mk)
+        # the two semantics really differ on this content (the fixture pins the flattened batch, not per-image routing twice)
+        assert any(not np.array_equal(batch[k], per[k]) for k in range(3)), (name, ri)
