@@ -16,7 +16,10 @@ from .codec import GrainCodec, CompressedBatch, mode_streams, STREAM_NAMES, deco
 from . import pipeline, highres, container, model, ops, experimental
 from .pipeline import HotPathPipeline, LaneStream, GraphLanes, capture_graph
 from .model import install, compress_batch, grain_merge, avg_pool, decoder_blend_medium, decoder_blend_fine
+from . import rate
+from .rate import RateTable, rate_table, grain_indices, gather_grain_indices, choose, default_candidates, compress_to_bpp
 
 __all__ = ["VectorQuantize2", "VectorQuantizer", "TripleGrainFixedEntropyRouter", "Entropy", "entropy_maps", "entropy_maps_u8", "entropy_maps_tiles",
            "HuffmanCoding", "BinaryCoding", "GrainCodec", "CompressedBatch", "mode_streams", "STREAM_NAMES",
-           "HotPathPipeline", "LaneStream", "GraphLanes", "capture_graph", "decoder_mode", "install", "compress_batch", "grain_merge", "avg_pool", "decoder_blend_medium", "decoder_blend_fine", "highres", "container", "CgicError", "LIB_PATH"]
+           "HotPathPipeline", "LaneStream", "GraphLanes", "capture_graph", "decoder_mode", "install", "compress_batch", "grain_merge", "avg_pool", "decoder_blend_medium", "decoder_blend_fine", "rate", "RateTable", "rate_table", "grain_indices", "gather_grain_indices", "choose",
+           "default_candidates", "compress_to_bpp", "highres", "container", "CgicError", "LIB_PATH"]

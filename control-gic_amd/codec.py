@@ -177,6 +177,11 @@ class GrainCodec:
                       _lib.ptr(ws), _lib.current_stream(dev))
         return CompressedBatch(data, nbytes, mode, h, w)
 
+    def rate_table(self, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, pixels=None):
+        """control_gic_amd.rate.rate_table with this codec's code table: exact stream sizes per candidate ratio -> RateTable"""
+        from .rate import rate_table
+        return rate_table(self, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=per_image, pixels=pixels)
+
     def post_conv_table(self, post_quant_conv, bias_first=False):
         """post_quant_conv applied to the codebook rows (model.py:52,115): gathering from it == convolving the gathered latent"""
         cbk = self.codebook.detach().contiguous()

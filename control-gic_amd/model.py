@@ -11,6 +11,7 @@ import types
 import torch
 
 from . import _lib
+from . import rate as _rate
 from .codec import GrainCodec
 from .entropy import Entropy
 from .indices_coding import HuffmanCoding
@@ -116,20 +117,22 @@ def compress_batch(model, input, h_indices=None, decode=True):
                 params["per_image"] = saved
     comp = codec.compress(ind, grain_mask, mode)
     bpp = comp.bpp(input.shape[2] * input.shape[3])                      # model.py:223,233
-    dec = None
-    if decode:
-        pqc = getattr(model, "post_quant_conv", None)
-        fuse = (getattr(model, "_cgic_fuse_post_quant_conv", False) and isinstance(pqc, torch.nn.Conv2d)
-                and tuple(pqc.weight.shape) == (4, 4, 1, 1) and hasattr(model, "decoder"))
-        ind_d, mask_d, quant_d, status = codec.decompress(comp, post_quant_conv=pqc if fuse else None)
-        if int(status.abs().max()) != 0:
-            raise RuntimeError("decoded symbol count does not match its mask")   # shape mismatch in the reference
-        if fuse:
-            quant, quant2 = quant_d                                      # post_quant_conv came out of the gather
-            dec = model.decoder(quant2, quant, mask_d)                   # model.py:115-116
-        else:
-            dec = model.decode(quant_d, mask_d)                          # model.py:399
+    dec = _decode(model, codec, comp) if decode else None
     return dec, bpp, comp
+
+
+def _decode(model, codec, comp):
+    """the decode half of compress (model.py:269-401): streams -> indices, masks, quant -> the model's decoder"""
+    pqc = getattr(model, "post_quant_conv", None)
+    fuse = (getattr(model, "_cgic_fuse_post_quant_conv", False) and isinstance(pqc, torch.nn.Conv2d)
+            and tuple(pqc.weight.shape) == (4, 4, 1, 1) and hasattr(model, "decoder"))
+    ind_d, mask_d, quant_d, status = codec.decompress(comp, post_quant_conv=pqc if fuse else None)
+    if int(status.abs().max()) != 0:
+        raise RuntimeError("decoded symbol count does not match its mask")   # shape mismatch in the reference
+    if fuse:
+        quant, quant2 = quant_d                                          # post_quant_conv came out of the gather
+        return model.decoder(quant2, quant, mask_d)                      # model.py:115-116
+    return model.decode(quant_d, mask_d)                                 # model.py:399
 
 
 def compress(self, input, path, h_indices=None, h_mask=None, save_img=False):
@@ -197,6 +200,7 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
                 setattr(dec, name, AvgPool(k))
     model.compress = types.MethodType(compress, model)
     model.compress_batch = types.MethodType(compress_batch, model)
+    model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)
     model._cgic_codec = None
     model._cgic_codec_key = None
     return model

@@ -8,12 +8,14 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     data, nbytes   = torch.ops.cgic.compress_streams(idx, mc, mm, mf, mode, table, None)          # table = HuffmanCoding(...).table.handle.value
     ind, dc, dm, df, z_q, status = torch.ops.cgic.decompress_streams(data, nbytes, h, w, mode, table, codebook, "auto")
     h = torch.ops.cgic.grain_merge(h_c, h_m, h_f, mc, mm, mf)                                     # differentiable (vqvae_blocks.py:361-366)
+    nbytes = torch.ops.cgic.rate_table(ind_c, ind_m, ind_f, e16, e8, [0.1, 0.2], [0.8, 0.5], True, table)   # [C,B,5] bytes per ratio
+    ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).
 """
 import ctypes
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -147,6 +149,20 @@ def _(z, codebook, beta, legacy, e16, e8, coarse_ratio, medium_ratio, per_image,
     return z.new_empty(z.shape), z.new_empty(()), z.new_empty((B * h * w,), dtype=torch.int64), mk(1), mk(2), mk(4)
 
 
+@torch.library.custom_op("cgic::gather_grain_indices", mutates_args=(), device_types=_DEV)
+def gather_grain_indices(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor,
+                         mask_f: torch.Tensor) -> torch.Tensor:
+    """the merged latent's VQ indices from the per-head ones (include/cgic_hip.h section I): int64 [B,h,w] =
+    mask_f ? ind_f : up2(mask_m) ? up2(ind_m) : up4(ind_c)"""
+    from .rate import gather_grain_indices as _gather
+    return _gather(ind_c, ind_m, ind_f, (mask_c, mask_m, mask_f))
+
+
+@gather_grain_indices.register_fake
+def _(ind_c, ind_m, ind_f, mask_c, mask_m, mask_f):
+    return ind_f.new_empty((mask_f.shape[0], mask_f.shape[-2], mask_f.shape[-1]), dtype=torch.int64)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the codec (CGIC.compress, model.py:217-260 / :269-397) and the single-stream coders (indices_coding.py, mask_coding.py)
 def _table(handle: int):
@@ -194,6 +210,27 @@ def _(ind, mask_c, mask_m, mask_f, mode, table, hist):
 
 
 _DECODERS = {"auto": 0, "latency": 1, "throughput": 2}
+
+
+@torch.library.custom_op("cgic::rate_table", mutates_args=(), device_types=_DEV)
+def rate_table(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e16: torch.Tensor, e8: torch.Tensor, coarse: List[float],
+               medium: List[float], per_image: bool, table: int, pixels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """exact .bin sizes per candidate ratio (coarse[c], medium[c]) without writing a stream (cgic_rate_table): int32 [C,B,5],
+    0 = stream not written in that mode; pixels: see router"""
+    if len(coarse) != len(medium):
+        raise ValueError("rate_table: one medium ratio per coarse ratio")
+    from .rate import rate_table as _rate_table
+
+    class _Codec:            # the op carries the table as its handle
+        class huffman:
+            class table:
+                handle = _table(table)
+    return _rate_table(_Codec, ind_c, ind_m, ind_f, e16, e8, list(zip(coarse, medium)), per_image=per_image, pixels=pixels).nbytes
+
+
+@rate_table.register_fake
+def _(ind_c, ind_m, ind_f, e16, e8, coarse, medium, per_image, table, pixels=None):
+    return e16.new_empty((len(coarse), e16.shape[0], _lib.NUM_STREAMS), dtype=torch.int32)
 
 
 @torch.library.custom_op("cgic::decompress_streams", mutates_args=(), device_types=_DEV)

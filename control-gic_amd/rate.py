@@ -1,0 +1,230 @@
+"""Rate control: exact per-ratio rate tables and compress-to-target-bpp.
+
+The bitrate of Control-GIC is set through the granularity ratio (coarse, medium) of the router; which ratio gives which bpp
+depends on the image.  `rate_table` answers that for C candidate ratios at once, exactly (the bytes CGIC.compress would write,
+model.py:217-262) and without writing a stream: the VQ of each encoder head at its own resolution gives the indices of every
+ratio (grain_indices), and a stream's size depends on the masks only through the summed code lengths of the symbols they
+select (include/cgic_hip.h, section I).  `compress_to_bpp` then compresses the ratio `choose` picks.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .quantize import FusedQuantConv, _vq_forward
+from .router import TripleGrainFixedEntropyRouter, _flat_of
+
+#: the most candidates one rate_table call takes (cgic_rate_table)
+MAX_CANDIDATES = 64
+
+
+def _head_indices(quantizer, h, quant_conv):
+    conv, bias_first = None, False
+    fused = isinstance(quant_conv, torch.nn.Conv2d) and tuple(quant_conv.weight.shape) == (4, 4, 1, 1) \
+        and quantizer.n_e % 64 == 0 and quantizer.n_e <= 1024
+    if quant_conv is not None and not fused:
+        h = quant_conv(h)
+        if hasattr(h, "materialize"):
+            h = h.materialize()
+    elif fused:
+        conv, bias_first = quant_conv, getattr(quant_conv, "bias_first", FusedQuantConv.bias_first)
+    h = h.detach().contiguous().float()
+    B, _, hh, ww = h.shape
+    idx = _vq_forward(h, quantizer.embedding.weight, quantizer.beta, quantizer.legacy, None, want_zq=False, want_loss=False,
+                      quant_conv=conv, conv_bias_first=bias_first, prepared=quantizer._prepared_image())[2]
+    return idx.view(B, hh, ww)
+
+
+def grain_indices(quantizer, h_c, h_m, h_f, quant_conv=None):
+    """VQ indices of the three encoder heads (conv_out_coarse / conv_out / conv_out_fine outputs, [B,4,h/4,w/4], [B,4,h/2,w/2],
+    [B,4,h,w]) at their own resolutions -> (ind_c, ind_m, ind_f) int64 [B,h/4,w/4], [B,h/2,w/2], [B,h,w].  quant_conv: the model's
+    quant_conv (fused into the VQ kernel as install() does), or None.  With finite latents these are the indices the VQ of the
+    merged latent gives at the positions each grain owns, for every ratio.  The usage counter / histogram are not touched."""
+    if quantizer.training:
+        raise RuntimeError("grain_indices: the quantiser is in training mode (its forward would count usage); call .eval() first")
+    with torch.no_grad():
+        return tuple(_head_indices(quantizer, h, quant_conv) for h in (h_c, h_m, h_f))
+
+
+def _check_candidates(candidates):
+    cand = [(float(c), float(m)) for c, m in candidates]
+    if not 1 <= len(cand) <= MAX_CANDIDATES:
+        raise ValueError(f"rate_table: {len(cand)} candidates; 1..{MAX_CANDIDATES} are supported")
+    return cand
+
+
+def default_candidates(coarse_ratio, n=16):
+    """n candidates with `coarse_ratio` fixed and the medium ratio spread evenly over [0, 1 - coarse], both ends included
+    (with coarse > 0: mode 2 at medium = 0, mode 0 inside, mode 3 at the top; coarse = 0 spans modes 6, 1, 5; coarse = 1: mode 4)"""
+    n = int(n)
+    if not 2 <= n <= MAX_CANDIDATES:
+        raise ValueError(f"default_candidates: n={n}; 2..{MAX_CANDIDATES}")
+    c = float(coarse_ratio)
+    if not 0.0 <= c <= 1.0:
+        raise ValueError(f"default_candidates: coarse ratio {c} outside [0, 1]")
+    top = 1.0 - c
+    return [(c, top * i / (n - 1) if i < n - 1 else top) for i in range(n)]
+
+
+class RateTable:
+    """rate_table's result: per candidate and image the sizes of the five .bin streams.
+    nbytes int32 [C,B,5] (0 = not written), bytes int64 [C,B], bpp float64 [C,B] (bytes * 8 / pixels, model.py:233),
+    batch_bpp float64 [C] (all bits of the batch over all its pixels); candidates: the (coarse, medium) list, modes: their modes"""
+
+    def __init__(self, nbytes, candidates, num_pixels):
+        self.nbytes = nbytes
+        self.candidates = list(candidates)
+        self.num_pixels = int(num_pixels)
+        self.modes = [int(_lib.lib().cgic_router_mode(c, m)) for c, m in self.candidates]
+        nb = nbytes.detach().cpu()
+        if int(nb.min()) < 0:
+            raise KeyError("rate_table: an index is not in the code table")
+        self.bytes = nb.to(torch.int64).sum(dim=2)
+        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
+        B = self.bytes.shape[1]
+        self.batch_bpp = self.bytes.sum(dim=1).to(torch.float64) * 8 / (self.num_pixels * B)
+
+
+def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, pixels=None, flat8=None):
+    """exact sizes of the streams GrainCodec.compress would write after routing at each candidate (coarse, medium) ratio
+    (cgic_rate_table).  ind_*: grain_indices(...); e16 / e8: the entropy maps; pixels: the image batch behind them (fp32
+    [B,3,H,W] or uint8 [B,H,W,3]) for the router's threshold-band refinement -- taken from the maps' tags when they come from
+    control_gic_amd.Entropy / entropy_maps, like the router does.  per_image as the router's.  -> RateTable"""
+    cand = _check_candidates(candidates)
+    _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
+    explicit = pixels is not None
+    if pixels is None:
+        p16, p8 = getattr(e16, "_cgic_pixels", None), getattr(e8, "_cgic_pixels", None)
+        pixels = p16 if (p16 is not None and p16 is p8) else None
+    if flat8 is None and pixels is not None:
+        flat8 = _flat_of(pixels, e8, e16)
+    e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
+    B, h16, w16 = e16c.shape
+    if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
+        raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
+    want = ((B, h16, w16), (B, 2 * h16, 2 * w16), (B, 4 * h16, 4 * w16))
+    inds = []
+    for t, shp in zip((ind_c, ind_m, ind_f), want):
+        if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
+            raise ValueError(f"grain indices must be int64 with shapes {want}")
+        inds.append(t.contiguous())
+    dev = e16c.device
+    C = len(cand)
+    cr = (ctypes.c_double * C)(*[c for c, _ in cand])
+    mr = (ctypes.c_double * C)(*[m for _, m in cand])
+    pi = int(bool(per_image))
+    px, keep = _lib.pixels_arg(pixels, B, h16, w16, pi, flat8=flat8, queues=False, explicit=explicit)
+    nbytes = torch.empty((C, B, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(_lib.lib().cgic_rate_table_workspace_bytes(B, h16, w16, C, pi)), 1), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("cgic_rate_table", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+                  _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, C, cr, mr, pi, px, _lib.ptr(nbytes), _lib.ptr(ws),
+                  _lib.current_stream(dev))
+    del keep
+    return RateTable(nbytes, cand, 256 * h16 * w16)
+
+
+def gather_grain_indices(ind_c, ind_m, ind_f, masks):
+    """ind [B,h,w] int64 = mask_f ? ind_f : up2(mask_m) ? up2(ind_m) : up4(ind_c) (cgic_gather_grain_indices): the indices of
+    the merged latent for these (router) masks"""
+    _lib.require_device(ind_c, ind_m, ind_f, *masks)
+    mc, mm, mf = (m.contiguous() for m in masks)
+    B, h, w = mf.shape[0], mf.shape[-2], mf.shape[-1]
+    for m in (mc, mm, mf):
+        if m.dtype != torch.int32:
+            raise TypeError("masks must be int32 like the router's")
+    if mc.numel() != B * (h // 4) * (w // 4) or mm.numel() != B * (h // 2) * (w // 2):
+        raise ValueError("masks at 1/4, 1/2, 1/1 of the fine grid expected")
+    ic, im, if_ = (t.contiguous() for t in (ind_c, ind_m, ind_f))
+    if any(t.dtype != torch.int64 for t in (ic, im, if_)) or ic.numel() != mc.numel() or im.numel() != mm.numel() \
+            or if_.numel() != mf.numel():
+        raise ValueError("grain indices: int64 on the grids of the three masks")
+    out = torch.empty((B, h, w), dtype=torch.int64, device=mf.device)
+    with _lib.on_device(mf.device):
+        _lib.call("cgic_gather_grain_indices", _lib.ptr(ic), _lib.ptr(im), _lib.ptr(if_), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf),
+                  B, h, w, _lib.ptr(out), _lib.current_stream(mf.device))
+    return out
+
+
+def _pick(bpp, candidates, target):
+    """index of the largest bpp <= target (ties: smaller coarse, then smaller medium); none fits: the smallest bpp"""
+    idx = list(range(len(candidates)))
+    fit = [i for i in idx if bpp[i] <= target]
+    if fit:
+        return min(fit, key=lambda i: (-bpp[i], candidates[i][0], candidates[i][1])), True
+    return min(idx, key=lambda i: (bpp[i], candidates[i][0], candidates[i][1])), False
+
+
+def choose(table, target_bpp, per="batch"):
+    """the candidate with the largest bpp that is <= target_bpp (ties: the smaller coarse ratio, then the smaller medium ratio);
+    if none fits, the smallest-bpp candidate with fits=False.  per="batch": on batch_bpp -> (c, fits); per="image": on each
+    image's bpp -> (c [B] int64, fits [B] bool) numpy-free lists as tensors, for callers that compress image by image"""
+    target = float(target_bpp)
+    if per == "batch":
+        return _pick(table.batch_bpp.tolist(), table.candidates, target)
+    if per == "image":
+        cs, fs = [], []
+        for b in range(table.bpp.shape[1]):
+            c, f = _pick(table.bpp[:, b].tolist(), table.candidates, target)
+            cs.append(c)
+            fs.append(f)
+        return torch.tensor(cs, dtype=torch.int64), torch.tensor(fs, dtype=torch.bool)
+    raise ValueError(f"choose: per={per!r}; 'batch' or 'image'")
+
+
+def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True):
+    """compress a batch at the granularity ratio whose exact bpp over the batch is the largest one <= target_bpp.
+    -> (dec [B,3,H,W] or None, bpp list[B], CompressedBatch, (coarse, medium), RateTable).
+    One model.encode (the three encoder heads and the entropy maps are taken from it by forward hooks), one rate table over the
+    candidates (default: default_candidates(the router config's coarse ratio)), then the chosen ratio is routed, gathered,
+    compressed and decoded exactly as compress_batch does (per-image routing): bit-identical to compress_batch with the router
+    config set to that ratio.  Does not touch the usage counter."""
+    from .model import _codec_for, _decode
+    assert len(input.shape) == 4
+    q = model.quantize
+    if q.training:
+        raise RuntimeError("compress_to_bpp: the quantiser is in training mode; call model.eval() first")
+    enc = model.encoder
+    rc = enc.router_config
+    params = rc["params"]
+    if candidates is None:
+        candidates = default_candidates(params["coarse_grain_ratio"])
+    cand = _check_candidates(candidates)
+    codec = _codec_for(model)
+    got = {}
+    hooks = []
+
+    def grab(name):
+        def hook(mod, args, out):
+            got[name] = out
+        return hook
+
+    for name, mod in (("c", enc.conv_out_coarse), ("m", enc.conv_out), ("f", enc.conv_out_fine),
+                      ("e8", model.entropy_calculation_p8), ("e16", model.entropy_calculation_p16)):
+        hooks.append(mod.register_forward_hook(grab(name)))
+    saved = params.get("per_image", None)
+    params["per_image"] = True
+    try:
+        with torch.no_grad():
+            model.encode(input)
+    finally:
+        for hk in hooks:
+            hk.remove()
+        if saved is None:
+            params.pop("per_image", None)
+        else:
+            params["per_image"] = saved
+    with torch.no_grad():
+        ind_c, ind_m, ind_f = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
+        e16, e8 = got["e16"], got["e8"]
+        table = rate_table(codec, ind_c, ind_m, ind_f, e16, e8, cand, per_image=True)
+        c, fits = choose(table, target_bpp)
+        cr, mr = cand[c]
+        router = TripleGrainFixedEntropyRouter(cr, mr, per_image=True)
+        masks, _, _, mode = router(e16, e8, want_gate=False)
+        ind = gather_grain_indices(ind_c, ind_m, ind_f, masks)
+        comp = codec.compress(ind, masks, mode)
+        bpp = comp.bpp(input.shape[2] * input.shape[3])
+        dec = _decode(model, codec, comp) if decode else None
+    table.fits = fits
+    return dec, bpp, comp, (cr, mr), table

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 8
+#define CGIC_ABI_VERSION 9
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -566,6 +566,51 @@ int cgic_compress_tiled(const cgic_table *t, const float *codebook, int K, int e
                         int src_is_u8, int64_t N, int64_t H, int64_t W, int ngroups, const cgic_tile_group *groups,
                         double coarse_ratio, double medium_ratio, float beta, int legacy, const float *bins, int nbins, float sigma,
                         int decoder, int *mode_out, cgic_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * I. Rate tables (ABI 9): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
+ * ratios, without writing a stream -- the "which ratio gives which bpp on THIS image" question of a controllable codec.
+ *
+ * Exactness.  In the encoder's merge h = up4(h_c)*up4(m_c) + up2(h_m)*up2(m_m) + h_f*m_f (vqvae_blocks.py:361-366) every
+ * position takes exactly one head's vector (for finite x: x*1 + y*0 + z*0 == x bit for bit); quant_conv is a 1x1 convolution
+ * (per position) and the VQ works on one vector at a time.  So ind[:, ::4, ::4] at a coarse position is VQ(quant_conv(h_c))
+ * there, likewise ind[:, ::2, ::2] on the medium grid and ind on the fine grid: the VQ of each head at its own resolution
+ * (n + n/4 + n/16 vectors) gives the indices of EVERY ratio.  And HuffmanCoding.compress (indices_coding.py:113-124) writes an
+ * empty file for an empty list, else nbits // 8 + 2 bytes (one header byte, 1..8 pad bits -- also when nbits % 8 == 0); a mask
+ * stream is n // 8 + 2 bytes for its fixed n (mask_coding.py): a stream's size depends on the masks only through the number
+ * and the summed code lengths of the symbols they select.  LIMIT: the argument needs finite latents -- inf * 0 is NaN in the
+ * reference's merge, so a head holding +-inf or NaN poisons the merged vector at positions that take ANOTHER head.
+ *
+ * cgic_rate_table:
+ *   ind_c / ind_m / ind_f  device int64 [B,h16,w16] / [B,2h16,2w16] / [B,4h16,4w16]: the per-head VQ indices (latent grids
+ *            h/4, h/2, h of the [B,4,h,w] latent, h = 4 h16)
+ *   e16, e8, B, h16, w16, per_image, refine   exactly what cgic_router_f32 takes (refine->scratch: required when
+ *            cgic_router_refine_in_lds(...) == 0, as there)
+ *   C, coarse, medium   host [C] candidate ratios, 1 <= C <= 64
+ *   nbytes   device int32 [C, B, 5]: nbytes[c, b, s] == nbytes[b, s] of cgic_compress_streams called after cgic_router_f32 at
+ *            (coarse[c], medium[c]) with the same per_image / refine, on ind = cgic_gather_grain_indices(.., those masks) --
+ *            except that a stream the mode does not write is 0 here (-1 there).  Bytes are per image also when per_image = 0
+ *            routes the flattened batch as one segment.  <= -10: a selected symbol outside the table (as cgic_compress_streams).
+ *   workspace device, cgic_rate_table_workspace_bytes(...) bytes, 16-byte aligned: the [C, ...] stack of the masks
+ * Every candidate is checked (mode, k <= n, the refinement's requirements -- for segments beyond the LDS also the scratch)
+ * before anything is enqueued: a bad candidate returns CGIC_ERR_INVALID / _UNSUPPORTED with nothing written.
+ * Launches: one router launch for all candidates (grid: the router's workgroups x C) into the mask stack + one reduction (B x C
+ * workgroups: code lengths in LDS, DPP wave sums).  Segments whose refinement is the launch chain of cgic_router_f32
+ * (cgic_router_refine_in_lds == 0) are routed candidate by candidate through cgic_router_f32, sequentially on `stream`: one
+ * scratch-carrying launch in flight at a time.  Not inside a launch group.
+ *
+ * cgic_gather_grain_indices: ind_out[b,y,x] = mask_f ? ind_f : up2(mask_m) ? up2(ind_m) : up4(ind_c) -- int64 [B,h,w] in one pass;
+ *   masks int32 as cgic_router_f32 writes them (a partition of the grid), h % 4 == w % 4 == 0.  Equal to the VQ indices of the
+ *   merged latent (finite latents, see above): what cgic_compress_streams takes for the chosen ratio.
+ * ------------------------------------------------------------------------- */
+size_t cgic_rate_table_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int C, int per_image);
+int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
+                    const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, int C, const double *coarse,
+                    const double *medium, int per_image, const cgic_pixels *refine, int32_t *nbytes, void *workspace,
+                    cgic_stream_t stream);
+int cgic_gather_grain_indices(const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f, const int32_t *mask_c,
+                              const int32_t *mask_m, const int32_t *mask_f, int64_t B, int64_t h, int64_t w, int64_t *ind_out,
+                              cgic_stream_t stream);
 
 #ifdef __cplusplus
 }
