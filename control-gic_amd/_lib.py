@@ -137,6 +137,9 @@ PROTOTYPES = {
     "cgic_rate_table": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, C.POINTER(_f64), C.POINTER(_f64), _int, _px, _vp, _vp,
                                _vp]),
     "cgic_gather_grain_indices": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "cgic_rate_curve_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "cgic_rate_curve": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp, _vp]),
+    "cgic_router_ranks": (_int, [_f64, _f64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     ind, dc, dm, df, z_q, status = torch.ops.cgic.decompress_streams(data, nbytes, h, w, mode, table, codebook, "auto")
     h = torch.ops.cgic.grain_merge(h_c, h_m, h_f, mc, mm, mf)                                     # differentiable (vqvae_blocks.py:361-366)
     nbytes = torch.ops.cgic.rate_table(ind_c, ind_m, ind_f, e16, e8, [0.1, 0.2], [0.8, 0.5], True, table)   # [C,B,5] bytes per ratio
+    nbytes = torch.ops.cgic.rate_curve(ind_c, ind_m, ind_f, e16, e8, 0.1, table)                          # [B,n8+1,5] bytes per medium rank
     ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
@@ -207,6 +208,26 @@ def _(ind, mask_c, mask_m, mask_f, mode, table, hist):
     B, h, w = mask_f.shape[0], mask_f.shape[-2], mask_f.shape[-1]
     return (ind.new_empty((B, _lib.NUM_STREAMS, _slot_bytes(table, h, w)), dtype=torch.uint8),
             ind.new_empty((B, _lib.NUM_STREAMS), dtype=torch.int32))
+
+
+@torch.library.custom_op("cgic::rate_curve", mutates_args=(), device_types=_DEV)
+def rate_curve(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e16: torch.Tensor, e8: torch.Tensor, coarse: float,
+               table: int) -> torch.Tensor:
+    """exact .bin sizes of EVERY medium rank K = 0 .. n8 at the coarse ratio `coarse`, per-image routing on the maps as given
+    (cgic_rate_curve): int32 [B,n8+1,5], 0 = stream not written in the curve's mode"""
+    from .rate import rate_curve as _rate_curve
+
+    class _Codec:            # the op carries the table as its handle
+        class huffman:
+            class table:
+                handle = _table(table)
+    # (ranks=(): the op returns the sizes only; which ranks a ratio reaches is host arithmetic the caller may not want)
+    return _rate_curve(_Codec, ind_c, ind_m, ind_f, e16, e8, coarse, ranks=()).nbytes
+
+
+@rate_curve.register_fake
+def _(ind_c, ind_m, ind_f, e16, e8, coarse, table):
+    return e16.new_empty((e16.shape[0], 4 * e16.shape[1] * e16.shape[2] + 1, _lib.NUM_STREAMS), dtype=torch.int32)
 
 
 _DECODERS = {"auto": 0, "latency": 1, "throughput": 2}

@@ -5,8 +5,14 @@ depends on the image.  `rate_table` answers that for C candidate ratios at once,
 model.py:217-262) and without writing a stream: the VQ of each encoder head at its own resolution gives the indices of every
 ratio (grain_indices), and a stream's size depends on the masks only through the summed code lengths of the symbols they
 select (include/cgic_hip.h, section I).  `compress_to_bpp` then compresses the ratio `choose` picks.
+
+`rate_curve` answers it for EVERY setting of the medium ratio at one coarse ratio: the medium decision of the router is one
+integer, the rank K of its threshold among the 8x8-patch entropies, and one sort of the image's patches gives the sizes of all
+n8 + 1 ranks (cgic_rate_curve).  `compress_to_bpp(..., search="curve")` picks among all of them.
 """
 import ctypes
+import functools
+import math
 
 import torch
 
@@ -124,6 +130,109 @@ def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, 
     return RateTable(nbytes, cand, 256 * h16 * w16)
 
 
+def router_ranks(coarse_ratio, medium_ratio, n16):
+    """(k_coarse, k_medium) the router derives from a ratio pair for a segment of n16 coarse patches (cgic_router_ranks: Python's
+    round on the float64 products; 0 where the mode uses none).  Raises CgicError if k > n, like the router."""
+    kc, km = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call("cgic_router_ranks", float(coarse_ratio), float(medium_ratio), int(n16), ctypes.byref(kc), ctypes.byref(km))
+    return kc.value, km.value
+
+
+def ratio_for_rank(K, n16, coarse_ratio):
+    """a medium ratio in (0, 1] whose medium rank is K at this coarse ratio, in the curve's mode (0 with coarse > 0, else 1), or
+    None if no ratio reaches K there: starts at (K - 4 n16 c) / n8 and steps by one float64 at a time until cgic_router_ranks
+    returns K and cgic_router_mode the curve's mode"""
+    l = _lib.lib()
+    K, n16, c = int(K), int(n16), float(coarse_ratio)
+    n8 = 4 * n16
+    want = 0 if c > 0.0 else 1
+    tiny = math.nextafter(0.0, 1.0)
+    m = (K - 4 * n16 * c) / n8
+    if m <= 0.0:
+        m = tiny
+    kc, km = ctypes.c_int64(0), ctypes.c_int64(0)
+    for _ in range(64):
+        rc = l.cgic_router_ranks(c, m, n16, ctypes.byref(kc), ctypes.byref(km))
+        ok = rc == _lib.OK and l.cgic_router_mode(c, m) == want
+        if ok and km.value == K:
+            return m
+        # a rank below K: a larger ratio; above it, k > n, or the fine ratio has reached 0 (modes 3 / 5): a smaller one
+        m = math.nextafter(m, 2.0 if (ok and km.value < K) else 0.0)
+        if not tiny <= m <= 1.0:
+            return None
+    return None
+
+
+@functools.lru_cache(maxsize=64)
+def reachable_ranks(n16, coarse_ratio):
+    """((K, medium ratio), ...) for every medium rank K in 0 .. n8 a ratio reaches at this coarse ratio (ratio_for_rank)"""
+    out = []
+    for K in range(4 * int(n16) + 1):
+        m = ratio_for_rank(K, n16, coarse_ratio)
+        if m is not None:
+            out.append((K, m))
+    return tuple(out)
+
+
+class RateCurve:
+    """rate_curve's result: per image and medium rank K = 0 .. n8 the sizes of the five .bin streams at one coarse ratio.
+    nbytes int32 [B,n8+1,5] (0 = not written), bytes int64 [B,n8+1], bpp float64 [B,n8+1], batch_bpp float64 [n8+1];
+    ranks: the K a medium ratio reaches (ascending), candidates: the (coarse, medium) pair of each, rank by rank, modes: their
+    mode (0, or 1 at coarse ratio 0); n_coarse int64 [B]: coarse patches of each image (ranks up to 4 n_coarse select no medium
+    patch).  The curve is not monotone in K: tied patches move together, and a patch that turns medium trades four fine symbols
+    for one medium symbol of another length."""
+
+    def __init__(self, nbytes, coarse_ratio, num_pixels, ranks=None, n_coarse=None):
+        self.nbytes = nbytes
+        self.coarse_ratio = float(coarse_ratio)
+        self.num_pixels = int(num_pixels)
+        nb = nbytes.detach().cpu()
+        if int(nb.min()) < 0:
+            raise KeyError("rate_curve: an index is not in the code table")
+        self.bytes = nb.to(torch.int64).sum(dim=2)
+        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
+        B, nk = self.bytes.shape
+        self.batch_bpp = self.bytes.sum(dim=0).to(torch.float64) * 8 / (self.num_pixels * max(B, 1))
+        if ranks is None:
+            ranks = reachable_ranks((nk - 1) // 4, self.coarse_ratio)
+        self.ranks = [int(k) for k, _ in ranks]
+        self.candidates = [(self.coarse_ratio, float(m)) for _, m in ranks]
+        self.modes = [0 if self.coarse_ratio > 0.0 else 1] * len(self.ranks)
+        self.n_coarse = n_coarse
+
+    def ratio(self, K):
+        """the (coarse, medium) pair that reaches rank K"""
+        return self.candidates[self.ranks.index(int(K))]
+
+
+def rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, ranks=None):
+    """exact sizes of the streams GrainCodec.compress would write for EVERY medium rank at `coarse_ratio`, every image routed on
+    its own thresholds on the maps as given (cgic_rate_curve; no threshold-band refinement: maps of
+    entropy_maps(x, reference_order=True) make that the reference's routing from the pixels).  Arguments as rate_table's;
+    ranks: ((K, medium ratio), ...) to carry instead of reachable_ranks(n16, coarse_ratio).  -> RateCurve"""
+    _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
+    e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
+    B, h16, w16 = e16c.shape
+    if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
+        raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
+    want = ((B, h16, w16), (B, 2 * h16, 2 * w16), (B, 4 * h16, 4 * w16))
+    inds = []
+    for t, shp in zip((ind_c, ind_m, ind_f), want):
+        if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
+            raise ValueError(f"grain indices must be int64 with shapes {want}")
+        inds.append(t.contiguous())
+    dev = e16c.device
+    n8 = 4 * h16 * w16
+    nbytes = torch.empty((B, n8 + 1, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(_lib.lib().cgic_rate_curve_workspace_bytes(B, h16, w16)), 16), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("cgic_rate_curve", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+                  _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, float(coarse_ratio), _lib.ptr(nbytes), _lib.ptr(ws),
+                  _lib.current_stream(dev))
+    n_coarse = ws[:B * 16].view(torch.int32).view(B, 4)[:, 0].to(torch.int64).cpu()
+    return RateCurve(nbytes, coarse_ratio, 256 * h16 * w16, ranks=ranks, n_coarse=n_coarse)
+
+
 def gather_grain_indices(ind_c, ind_m, ind_f, masks):
     """ind [B,h,w] int64 = mask_f ? ind_f : up2(mask_m) ? up2(ind_m) : up4(ind_c) (cgic_gather_grain_indices): the indices of
     the merged latent for these (router) masks"""
@@ -158,38 +267,65 @@ def _pick(bpp, candidates, target):
 def choose(table, target_bpp, per="batch"):
     """the candidate with the largest bpp that is <= target_bpp (ties: the smaller coarse ratio, then the smaller medium ratio);
     if none fits, the smallest-bpp candidate with fits=False.  per="batch": on batch_bpp -> (c, fits); per="image": on each
-    image's bpp -> (c [B] int64, fits [B] bool) numpy-free lists as tensors, for callers that compress image by image"""
+    image's bpp -> (c [B] int64, fits [B] bool) numpy-free lists as tensors, for callers that compress image by image.
+    table: a RateTable (c = the candidate's index) or a RateCurve (c = the medium rank K, among the ranks a ratio reaches; the
+    curve is not monotone in K, so this is a search over all of them, not a bisection)"""
     target = float(target_bpp)
+    curve = isinstance(table, RateCurve)
+    if curve:
+        if not table.ranks:
+            raise ValueError(f"choose: no medium ratio reaches a rank at coarse ratio {table.coarse_ratio}")
+        sel = torch.tensor(table.ranks, dtype=torch.int64)
+        batch_bpp, bpp = table.batch_bpp[sel], table.bpp[:, sel].t()
+    else:
+        batch_bpp, bpp = table.batch_bpp, table.bpp
     if per == "batch":
-        return _pick(table.batch_bpp.tolist(), table.candidates, target)
+        c, f = _pick(batch_bpp.tolist(), table.candidates, target)
+        return (table.ranks[c] if curve else c), f
     if per == "image":
         cs, fs = [], []
-        for b in range(table.bpp.shape[1]):
-            c, f = _pick(table.bpp[:, b].tolist(), table.candidates, target)
-            cs.append(c)
+        for b in range(bpp.shape[1]):
+            c, f = _pick(bpp[:, b].tolist(), table.candidates, target)
+            cs.append(table.ranks[c] if curve else c)
             fs.append(f)
         return torch.tensor(cs, dtype=torch.int64), torch.tensor(fs, dtype=torch.bool)
     raise ValueError(f"choose: per={per!r}; 'batch' or 'image'")
 
 
-def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True):
+def _curve_ends(coarse_ratio):
+    """the two ends of the medium axis the curve's mode does not hold: medium 0 and fine 0 (modes 2 and 3; coarse 0: 6 and 5)"""
+    c = float(coarse_ratio)
+    return [(c, 0.0)] if c == 1.0 else [(c, 0.0), (c, 1.0 - c)]
+
+
+def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True, search="candidates"):
     """compress a batch at the granularity ratio whose exact bpp over the batch is the largest one <= target_bpp.
     -> (dec [B,3,H,W] or None, bpp list[B], CompressedBatch, (coarse, medium), RateTable).
     One model.encode (the three encoder heads and the entropy maps are taken from it by forward hooks), one rate table over the
     candidates (default: default_candidates(the router config's coarse ratio)), then the chosen ratio is routed, gathered,
     compressed and decoded exactly as compress_batch does (per-image routing): bit-identical to compress_batch with the router
-    config set to that ratio.  Does not touch the usage counter."""
+    config set to that ratio.  Does not touch the usage counter.
+    search="curve": instead of the candidates, EVERY medium ratio at the router config's coarse ratio -- one rate_curve over all
+    medium ranks plus the two ends of the axis (medium 0, fine 0) from a rate table, on the maps of
+    entropy_maps(input, reference_order=True), on which routing on the maps as given is the reference's routing from the pixels.
+    Returns a RateCurve in place of the table, with .fits, .chosen_rank (None: an end was chosen) and .ends (their RateTable);
+    the returned bpp is the curve's entry of the chosen rank."""
     from .model import _codec_for, _decode
     assert len(input.shape) == 4
+    if search not in ("candidates", "curve"):
+        raise ValueError(f"compress_to_bpp: search={search!r}; 'candidates' or 'curve'")
+    if search == "curve" and candidates is not None:
+        raise ValueError("compress_to_bpp: search='curve' takes no candidates (it covers every medium ratio of the router config's coarse ratio)")
     q = model.quantize
     if q.training:
         raise RuntimeError("compress_to_bpp: the quantiser is in training mode; call model.eval() first")
     enc = model.encoder
     rc = enc.router_config
     params = rc["params"]
-    if candidates is None:
-        candidates = default_candidates(params["coarse_grain_ratio"])
-    cand = _check_candidates(candidates)
+    if search == "candidates":
+        if candidates is None:
+            candidates = default_candidates(params["coarse_grain_ratio"])
+        cand = _check_candidates(candidates)
     codec = _codec_for(model)
     got = {}
     hooks = []
@@ -216,9 +352,20 @@ def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True):
             params["per_image"] = saved
     with torch.no_grad():
         ind_c, ind_m, ind_f = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
-        e16, e8 = got["e16"], got["e8"]
-        table = rate_table(codec, ind_c, ind_m, ind_f, e16, e8, cand, per_image=True)
-        c, fits = choose(table, target_bpp)
+        if search == "curve":
+            from .entropy import entropy_maps
+            coarse = float(params["coarse_grain_ratio"])
+            e8, e16 = entropy_maps(input, reference_order=True)
+            table = rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse)
+            table.ends = rate_table(codec, ind_c, ind_m, ind_f, e16, e8, _curve_ends(coarse), per_image=True)
+            cand = table.candidates + table.ends.candidates
+            bb = table.batch_bpp[torch.tensor(table.ranks, dtype=torch.int64)].tolist() + table.ends.batch_bpp.tolist()
+            c, fits = _pick(bb, cand, float(target_bpp))
+            table.chosen_rank = table.ranks[c] if c < len(table.ranks) else None
+        else:
+            e16, e8 = got["e16"], got["e8"]
+            table = rate_table(codec, ind_c, ind_m, ind_f, e16, e8, cand, per_image=True)
+            c, fits = choose(table, target_bpp)
         cr, mr = cand[c]
         router = TripleGrainFixedEntropyRouter(cr, mr, per_image=True)
         masks, _, _, mode = router(e16, e8, want_gate=False)

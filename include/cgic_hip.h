@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 9
+#define CGIC_ABI_VERSION 10
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -568,7 +568,7 @@ int cgic_compress_tiled(const cgic_table *t, const float *codebook, int K, int e
                         int decoder, int *mode_out, cgic_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * I. Rate tables (ABI 9): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
+ * I. Rate tables (ABI 9) and rate curves (ABI 10): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
  * ratios, without writing a stream -- the "which ratio gives which bpp on THIS image" question of a controllable codec.
  *
  * Exactness.  In the encoder's merge h = up4(h_c)*up4(m_c) + up2(h_m)*up2(m_m) + h_f*m_f (vqvae_blocks.py:361-366) every
@@ -611,6 +611,38 @@ int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const int64_t *in
 int cgic_gather_grain_indices(const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f, const int32_t *mask_c,
                               const int32_t *mask_m, const int32_t *mask_f, int64_t B, int64_t h, int64_t w, int64_t *ind_out,
                               cgic_stream_t stream);
+
+/* Rate curves (ABI 10): the sizes of EVERY medium rank of one coarse ratio.  With the coarse ratio fixed, the router's medium
+ * decision is one integer, the rank K of the medium threshold among the 8x8-patch entropies (RouterTriple.py:28-32): n8 + 1 =
+ * 4 h16 w16 + 1 settings per image, of which a rate table samples at most 64.
+ *
+ * cgic_rate_curve:
+ *   t, ind_c / ind_m / ind_f, e16, e8, B, h16, w16   as cgic_rate_table; finite, non-negative maps
+ *   coarse_ratio  in [0, 1].  > 0: the coarse rank k_c = round(n16 * coarse_ratio) and the stream set of mode 0; == 0: mode 1
+ *            (no coarse patch; K = round(n8 * medium))
+ *   nbytes   device int32 [B, n8 + 1, 5]: nbytes[b, K, :] == nbytes[c, b, :] of cgic_rate_table with per_image = 1 and
+ *            refine = NULL (every image routed on its own thresholds, on the maps AS GIVEN) for a candidate c whose ranks
+ *            (cgic_router_ranks) are (k_c, K): the coarse mask is e16 < s16[k_c - 1] (k_c == 0: index 0), the medium list
+ *            e8 * (1 - up2(gate_coarse)), its threshold t = sorted[K - 1] (K == 0: index 0), medium = e8 < t and not coarse
+ *            (strict: tied patches move together, so the curve has plateaus and is NOT monotone in K), fine = the rest.  All K
+ *            in 0 .. n8 are written; which of them a ratio reaches is host arithmetic (cgic_router_ranks).  <= -10: a selected
+ *            symbol outside the table, as cgic_rate_table.
+ *   workspace device, cgic_rate_curve_workspace_bytes(...) bytes, 16-byte aligned; on return int32 [B, 4] per image: the
+ *            number of coarse patches, the coarse threshold's bit pattern, the medium / fine code bits of all non-coarse patches
+ * One launch, one workgroup per image: the image's patches are sorted ONCE by entropy in LDS (64-bit words: the entropy's
+ * bit pattern above the code lengths of the patch's medium symbol and of its four fine symbols), both payloads are prefix-
+ * summed in that order, and every K is a binary search and two prefix reads.  LIMIT: 12 bytes of LDS per 8x8 patch, at most
+ * 12288 patches per image (n8 <= 12288: up to 768x1024 pixels; a 768x768 tile has 9216), codes of at most 4095 bits; beyond:
+ * CGIC_ERR_UNSUPPORTED.  Every argument is checked before anything is enqueued.  Not inside a launch group.
+ *
+ * cgic_router_ranks (host only): the ranks cgic_router_f32 derives from a ratio pair for a segment of n16 coarse patches --
+ * k_coarse = round(n16 c) in modes 0, 2, 3; k_medium = round(4 n16 c + n8 m) in mode 0, round(n8 m) in mode 1; 0 where the mode
+ * uses none -- with Python's round-half-even on the float64 product.  CGIC_ERR_INVALID if k > n, as the router. */
+size_t cgic_rate_curve_workspace_bytes(int64_t B, int64_t h16, int64_t w16);
+int cgic_rate_curve(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f, const float *e16,
+                    const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio, int32_t *nbytes, void *workspace,
+                    cgic_stream_t stream);
+int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64_t n16, int64_t *k_coarse, int64_t *k_medium);
 
 #ifdef __cplusplus
 }
