@@ -36,15 +36,10 @@ __device__ long long g_phase_clk[32];
 __device__ long long g_blk_t[2 * 4096];
 #endif
 
-#ifndef CGIC_ENC_THREADS
-#define CGIC_ENC_THREADS 512       // 1024 -> 512 in round 3: with four batches in flight 36.3 -> 35.5 us per step (smaller workgroups find a CU sooner); alone +0.5 us
-#endif
-constexpr int kEncThreads = CGIC_ENC_THREADS;         // x kEncItems = 4096 positions per scan round: one round per 256x256 stream
+// 1024 -> 512 in round 3: with four batches in flight 36.3 -> 35.5 us per step (smaller workgroups find a CU sooner); alone +0.5 us
+constexpr int kEncThreads = 512;         // x kEncItems = 4096 positions per scan round: one round per 256x256 stream
 constexpr int kEncItems = 4;            // consecutive positions per thread per scan round
-#ifndef CGIC_LDS_POS
-#define CGIC_LDS_POS 8192
-#endif
-constexpr int kLdsPos = CGIC_LDS_POS;           // streams up to this many positions keep phase-A results in LDS
+constexpr int kLdsPos = 8192;           // streams up to this many positions keep phase-A results in LDS
 constexpr int kLdsPosSmall = 4096;              // ... and the small instantiation of the compress kernel (grids up to 64x64)
 
 // -------------------------------------------------------------------------------------------
@@ -165,6 +160,7 @@ __device__ int pack_huffman_stream(const TableDev &t, unsigned long long carry, 
 // ranges).  A part compacts and sizes its own range, tells the others (symbols, bits, its first 32 code bits), learns where
 // its bits start from the parts before it, and packs the output words whose FIRST payload bit is its own; the tail of its last
 // word comes from the heads of the parts behind it.  No atomics on the output, no pre-zeroed buffer.
+constexpr int kEncPartPos = 4096;         // positions per part of a split stream: measured 8192 -> 14.1 us, 4096 -> 12.2 us, 3072 -> 12.2 us (8 tiles of 768x768)
 constexpr int kEncMaxParts = 7;           // descriptors of a stream fit two ticket slots: 4 words per part + the reader count
 constexpr int kEncDoneWord = 4 * kEncMaxParts;
 struct EncExchange {
@@ -726,14 +722,8 @@ extern "C" int cgic_compress_streams(const cgic_table *t, const int64_t *ind, co
     const bool split = B * 6 <= (int64_t)(16384 / 4);
     for (int g = 0; g < 3; ++g) {
         const int64_t npos = (h >> (2 - g)) * (w >> (2 - g));
-#ifndef CGIC_ENC_PART_POS
-#define CGIC_ENC_PART_POS 4096       // positions per part: measured 8192 -> 14.1 us, 4096 -> 12.2 us, 3072 -> 12.2 us (8 tiles of 768x768)
-#endif
-        int64_t P = split && npos > kLdsPos ? (npos + CGIC_ENC_PART_POS - 1) / CGIC_ENC_PART_POS : 1;
+        int64_t P = split && npos > kLdsPos ? (npos + kEncPartPos - 1) / kEncPartPos : 1;
         P = P > kEncMaxParts ? kEncMaxParts : P;
-#ifdef CGIC_ENC_PARTS_MAX
-        P = P > CGIC_ENC_PARTS_MAX ? CGIC_ENC_PARTS_MAX : P;
-#endif
         a.parts[g] = (int)P;
         const int64_t per = P > 1 ? (((npos + P - 1) / P) + 3) & ~(int64_t)3 : npos;
         if (npos > kLdsPos && per > longest) longest = per;

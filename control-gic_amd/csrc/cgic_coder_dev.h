@@ -4,35 +4,16 @@
 #pragma once
 #include "cgic_common.h"
 
+namespace cgic {
+
 // VGPR caps of the per-image kernels (registers per lane).  What matters is not their own occupancy but what they
 // leave to the kernels of OTHER batches in flight on the same CU (bench.py --lanes): a 512-thread VQ workgroup takes
 // 2 x 152 of a SIMD's 512 registers per lane.
-#ifndef CGIC_CAP_COMPRESS
-#define CGIC_CAP_COMPRESS 48     // 49 uncapped, no spills at 48: 4 waves x 48 fit beside a VQ workgroup (86.1 -> 87.9 GPixel/s at 4 lanes)
-#endif
-#ifndef CGIC_CAP_DECODE
-#define CGIC_CAP_DECODE 0        // 69 uncapped; 56 / 48 spill 13 / 36 registers and were measured slower (85.8 / 83.3)
-#endif
-#ifndef CGIC_CAP_MERGE
-#define CGIC_CAP_MERGE 0
-#endif
-#if CGIC_CAP_COMPRESS
-#define CGIC_VGPR_CAP_COMPRESS __attribute__((amdgpu_num_vgpr(CGIC_CAP_COMPRESS / 2)))
-#else
-#define CGIC_VGPR_CAP_COMPRESS
-#endif
-#if CGIC_CAP_DECODE
-#define CGIC_VGPR_CAP_DECODE __attribute__((amdgpu_num_vgpr(CGIC_CAP_DECODE / 2)))
-#else
-#define CGIC_VGPR_CAP_DECODE
-#endif
-#if CGIC_CAP_MERGE
-#define CGIC_VGPR_CAP_MERGE __attribute__((amdgpu_num_vgpr(CGIC_CAP_MERGE / 2)))
-#else
-#define CGIC_VGPR_CAP_MERGE
-#endif
-
-namespace cgic {
+constexpr int kCapCompress = 48;     // 49 uncapped, no spills at 48: 4 waves x 48 fit beside a VQ workgroup (86.1 -> 87.9 GPixel/s at 4 lanes)
+// (amdgpu_num_vgpr counts VGPR + AGPR on gfx950: the attribute carries half the cap)
+#define CGIC_VGPR_CAP_COMPRESS __attribute__((amdgpu_num_vgpr(kCapCompress / 2)))
+// The decoders and the merge carry no cap: the decoders use 69, caps of 56 / 48 spill 13 / 36 registers and were measured slower
+// (85.8 / 83.3).
 
 constexpr int kDecLutMax = 1 << kLutBitsMax;        // 13-bit LUT
 
@@ -46,15 +27,9 @@ constexpr int kLdsTrieNodes = 2048;                // decode tries up to this ma
 constexpr int kFastChunks = 192;                   // streams up to this many chunks (1.5 KB) cache per-position
                                                    // lengths / symbols / chunk functions for the lane-per-chunk pass C
 constexpr int kPackBig = 0xFF;                     // packed "past the end" marker (max real next = 63 + 64)
-#ifndef CGIC_DEC_PARTS_MAX
-#define CGIC_DEC_PARTS_MAX 12
-#endif
-constexpr int kDecPartsMax = CGIC_DEC_PARTS_MAX;                    // ... and at most in the one-launch form: flags 0..11 and the reader count (word 15) share one ticket slot
+constexpr int kDecPartsMax = 12;                    // ... and at most in the one-launch form: flags 0..11 and the reader count (word 15) share one ticket slot
 constexpr int kDecDoneWord = 15;
-#ifndef CGIC_DEC_PART_BYTES
-#define CGIC_DEC_PART_BYTES 1280
-#endif
-constexpr int kDecPartBytes = CGIC_DEC_PART_BYTES;     // stream bytes per part: 160 chunks, one pass-A round of 16 waves x 10 chunks
+constexpr int kDecPartBytes = 1280;     // stream bytes per part: 160 chunks, one pass-A round of 16 waves x 10 chunks
 
 struct DecodeArgs {
     TableDev tab;
@@ -73,11 +48,8 @@ struct DecodeArgs {
 };
 
 // the self-synchronising one-workgroup-per-image decoder (cgic_decode_ss.hip); launched by cgic_decompress_streams
-#ifndef CGIC_SS_THREADS_SMALL
-#define CGIC_SS_THREADS_SMALL 256
-#endif
+constexpr int kSsThreadsSmall = 256;      // its workgroup for small streams (large ones: kDecThreads)
 __global__ void decode_image_kernel(DecodeArgs a, int stage_cap, int chunk_cap);
-__global__ void decode_image_stream_kernel(DecodeArgs a, int stage_cap, int chunk_cap);
 struct DecodeImageArgs { DecodeArgs a; int stage_cap, chunk_cap; };      // its argument block in a grouped launch
 
 static const int kModeStreams[7] = {0x1f, 0x16, 0x0d, 0x0b, 0x01, 0x02, 0x04};  // model.py:225-260

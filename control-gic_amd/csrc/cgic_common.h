@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <functional>
@@ -71,6 +72,17 @@ int acquire_tickets(hipStream_t stream, int n, unsigned int **ptr, int kind = 0)
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (function, device) and size -- not on every launch
 int ensure_dynamic_lds(const void *fn, size_t bytes);
+
+// compute units of the current device (cached per device): persistent-workgroup kernels size their grids by it
+int device_cu_count(int *out);
+
+// integer environment knobs of the dev tooling (tools/probes/): they exist in `make dbg` builds only, the shipping library reads
+// no environment
+#ifdef CGIC_DEV_KNOBS
+inline int dev_knob(const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; }
+#else
+inline int dev_knob(const char *) { return 0; }
+#endif
 
 // ---- launch groups (cgic_group_begin / _select / _launch, cgic_launch.hip) ------------------------------------------
 // Independent sub-batches of DIFFERENT shapes (the shape groups of one tiled image: inference_high_resolution.py:112-125 cuts

@@ -765,23 +765,20 @@ __device__ __forceinline__ void decode_split_body(const DecodeArgs &a_in, const 
     if (tid == 0 && part == nparts - 1) *dc = s_count > cap ? -3 : s_count;      // the last part knows the total
 }
 
-__global__ __launch_bounds__(kDecThreads) CGIC_VGPR_CAP_DECODE void decode_split_kernel(DecodeArgs a)
+__global__ __launch_bounds__(kDecThreads) void decode_split_kernel(DecodeArgs a)
 {
     decode_split_body(a, own_blk());
 }
 
 // several shape groups in one launch (cgic_common.h: launch groups)
-__global__ __launch_bounds__(kDecThreads) CGIC_VGPR_CAP_DECODE void decode_split_grouped_kernel(Grouped<DecodeArgs> g)
+__global__ __launch_bounds__(kDecThreads) void decode_split_grouped_kernel(Grouped<DecodeArgs> g)
 {
     Blk blk;
     decode_split_body(g.a[group_locate(g, &blk)], blk);
 }
 
 constexpr int kMergeThreads = 512;
-#ifndef CGIC_MERGE_ONE_BAND_THREADS
-#define CGIC_MERGE_ONE_BAND_THREADS 512      // 1024 until round 3: 512 measured ~0.5-1 us per step better in flight
-#endif
-constexpr int kMergeOneBandThreads = CGIC_MERGE_ONE_BAND_THREADS;       // throughput mode: one band per image
+constexpr int kMergeOneBandThreads = 512;       // throughput mode: one band per image (1024 until round 3: 512 measured ~0.5-1 us per step better in flight)
 constexpr int kMergeBands = 4;          // row bands per image at least; more for few large images (gridDim.x)
 
 struct MergeArgs {
@@ -832,19 +829,11 @@ typedef unsigned int cgic_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int cgic_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void nt_store16(void *p, const void *v)
 {
-#ifndef CGIC_MERGE_PLAIN_STORES
     __builtin_nontemporal_store(*reinterpret_cast<const cgic_u32x4 *>(v), reinterpret_cast<cgic_u32x4 *>(p));
-#else
-    *reinterpret_cast<cgic_u32x4 *>(p) = *reinterpret_cast<const cgic_u32x4 *>(v);
-#endif
 }
 __device__ __forceinline__ void nt_store8(void *p, const void *v)
 {
-#ifndef CGIC_MERGE_PLAIN_STORES
     __builtin_nontemporal_store(*reinterpret_cast<const cgic_u32x2 *>(v), reinterpret_cast<cgic_u32x2 *>(p));
-#else
-    *reinterpret_cast<cgic_u32x2 *>(p) = *reinterpret_cast<const cgic_u32x2 *>(v);
-#endif
 }
 
 template <int NT, bool WAIT = false>
@@ -1188,13 +1177,13 @@ __device__ __forceinline__ void merge_body(const MergeArgs &a, const Blk blk, un
 }
 
 template <int NT>
-__global__ __launch_bounds__(NT) CGIC_VGPR_CAP_MERGE void merge_kernel(MergeArgs a)
+__global__ __launch_bounds__(NT) void merge_kernel(MergeArgs a)
 {
     merge_body<NT>(a, own_blk());
 }
 
 // several shape groups in one launch (cgic_common.h: launch groups)
-__global__ __launch_bounds__(kMergeThreads) CGIC_VGPR_CAP_MERGE void merge_grouped_kernel(Grouped<MergeArgs> g)
+__global__ __launch_bounds__(kMergeThreads) void merge_grouped_kernel(Grouped<MergeArgs> g)
 {
     Blk blk;
     merge_body<kMergeThreads>(g.a[group_locate(g, &blk)], blk);
@@ -1227,11 +1216,11 @@ __device__ __forceinline__ void decode_merge_body(const DecodeMergeArgs &p, cons
     merge_body<kDecThreads, true>(p.m, Blk{r - b * p.nbands, b, 0u, p.nbands, p.B}, p.done + (size_t)b * kTicketStride, p.ndec,
                                   p.ndec + p.active_bands);
 }
-__global__ __launch_bounds__(kDecThreads) CGIC_VGPR_CAP_DECODE void decode_merge_kernel(DecodeMergeArgs p)
+__global__ __launch_bounds__(kDecThreads) void decode_merge_kernel(DecodeMergeArgs p)
 {
     decode_merge_body(p, blockIdx.x);
 }
-__global__ __launch_bounds__(kDecThreads) CGIC_VGPR_CAP_DECODE void decode_merge_grouped_kernel(Grouped<DecodeMergeArgs> g)
+__global__ __launch_bounds__(kDecThreads) void decode_merge_grouped_kernel(Grouped<DecodeMergeArgs> g)
 {
     Blk blk;
     const DecodeMergeArgs &p = g.a[group_locate(g, &blk)];
@@ -1276,31 +1265,11 @@ extern "C" int cgic_decode_stream(const cgic_table *t, const uint8_t *in, int64_
 
 static const size_t kLdsBudget = 150 * 1024;
 
-#ifndef CGIC_DEC_WGS_SMALL
-#define CGIC_DEC_WGS_SMALL 4
-#endif
-#ifndef CGIC_DEC_WGS_LARGE
-#define CGIC_DEC_WGS_LARGE 24
-#endif
-#ifdef CGIC_DEV_KNOBS
-static int dev_knob_dec(const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; }
-#else
-static int dev_knob_dec(const char *) { return 0; }      // the environment knobs exist in `make dbg` builds only
-#endif
-static int device_cu_count_dec(int *out)
-{
-    static std::atomic<int> cached{0};
-    int n = cached.load();
-    if (n == 0) {
-        int dev = 0;
-        CGIC_HIP_TRY(hipGetDevice(&dev));
-        CGIC_HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        if (n <= 0) n = 256;
-        cached.store(n);
-    }
-    *out = n;
-    return CGIC_OK;
-}
+// decoder workgroups per image (decode_split_kernel): grids up to 64x64 | beyond | beyond when the merge rides in the launch -- 16 are
+// as fast as 24 per call, and the CUs they leave go to merge bands (2040x1356 chain 0.105 -> 0.104 ms; 12 falls off the fast path)
+constexpr unsigned int kDecWgsSmall = 4, kDecWgsLarge = 24, kDecWgsFusedLarge = 16;
+// merge bands per image are doubled while the launch has fewer than kMergeWgs workgroups and a band keeps 2 x kMergeMinRows coarse rows
+constexpr int64_t kMergeWgs = 256, kMergeMinRows = 1;
 static std::atomic<int> g_decode_mode{CGIC_DECODE_AUTO};
 static std::atomic<unsigned int *> g_decode_stats{nullptr};
 extern "C" int cgic_decode_stats(unsigned int *device_counters)
@@ -1391,13 +1360,9 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
     // so not more than needed): ~256 workgroups in all, at least 2 coarse rows per band
     // Decoder and merge go out as ONE launch when every workgroup of both gets a CU of its own (B = 1 .. a few dozen images, or
     // a few tiles; inside a launch group: within the group's share of the chip)
-#ifndef CGIC_DEC_WGS_FUSED_LARGE
-#define CGIC_DEC_WGS_FUSED_LARGE 16      // decoder workgroups per large grid when the merge rides in the launch: as fast as 24 per call, and the
-                                         // CUs it leaves go to merge bands (2040x1356 chain 0.105 -> 0.104 ms; 12 falls off the fast path)
-#endif
-    const unsigned int ndec = large ? CGIC_DEC_WGS_FUSED_LARGE : CGIC_DEC_WGS_SMALL;
+    const unsigned int ndec = large ? kDecWgsFusedLarge : kDecWgsSmall;
     int cus = 0;
-    rc = device_cu_count_dec(&cus);
+    rc = device_cu_count(&cus);
     if (rc) return rc;
     const int64_t cu_share = (int64_t)((double)cus * group_cu_share() + 0.5);
     // The fused launch's merge bands SPIN on the decoder workgroups of the same launch (wait_decoded).  Alone on the chip that cannot
@@ -1408,17 +1373,11 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
     // of them is resident at once and nobody waits for a slot.  CGIC_DECODE_LATENCY is the caller's statement that this call has
     // the GPU to itself (one batch at a time): it keeps the whole chip as its budget.
     const int64_t cu_budget = dec_mode == CGIC_DECODE_LATENCY ? cu_share : cu_share / 2;
-    const bool fuse_base = dec_mode != CGIC_DECODE_THROUGHPUT && d.tab.max_len <= 64 && B * 3 <= (int64_t)(16384 / 4) && !dev_knob_dec("CGIC_NO_DECODE_MERGE");
+    const bool fuse_base = dec_mode != CGIC_DECODE_THROUGHPUT && d.tab.max_len <= 64 && B * 3 <= (int64_t)(16384 / 4) && !dev_knob("CGIC_NO_DECODE_MERGE");
     int64_t nbands = kMergeBands;
     {
         const int64_t h4 = h >> 2;
-#ifndef CGIC_MERGE_MINROWS
-#define CGIC_MERGE_MINROWS 1
-#endif
-#ifndef CGIC_MERGE_WGS
-#define CGIC_MERGE_WGS 256
-#endif
-        while (nbands * B < CGIC_MERGE_WGS && nbands * 2 <= h4 / CGIC_MERGE_MINROWS) {
+        while (nbands * B < kMergeWgs && nbands * 2 <= h4 / kMergeMinRows) {
             // (keep a small launch fusable with its decoder: see below)
             if (fuse_base && B * (int64_t)(ndec + 2 * nbands) > cu_budget && B * (int64_t)(ndec + nbands) <= cu_budget) break;
             nbands *= 2;
@@ -1452,7 +1411,6 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
         }
     }
     bool ss = false;
-#ifndef CGIC_DEC_NO_SS
     if (d.tab.max_len <= 64 && dec_mode == CGIC_DECODE_THROUGHPUT) {
         const size_t bits_cap = per * (size_t)d.tab.max_len + 3 * 64;
         const size_t stage_cap = align16(bits_cap / 8 + 3 * 48), chunk_cap = align16(bits_cap / 64 + 8);
@@ -1460,22 +1418,15 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
         if (lds_ss <= kLdsBudget) {
             ss = true;
             { int rc_ = ensure_dynamic_lds((const void *)decode_image_kernel, lds_ss); if (rc_) return rc_; }
-            const int T = large ? kDecThreads : CGIC_SS_THREADS_SMALL;
+            const int T = large ? kDecThreads : kSsThreadsSmall;
             const int sc_ = (int)stage_cap, cc_ = (int)chunk_cap;
             DecodeImageArgs dia;
             dia.a = d; dia.stage_cap = sc_; dia.chunk_cap = cc_;
-            static const bool per_stream = getenv("CGIC_SS_PER_STREAM") && atoi(getenv("CGIC_SS_PER_STREAM")) != 0;      // dev A/B, round 6
-            if (per_stream && !group_recording()) {
-                { int rc_ = ensure_dynamic_lds((const void *)decode_image_stream_kernel, lds_ss); if (rc_) return rc_; }
-                hipLaunchKernelGGL(decode_image_stream_kernel, dim3((unsigned)B, 3u), dim3(T), lds_ss, s, d, sc_, cc_);
-                rc = launch_check("decode_image_stream_kernel");
-            } else
             rc = launch_or_record(KID_DECODE_IMAGE, dim3((unsigned)B), dim3(T), lds_ss, dia, s, [=] {
                 hipLaunchKernelGGL(decode_image_kernel, dim3((unsigned)B), dim3(T), lds_ss, s, d, sc_, cc_);
                 return launch_check("decode_image_kernel"); });
         }
     }
-#endif
     if (ss) {
     } else if (d.tab.max_len <= 64) {
         if (lds_d > 48 * 1024)
@@ -1493,7 +1444,7 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
             c.bf = d.bf + (size_t)b0 * 3 * kDecPartsMax * kWave;
             rc = acquire_tickets(s, (int)(nb * 3), &c.tick);
             if (rc) return rc;
-            const dim3 grid_c(large ? CGIC_DEC_WGS_LARGE : CGIC_DEC_WGS_SMALL, (unsigned)nb);
+            const dim3 grid_c(large ? kDecWgsLarge : kDecWgsSmall, (unsigned)nb);
             rc = launch_or_record(KID_DECODE_SPLIT, grid_c, dim3(kDecThreads), lds_d, c, s, [=] {
                 hipLaunchKernelGGL(decode_split_kernel, grid_c, dim3(kDecThreads), lds_d, s, c);
                 return launch_check("decode_split_kernel"); });

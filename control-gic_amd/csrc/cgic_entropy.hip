@@ -34,6 +34,7 @@ namespace cgic {
 
 constexpr int kEntThreads = 256;
 constexpr int kEntWaves = kEntThreads / kWave;
+constexpr int kEntTilesPpw = 4;      // patches a wave walks in the windowed (tiles) form
 constexpr int kWin = 2;            // bins evaluated per pixel: the two that bracket it
 constexpr int kHistStride = 36;    // dwords per bin: 4 sub-patches x 8 replicas + 4 pad (conflict-free b128 rows)
 constexpr float kFixScale = 67108864.f;           // 2^26: a replica collects <= 8 pixels with values <= 1, four replicas < 2^31
@@ -512,11 +513,7 @@ static int entropy_maps_launch(const void *x, bool u8, int64_t B, int64_t H, int
     memcpy(ba.v, bins, sizeof(ba.v));
     hipStream_t s = (hipStream_t)stream;
     // a wave walks `ppw` patches of its row band: 4 for a 256-wide image (one workgroup per 16 rows)
-#ifdef CGIC_ENT_PPW
-    const int ppw = CGIC_ENT_PPW;       // dev: tools/build_variants.sh
-#else
     const int ppw = 4;
-#endif
     const int64_t per_wg = (int64_t)kEntWaves * ppw;
     dim3 grid((unsigned)((W / 16 + per_wg - 1) / per_wg), (unsigned)(H / 16), (unsigned)B);
     // exp(-0.5 (r/sigma)^2) = exp2(c r^2), c = -0.5 log2(e) / sigma^2 (float64 on the host, rounded once)
@@ -526,7 +523,7 @@ static int entropy_maps_launch(const void *x, bool u8, int64_t B, int64_t H, int
     a.bins = ba;
 #ifdef CGIC_DEV_KNOBS
     // dev: pad the workgroup's LDS so that fewer of them fit a CU (co-residency experiments)
-    static const int pad = getenv("CGIC_ENT_PAD") ? atoi(getenv("CGIC_ENT_PAD")) : 0;
+    const int pad = dev_knob("CGIC_ENT_PAD");
     if (pad > 0 && !u8 && !group_recording()) {
         CGIC_HIP_TRY(hipFuncSetAttribute((const void *)entropy_maps_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
         hipLaunchKernelGGL(entropy_maps_kernel<false>, grid, dim3(kEntThreads), (size_t)pad, s, a);
@@ -589,10 +586,7 @@ extern "C" int cgic_entropy_maps_tiles(const void *src, int is_u8, int64_t N, in
     if (N == 0) return CGIC_OK;
     EntWinArgs a;
     memcpy(a.e.bins.v, bins, sizeof(a.e.bins.v));
-#ifndef CGIC_ENT_TILES_PPW
-#define CGIC_ENT_TILES_PPW 4
-#endif
-    a.e.x = nullptr; a.e.H = th; a.e.W = tw; a.e.ppw = CGIC_ENT_TILES_PPW; a.e.e8 = e8; a.e.e16 = e16; a.e.x_out = x_out; a.e.flat8 = flat8;
+    a.e.x = nullptr; a.e.H = th; a.e.W = tw; a.e.ppw = kEntTilesPpw; a.e.e8 = e8; a.e.e16 = e16; a.e.x_out = x_out; a.e.flat8 = flat8;
     a.e.exp2_scale = (float)(-0.5 * 1.4426950408889634 / ((double)sigma * (double)sigma));
     a.w.src = src; a.w.srcH = (int)H; a.w.srcW = (int)W; a.w.T = T;
     for (int k = 0; k < kEntMaxTiles; ++k) {

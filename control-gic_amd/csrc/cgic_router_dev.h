@@ -231,6 +231,8 @@ constexpr int kRefWavesMax = 8;            // waves of a workgroup that evaluate
 constexpr int kRefListCap = 1024;          // band elements listed per sweep (a longer band is swept range by range)
 constexpr int kRefFlatSlots = 128;         // distinct grays of constant patches per select (more: the rest go patch by patch)
 constexpr unsigned int kRefEmpty = 0xFFFFFFFFu;      // (a NaN pattern: never the gray of a constant patch)
+constexpr int kFusedQRounds = 8;          // rounds of its waves' work above which an image with a workgroup of its own starts over with the launch's queues (refine_select, BAIL)
+constexpr int kFusedHelpWaves = 2;        // waves of a fused-launch router that did not refine itself and help while the board says busy (router_body)
 constexpr int kRefBitWords = 176;          // 64-bit words of the band's member bitmap: 11264 elements, more than any segment whose maps fit kRouterFusedLds
 
 // ---- evaluating a band's patches with the whole chip -------------------------------------------------------------------------
@@ -857,15 +859,7 @@ __device__ __forceinline__ float refine_select(const RouterArgs &a, int qid, int
         // eight -- the restart and the queue's hand-offs cost ~15 us, and a band of a few rounds is done sooner where it was found)
         // (... and only a band of at most 64 members, the FEW form: a band of hundreds of mostly constant patches -- flat regions with
         // edges -- spends its time in passes over the map that the restart would repeat: 57 us where it was found, 62 with the queues)
-#ifdef CGIC_FUSED_Q_MANY        // dev A/B: long bands of more than 64 members of an image with a workgroup of its own go to the queues too
-        const bool many_ok = true;
-#else
-        const bool many_ok = false;
-#endif
-#ifndef CGIC_FUSED_Q_ROUNDS
-#define CGIC_FUSED_Q_ROUNDS 8
-#endif
-        if (a.rq.nq != 0 && heavy * UPP > (nb > 1 ? 4 : CGIC_FUSED_Q_ROUNDS) * NWR && (nb > 1 || few || many_ok)) {      // (workgroup-uniform, and the same in every row band)
+        if (a.rq.nq != 0 && heavy * UPP > (nb > 1 ? 4 : kFusedQRounds) * NWR && (nb > 1 || few)) {      // (workgroup-uniform, and the same in every row band)
             *bail_out = true;
             __builtin_amdgcn_s_setprio(0);
             return t_a;
@@ -1223,55 +1217,34 @@ __device__ __forceinline__ void router_body(const RouterArgs &a, int64_t blk, un
         if constexpr (SPLIT) {
             RouterResume rr;
             rr.at = 0; rr.thr = 0.f; rr.si.h = nullptr; rr.si.digit = 0; rr.si.before = 0;
-#ifdef CGIC_FUSED_Q_NORESUME      // dev A/B: the second attempt starts from the top
-            const int how = router_team<NT, true, false, false, true>(a, blk, dyn);
-#else
             const int how = router_team<NT, true, false, false, true>(a, blk, dyn, 0u, &rr);
-#endif
             if (how != 1) {
                 // Done in the plain code.  One image per workgroup (round 6): the images of the launch whose bands ARE long have
                 // started over with the refinement queues -- while any of them holds a band open, the waves of a workgroup that had
                 // a (short) band of its own evaluate patches for them instead of leaving: tie-heavy content comes by the batch.  The
                 // ordinary image (how == 0: no band) leaves at once -- the look at the board is a memory round trip at the very end
                 // of the launch's critical path (measured: +1.9 us on every launch when every router took it).
-#ifndef CGIC_FUSED_Q_NOAFTER
-#ifdef CGIC_FUSED_Q_REFINERS_ONLY      // dev A/B: only the routers that refined look at the board (the form of the first half of round 6)
-                if (how == 2 && a.bands <= 1 && a.rq.nq != 0 && a.rf.x != nullptr) {
-#else
                 // (a launch WITH queues is one the caller chose for tie-heavy batches -- pipeline.HotPathPipeline.decide: there every
                 // router looks, and an image that starts over says so on the board BEFORE it does (below): the ordinary images'
                 // routers are done 2-3 us before its list is out and used to be gone by then -- smooth 8-bit batches: two images of
                 // 64 with 30-40 patches each and ~12 helpers that arrived 5-15 us late)
                 if (a.bands <= 1 && a.rq.nq != 0 && a.rf.x != nullptr) {
-#endif
                     RefineShared *rs = router_refine_shared(a, dyn);
                     __syncthreads();
                     if (threadIdx.x == 0) rs->flag = ld_sc1(a.rq.board + QB_BUSY);
                     __syncthreads();
-#ifndef CGIC_FUSED_HELP_WAVES
-#define CGIC_FUSED_HELP_WAVES 2
-#endif
-                    if (rs->flag) refine_help_while_busy(a, &rs->tl, how == 2 ? kRefWavesMax : CGIC_FUSED_HELP_WAVES);
+                    if (rs->flag) refine_help_while_busy(a, &rs->tl, how == 2 ? kRefWavesMax : kFusedHelpWaves);
                 }
-#endif
                 return;
             }
             __syncthreads();
             // second attempt, from the top: the row bands of a large tile split the band between them; an image with a workgroup of
             // its own publishes it to the launch's queues (the stand-alone launch's instantiation: owner + helpers)
-#ifdef CGIC_FUSED_Q_NOHELP      // dev A/B: without the queue instantiation in the kernel
-            router_team<NT, true, false, true, false>(a, blk, dyn);
-#else
             if (a.bands > 1) router_team<NT, true, false, true, false>(a, blk, dyn);
             else {
-#ifndef CGIC_FUSED_Q_REFINERS_ONLY
                 if (threadIdx.x == 0) add_sc1(a.rq.board + QB_BUSY, 1u);        // held until this image's last select (router_team: busy_held)
                 router_team<NT, true, true, false, false>(a, blk, dyn, 1u, &rr);
-#else
-                router_team<NT, true, true, false, false>(a, blk, dyn);
-#endif
             }
-#endif
         } else {
             router_team<NT, true, HELP, false, false>(a, blk, dyn);
         }

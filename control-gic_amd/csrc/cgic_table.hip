@@ -156,6 +156,23 @@ int ensure_dynamic_lds(const void *fn, size_t bytes)
     return CGIC_OK;
 }
 
+int device_cu_count(int *out)
+{
+    static std::mutex mu;
+    static std::map<int, int> cus;
+    int dev = 0;
+    CGIC_HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cus.find(dev);
+    if (it == cus.end()) {
+        int n = 0;
+        CGIC_HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        it = cus.emplace(dev, n > 0 ? n : 256).first;
+    }
+    *out = it->second;
+    return CGIC_OK;
+}
+
 struct DevImage {
     int32_t *len = nullptr;
     uint32_t *code = nullptr;

@@ -147,44 +147,6 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return __builtin_bit_cast(double, ((unsigned long long)b.x << 32) | a.x) + __builtin_bit_cast(double, ((unsigned long long)b.y << 32) | a.y);
 }
 
-#ifdef CGIC_VQF_DRAIN_HANDOFF      // dev A/B: round 5's hand-off (partials in the caller's workspace, drained before the ticket)
-// Variant for the filter path, executed by ONE wave: lane 0 publishes the workgroup's partial (write-through
-// store, drained, then the ticket); the wave of the last workgroup sums all partials in a fixed order.
-__device__ __forceinline__ void finish_loss_wave(double block_sum, double *sq_partial, unsigned int *ticket, double count,
-                                                 float beta, int legacy, float *loss, unsigned int blk, unsigned int nblk, unsigned int = 0)
-{
-    const int lane = lane_id();
-    int last = 0;
-    if (lane == 0) {
-#ifdef CGIC_STRICT_HANDOFF
-        // textbook form (make FLAGS+=-DCGIC_STRICT_HANDOFF): plain store, release at the ticket; for A/B runs against the
-        // write-through shortcut below on a new ROCm / GPU
-        sq_partial[blk] = block_sum;
-        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
-#else
-        __hip_atomic_store(&sq_partial[blk], block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
-#endif
-    }
-    last = __builtin_amdgcn_readfirstlane(last);
-    if (!last) return;
-#ifdef CGIC_STRICT_HANDOFF
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-    // (no acquire fence: sc1 stores on the producers' side, sc1 loads here -- see finish_loss)
-    double a = 0.0;
-    for (unsigned int i = lane; i < nblk; i += kWave)
-        a += __hip_atomic_load(&sq_partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a = wave_sum_f64(a);
-    if (lane == 0) {
-        const float m = (float)(a / count);
-        *loss = legacy ? (m + beta * m) : (beta * m + m);
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-    }
-}
-
-#else
 // Variant for the filter path, executed by ONE wave.  Round 6: the partials live in LIBRARY-owned, zero-on-entry slots (behind the
 // ticket: acquire_tickets) instead of the caller's workspace, and a workgroup publishes -partial -- the sum of squares is never
 // negative, so the sign bit says "written" (a +0.0 partial goes out as -0.0, a NaN stays a NaN with its sign set) -- with a
@@ -229,7 +191,6 @@ __device__ __forceinline__ void finish_loss_wave(double block_sum, double *sq_pa
     if (!last) return;
     loss_collect(slots, ticket, count, beta, legacy, loss, nblk);
 }
-#endif
 // ZT = latent tiles (of 16 vectors) per wave; a wave owns 16*ZT vectors and scans all K codes;
 // a block owns 4 * 16 * ZT vectors.  __launch_bounds__(256, 2): a <=256-VGPR budget makes hipcc
 // pick the VGPR-destination MFMA form (no v_accvgpr_read per output).
@@ -258,8 +219,9 @@ struct VqArgs {
     unsigned int n_early, g_early, g_late;
     // loss hand-off of the filter path: 0 = the VQ workgroups take a ticket, the last one sums (finish_loss_wave); 2 (round 6) = a VQ
     // workgroup only PUBLISHES its partial and workgroup 0 waits for all of them and sums -- 256 returning atomics on one word at the
-    // end of every VQ workgroup were 2.3 us of the launch; 1 = dev A/B: the router workgroups of the fused launch take the ticket among
-    // themselves and the last ROUTER sums (loss_collect_by_routers: slower, the routers are the launch's tail)
+    // end of every VQ workgroup were 2.3 us of the launch; 1 = the router workgroups of the fused launch take the ticket among
+    // themselves and the last ROUTER sums (loss_collect_by_routers: slower, the routers are the launch's tail).  Live values: every
+    // launch sets 2 with a loss and 0 (tail not entered: sq_partial is NULL) without one; nothing sets 1 or enters the tail with 0.
     unsigned int tail_mode;
     // quant_conv fused in front of the quantiser (model.py:51,110): z = W h (+ b), 4 -> 4, or NULL
     const float *conv_w, *conv_b;
@@ -276,7 +238,6 @@ struct VqArgs {
     float *probe_scores, *probe_aux;
 };
 
-#ifndef CGIC_VQF_DRAIN_HANDOFF
 // tail_mode 1, called by every thread of a ROUTER workgroup of the fused launch when its routing is done: the routers take the ticket
 // among themselves (64 atomics spread over ~1 us instead of 256 within the VQ workgroups' last microsecond) and the last one sums
 // the VQ workgroups' partials -- which were published long before in the usual launch (the routers are its tail), and are simply
@@ -291,9 +252,6 @@ __device__ __forceinline__ void loss_collect_by_routers(const VqArgs &a, unsigne
     if (!last) return;
     loss_collect(reinterpret_cast<unsigned long long *>(a.sq_partial), a.ticket, (double)a.N * 4.0, a.beta, a.legacy, a.loss, a.nblk);
 }
-#else
-__device__ __forceinline__ void loss_collect_by_routers(const VqArgs &, unsigned int) {}
-#endif
 
 // The reference's quant_conv is a torch.nn.Conv2d(4, 4, 1) on the CPU.  Its fp32 rounding sequence is an fma chain over
 // the input channels in order, with the bias either seeding the accumulator or added at the end -- oneDNN picks one or
@@ -700,6 +658,7 @@ __device__ __forceinline__ void vqf_stage(const float *__restrict__ cb, const in
 // PERM: the prepared image is permuted -- near-duplicate rows (a trained codebook's clusters: quantize.py:22-26,78) sit in one tile,
 // so that the 32-code exact step resolves them instead of every vector running into the all-K scan; "index" below is then the key
 // (original index << 16 | position): ties go to the lowest ORIGINAL index like the reference's argmin, the position finds the row.
+constexpr int kVqfTurnPrio = 1;      // issue priority of the wave whose turn it is (the loop over the groups below)
 template <int NT, bool ALIGNED, bool CONV, bool PROBE = false, bool PERM = false>
 __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *smem, const unsigned int vblk)
 {
@@ -829,21 +788,14 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
 #ifdef CGIC_PHASE_CLOCKS      // dev: per-wave (loop start, loop end) of the first 64 workgroups, slots 512 + 8 wg + wave of g_blk_t
     if (lane == 0 && vblk < 64 && wave < 8) g_blk_t[2 * (512 + 8 * vblk + wave)] = wall_clock64();
 #endif
-#ifndef CGIC_VQF_TURN_PRIO
-#define CGIC_VQF_TURN_PRIO 1
-#endif
-#ifndef CGIC_VQF_NO_TURNS
     // Two waves share a SIMD (wave w and w + NW/2), and the arbiter serves the OLDER one first: waves 0..NW/2-1 ran their two
     // groups in 11.6 us and left, their younger mates then ran alone -- a lone wave's MFMAs and VALU work do not overlap -- until
     // 14.6 us (per-wave loop clocks, tools/probes/probe_vq_phases.py waves).  The mates take turns instead: group by group the one
     // that is behind gets the issue priority, so both have work until the end.
     int turn = wave >= NW / 2 ? 1 : 0;
-#endif
     while (cur < blk_hi) {
-#ifndef CGIC_VQF_NO_TURNS
-        if (turn & 1) __builtin_amdgcn_s_setprio(CGIC_VQF_TURN_PRIO); else __builtin_amdgcn_s_setprio(0);
+        if (turn & 1) __builtin_amdgcn_s_setprio(kVqfTurnPrio); else __builtin_amdgcn_s_setprio(0);
         ++turn;
-#endif
         const int64_t grp = cur;
         const int64_t base = grp * G;
         CGIC_PHASE_T0();
@@ -909,20 +861,8 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
                             a.probe_scores[(base + 32 * t + j) * K + 32 * T + 8 * (r >> 2) + 4 * hf + (r & 3)] = ldexpf(D[t][r], -qs[t]);
                     }
                     float u = __builtin_inff();        // seeded with a constant: a two-operand fminf() canonicalises both operands first
-#ifdef CGIC_VQF_TREE
-                    {
-                        float ua = u, ub = u;
-#pragma unroll
-                        for (int r = 0; r < 8; r += 2) {
-                            ua = __builtin_fminf(__builtin_fminf(ua, D[t][r]), D[t][r + 1]);
-                            ub = __builtin_fminf(__builtin_fminf(ub, D[t][8 + r]), D[t][9 + r]);
-                        }
-                        u = __builtin_fminf(ua, ub);
-                    }
-#else
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) u = __builtin_fminf(__builtin_fminf(u, D[t][r]), D[t][r + 1]);     // v_min3_f32 on the raw MFMA outputs
-#endif
                     // the tile's index rides in the low 5 mantissa bits of its minimum (one v_and_or_b32 instead of a
                     // compare + select per tile); the 2^-18 relative perturbation is part of the margin
                     u = __uint_as_float((__float_as_uint(u) & ~31u) | (unsigned int)T);
@@ -1070,18 +1010,7 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
                             bi = take ? c : bi;
                         }
                     }
-#ifndef CGIC_VQF_SHFLMIN
                     wave_argmin(bd, bi);
-#else
-#pragma unroll
-                    for (int off = 1; off < 64; off <<= 1) {
-                        const float od = __shfl_xor(bd, off, kWave);
-                        const int oi = __shfl_xor(bi, off, kWave);
-                        const bool take = od < bd || (od == bd && (unsigned int)oi < (unsigned int)bi);
-                        bd = take ? od : bd;
-                        bi = take ? oi : bi;
-                    }
-#endif
                     wi = lane == v ? bi : wi;
                 }
             } else if (nflag != 0) {
@@ -1162,12 +1091,7 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
         }
         // indices and z_q leave as nontemporal stores: 6.3 MB per launch that nobody in this launch reads again -- as ordinary stores they
         // sat dirty in the L2s until the end-of-kernel write-back (fused launch 23.2 -> 22.4 us, same box A/B: profiles/r06_vq_ab.md)
-#ifndef CGIC_VQF_PLAIN_STORES
-#define CGIC_VQF_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define CGIC_VQF_STORE(p, v) (*(p) = (v))
-#endif
-        if (idx_out && base + lane < N) CGIC_VQF_STORE(&idx_out[base + lane], (int64_t)(PERM ? wi >> 16 : wi));
+        if (idx_out && base + lane < N) __builtin_nontemporal_store((int64_t)(PERM ? wi >> 16 : wi), &idx_out[base + lane]);
         if (PERM) wi &= 0xFFFF;                                   // from here on: where the row sits
         if (zq_out || a.sq_partial) {
             const uint2 wt = rows32((unsigned int)wi);           // .x: tile 0's winners (lanes 0..31), .y: tile 1's
@@ -1184,8 +1108,8 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
                     if (zq_out) {
                         if (ALIGNED) {
                             float *qb = zq_out + (gb * 4 * hw + gp0 + 32 * t) + out_off;
-                            CGIC_VQF_STORE(&qb[0], za + da);
-                            CGIC_VQF_STORE(&qb[hw], zb + db);
+                            __builtin_nontemporal_store(za + da, &qb[0]);
+                            __builtin_nontemporal_store(zb + db, &qb[hw]);
                         } else {
                             int64_t b, p;
                             divmod(n, &b, &p);
@@ -1201,18 +1125,12 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
         CGIC_PHASE_ACC(3);
     }
 
-#ifndef CGIC_VQF_NO_TURNS
     __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef CGIC_PHASE_CLOCKS
     if (lane == 0 && vblk < 64 && wave < 8) g_blk_t[2 * (512 + 8 * vblk + wave) + 1] = wall_clock64();
 #endif
     CGIC_STAMP(5);
-#ifdef CGIC_VQF_NO_TAIL           // dev: no reduction, no barrier, no hand-off (the loss is garbage): what the tail costs
-    if (false) {
-#else
     if (a.sq_partial) {
-#endif
         // Only wave 0 stays for the hand-off: the other waves leave at the barrier WITHOUT draining their z_q /
         // index stores (an s_waitcnt vmcnt(0) in every wave before the barrier cost ~4 us at the end of every
         // workgroup); wave 0's own stores are long complete by the time it has waited for the others.
@@ -1223,34 +1141,21 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
             double bs = 0.0;
 #pragma unroll
             for (int w = 0; w < NW; ++w) bs += s_wsum[w];
-#ifndef CGIC_VQF_NO_HANDOFF      // dev: reduction + barrier, but no store / ticket / last-workgroup sum
             finish_loss_wave(bs, a.sq_partial, a.ticket, (double)N * 4.0, a.beta, a.legacy, a.loss, vblk, a.nblk, a.tail_mode);
-#else
-            if (bs == 12345.678) a.loss[0] = (float)bs;
-#endif
         }
     }
     CGIC_STAMP(6);
     CGIC_BLK_END();
 }
 
-#ifndef CGIC_VQF_THREADS
-#define CGIC_VQF_THREADS 512
-#endif
-constexpr int kVqfThreads = CGIC_VQF_THREADS;      // one workgroup per CU, 2 waves per SIMD.  Alone at B=64 x 64x64 latents 512 / 768 / 1024 threads are within 1 us of each other; with several batches in flight (bench.py --lanes 4) 512 leaves a third of the register file to the other batches' kernels: 86.9 vs 83.4 (768) vs 82.9 (1024) GPixel/s
+constexpr int kVqfThreads = 512;      // one workgroup per CU, 2 waves per SIMD.  Alone at B=64 x 64x64 latents 512 / 768 / 1024 threads are within 1 us of each other; with several batches in flight (bench.py --lanes 4) 512 leaves a third of the register file to the other batches' kernels: 86.9 vs 83.4 (768) vs 82.9 (1024) GPixel/s
 // 128 registers per lane (4-10 spilled, 20-44 bytes of scratch) instead of 144-150: two 512-thread workgroups then fit a CU's
 // register file, so a ROUTER workgroup of the fused launch (same launch => same allocation) shares its CU with a VQ workgroup
 // instead of holding the CU to itself for ~12 us: fused launch 26.3 -> 24.1 us at B=64 (the VQ kernel alone: 23.3 -> 23.8 on the
 // same GPU), no uneven split of the VQ shares needed any more.
-#ifndef CGIC_VQF_VGPR_CAP
-#define CGIC_VQF_VGPR_CAP 128
-#endif
-#if CGIC_VQF_VGPR_CAP
+constexpr int kVqfVgprCap = 128;
 // (amdgpu_num_vgpr counts VGPR + AGPR on gfx950: the attribute carries half the cap)
-#define CGIC_VQF_BOUNDS __launch_bounds__(kVqfThreads, kVqfThreads / 256 > 1 ? kVqfThreads / 256 : 1) __attribute__((amdgpu_num_vgpr(CGIC_VQF_VGPR_CAP / 2)))
-#else
-#define CGIC_VQF_BOUNDS __launch_bounds__(kVqfThreads, kVqfThreads / 256 > 1 ? kVqfThreads / 256 : 1)
-#endif
+#define CGIC_VQF_BOUNDS __launch_bounds__(kVqfThreads, kVqfThreads / 256 > 1 ? kVqfThreads / 256 : 1) __attribute__((amdgpu_num_vgpr(kVqfVgprCap / 2)))
 
 template <bool ALIGNED, bool CONV>
 __global__ CGIC_VQF_BOUNDS void vq_filter_kernel(VqArgs a)
@@ -1289,9 +1194,6 @@ __global__ CGIC_VQF_BOUNDS void vq_filter_router_kernel(VqArgs a, RouterArgs r, 
     // (every VQ workgroup gets a CU at once and the router workgroups move in beside them)
     const unsigned int rb = router_behind ? a.nblk : 0u, vb = router_behind ? 0u : nrouter;
     if (blockIdx.x - rb < nrouter) {
-#ifdef CGIC_ROUTER_PRIO
-        __builtin_amdgcn_s_setprio(CGIC_ROUTER_PRIO);
-#endif
         router_body<kVqfThreads, false, SPLIT>(r, (int64_t)(blockIdx.x - rb), smem_f);
         loss_collect_by_routers(a, nrouter);
         return;
@@ -1529,29 +1431,6 @@ static int launch_mfma(const float *z, int64_t hw, int64_t N, const float *cb, i
         return launch_check("vq_router_kernel"); });
 }
 
-static int device_cu_count(int *out)
-{
-    static std::mutex mu;
-    static std::map<int, int> cus;
-    int dev = 0;
-    CGIC_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cus.find(dev);
-    if (it == cus.end()) {
-        int n = 0;
-        CGIC_HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        it = cus.emplace(dev, n > 0 ? n : 256).first;
-    }
-    *out = it->second;
-    return CGIC_OK;
-}
-
-#ifdef CGIC_DEV_KNOBS
-static int dev_knob(const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; }
-#else
-static int dev_knob(const char *) { return 0; }      // the environment knobs exist in `make dbg` builds only
-#endif
-
 static bool prepared_is_perm(const void *prepared);      // (below, next to cgic_vq_prepare_f32)
 
 template <bool ALIGNED, bool CONV>
@@ -1574,12 +1453,7 @@ static int launch_filter(const float *z, int64_t hw, int64_t N, const float *cb,
     VqArgs a;
     a.z = z; a.hw = hw; a.N = N; a.cb = cb; a.K = K; a.idx_out = idx; a.zq_out = zq;
     a.sq_partial = nullptr; a.ticket = ws.ticket; a.beta = beta; a.legacy = legacy; a.loss = loss;
-#ifdef CGIC_VQF_DRAIN_HANDOFF
-    a.sq_partial = loss ? ws.partial : nullptr;
-    if (false) {
-#else
     if (loss) {
-#endif
         // the ticket and, behind it, one 8-byte partial per workgroup: library-owned, zero when handed out, zeroed again by the launch
         // (finish_loss_wave); the caller's workspace is not touched by this path
         unsigned int *t = nullptr;
@@ -1589,13 +1463,7 @@ static int launch_filter(const float *z, int64_t hw, int64_t N, const float *cb,
         a.sq_partial = reinterpret_cast<double *>(t + kTicketStride);
     }
     a.nblk = (unsigned int)nblk;
-#if defined(CGIC_VQF_ROUTER_TAIL)
-    a.tail_mode = (router && loss) ? 1u : 0u;       // dev A/B: the routers sum the loss
-#elif !defined(CGIC_VQF_TICKET_TAIL) && !defined(CGIC_VQF_DRAIN_HANDOFF)
     a.tail_mode = loss ? 2u : 0u;                   // workgroup 0 collects (VqArgs::tail_mode)
-#else
-    a.tail_mode = 0u;
-#endif
     a.conv_w = CONV ? qc->weight : nullptr; a.conv_b = CONV ? qc->bias : nullptr; a.conv_bias_first = CONV ? qc->bias_first : 0;
     a.prep = prepared;
     a.stats = g_vq_stats.load(std::memory_order_relaxed);
@@ -1605,17 +1473,13 @@ static int launch_filter(const float *z, int64_t hw, int64_t N, const float *cb,
     int64_t per = (ngroups + nblk - 1) / nblk, g_early = per, g_late = per, n_early = nblk;
     const int64_t late = router ? nblk + router_blocks - cus : 0;
     bool router_first = false;
-#if CGIC_VQF_VGPR_CAP && CGIC_VQF_VGPR_CAP <= 128
     // A router workgroup can share its CU with a VQ workgroup.  Behind the VQ workgroups in the grid (every VQ workgroup gets a
     // CU at once and keeps its even share, the routers move in beside them) the router is free as long as it ends before the VQ
     // does -- beside an issue-bound VQ workgroup it runs ~1.6x slower than alone: 64 images of 256x256 24.1 us fused against
     // 23.5 for the VQ alone (in front with even shares: 27.1 -- the VQ workgroups pair up on the free CUs).  Few large tiles
     // (8 of 768x768: router 21 us alone, VQ 26) keep the older scheme: routers in front, uneven VQ shares.
     const double t_router = 10.9 + 0.000275 * (double)hw, t_vq = 3.0 + 1.25 * (double)per;
-    const bool coresident = router && 1.6 * t_router <= t_vq;
-#else
-    const bool coresident = false;
-#endif
+    const bool coresident = kVqfVgprCap <= 128 && router && 1.6 * t_router <= t_vq;
     if (!coresident && late > 0 && late < nblk && !dev_knob("CGIC_VQ_NOSPLIT")) {
         // how long a router workgroup holds its CU, in groups of VQ work (~1.05 us each per workgroup): measured 12 us at
         // 64x64 latents, 21 us at 192x192 (with its row bands)
