@@ -62,6 +62,12 @@ class Tile(C.Structure):
     _fields_ = [("dst", _vp), ("image_stride", _i64), ("y0", _int), ("x0", _int), ("th", _int), ("tw", _int)]
 
 
+class RateTile(C.Structure):
+    """struct cgic_rate_tile (include/cgic_hip.h): one tile of cgic_rate_curve_tiles"""
+    _fields_ = [("h16", _i32), ("w16", _i32), ("k_c", _i32), ("shape", _i32), ("image", _i32), ("reserved", _i32),
+                ("off_c", _i64), ("off_m", _i64), ("off_f", _i64), ("off_e16", _i64), ("off_e8", _i64)]
+
+
 # name -> (restype, argtypes); every function include/cgic_hip.h declares
 PROTOTYPES = {
     "cgic_last_error": (C.c_char_p, []),
@@ -140,6 +146,9 @@ PROTOTYPES = {
     "cgic_rate_curve_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "cgic_rate_curve": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp, _vp]),
     "cgic_router_ranks": (_int, [_f64, _f64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "cgic_rate_curve_tiles_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "cgic_rate_curve_tiles": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(RateTile), _vp, _i64, _i64, _f64, _vp, _i64,
+                                     _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

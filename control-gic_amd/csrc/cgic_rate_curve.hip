@@ -15,6 +15,10 @@
 //      two payloads; coarse patches: 0.  Bitonic sort in place
 //   3. inclusive scan of both payloads in sorted order
 //   4. every K: a binary search for cnt(K), two prefix reads, five sizes out
+//
+// cgic_rate_curve_tiles (section I, ABI 11) runs the same steps 1-3 (curve_sort_scan: ONE body for both kernels) for T tiles of
+// mixed shapes, one workgroup per tile, its shape and offsets read from a descriptor; step 4 answers the M requested ranks of the
+// tile's shape class, and a second launch sums the tiles of each image per setting and stream.
 #include "cgic_common.h"
 
 #include <math.h>
@@ -93,31 +97,49 @@ __device__ __forceinline__ int32_t stream_bytes(unsigned int count, unsigned int
     return bad ? (int32_t)(CGIC_ERR_INVALID - 10) : count == 0 ? 0 : (int32_t)(bits / 8u + 2u);
 }
 
-__global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs a)
+// one image / tile as steps 1-3 see it
+struct CurveTile {
+    const int64_t *ind_c, *ind_m, *ind_f;            // [n16], [4 n16], [16 n16]
+    const float *e16, *e8;
+    int h16, w16;
+    int k_c;
+};
+
+// what steps 1-3 leave beside the sorted words: kv[i] = key << 32 | medium bits of sorted[0 .. i], sf[i] = fine bits of sorted[0 .. i]
+struct CurveSorted {
+    const unsigned long long *kv;
+    const unsigned int *sf;
+    int n8;
+    unsigned int ncoarse, thr, total_m, total_f, first_bad_m, last_bad_f;
+    int32_t size_c, size_mc, size_mm;
+};
+
+// steps 1-3 for one image / tile by the whole workgroup, in the dynamic LDS `dyn` (12 bytes per 8x8 patch, then the staged code
+// lengths).  Every argument is workgroup-uniform.  Ends behind a barrier: kv / sf may be read by any thread
+__device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const int32_t *glen, int nsym, int staged, int streams,
+                                                       unsigned char *dyn)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ unsigned long long scan_tmp[kCurveThreads / kWave + 1];
     __shared__ unsigned int sh_thr, sh_ncoarse, sh_cbits, sh_cbad, sh_first_bad_m, sh_last_bad_f;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int64_t b = blockIdx.x;
-    const int n16 = a.h16 * a.w16, n8 = 4 * n16, w8 = 2 * a.w16, w4 = 4 * a.w16;
+    const int n16 = c.h16 * c.w16, n8 = 4 * n16, w8 = 2 * c.w16, w4 = 4 * c.w16;
     unsigned long long *kv = reinterpret_cast<unsigned long long *>(dyn);        // [n8] key << 32 | payload
     unsigned int *sf = reinterpret_cast<unsigned int *>(dyn + (size_t)n8 * 8);  // [n8] fine prefix
     int32_t *slen = reinterpret_cast<int32_t *>(dyn + (size_t)n8 * 12);
-    const float *e16 = a.e16 + b * n16, *e8 = a.e8 + b * n8;
-    const int64_t *ind_c = a.ind_c + b * n16, *ind_m = a.ind_m + b * n8, *ind_f = a.ind_f + b * 4 * (int64_t)n8;
+    const float *e16 = c.e16, *e8 = c.e8;
+    const int64_t *ind_c = c.ind_c, *ind_m = c.ind_m, *ind_f = c.ind_f;
 
-    if (a.staged)
-        for (int i = tid; i < a.nsym; i += nt) slen[i] = a.len[i];
-    const int32_t *len = a.staged ? slen : a.len;
+    if (staged)
+        for (int i = tid; i < nsym; i += nt) slen[i] = glen[i];
+    const int32_t *len = staged ? slen : glen;
     if (tid == 0) { sh_thr = 0; sh_ncoarse = 0; sh_cbits = 0; sh_cbad = 0; sh_first_bad_m = 0xFFFFFFFFu; sh_last_bad_f = 0; }
 
     // ---- 1. the coarse threshold s16[k_c - 1] (k_c == 0: nothing is below the smallest, RouterTriple.py:24-25) and the coarse stream
-    if (a.k_c > 0) {
+    if (c.k_c > 0) {
         for (int i = tid; i < n16; i += nt) kv[i] = entropy_key(e16[i]);
         __syncthreads();
         lds_sort_u64(kv, n16, tid, nt);
-        if (tid == 0) sh_thr = (unsigned int)kv[a.k_c - 1];
+        if (tid == 0) sh_thr = (unsigned int)kv[c.k_c - 1];
     }
     __syncthreads();
     const unsigned int thr = sh_thr;                 // (0 without a coarse rank: no key is below it)
@@ -126,7 +148,7 @@ __global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs
         for (int i = tid; i < n16; i += nt) {
             if (entropy_key(e16[i]) < thr) {
                 const int64_t s = ind_c[i];
-                if (s < 0 || s >= a.nsym) bad = 1;
+                if (s < 0 || s >= nsym) bad = 1;
                 else bits += (unsigned int)len[s];
                 ++cnt;
             }
@@ -142,16 +164,16 @@ __global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs
     for (int p = tid; p < n8; p += nt) {
         const int y = p / w8, x = p - y * w8;
         unsigned long long word = 0;                 // a coarse patch: the zero of e8 * (1 - gate), no symbols
-        if (!(entropy_key(e16[(y >> 1) * a.w16 + (x >> 1)]) < thr)) {
+        if (!(entropy_key(e16[(y >> 1) * c.w16 + (x >> 1)]) < thr)) {
             unsigned int pm = 0, pf = 0, flags = 0;
             const int64_t sm = ind_m[p];
-            if (sm < 0 || sm >= a.nsym) flags |= 0x80000000u;
+            if (sm < 0 || sm >= nsym) flags |= 0x80000000u;
             else pm = (unsigned int)len[sm];
             const int64_t *f = ind_f + (int64_t)(2 * y) * w4 + 2 * x;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int64_t s = f[(q >> 1) * w4 + (q & 1)];
-                if (s < 0 || s >= a.nsym) flags |= 0x40000000u;
+                if (s < 0 || s >= nsym) flags |= 0x40000000u;
                 else pf += (unsigned int)len[s];
             }
             word = (unsigned long long)entropy_key(e8[p]) << 32 | flags | pm << 16 | pf;
@@ -183,41 +205,138 @@ __global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs
     }
     __syncthreads();
 
-    // ---- 4. every rank
-    const unsigned int ncoarse = sh_ncoarse, zeros = 4u * ncoarse;
-    const unsigned int total_f = (unsigned int)(total >> 32);
-    const unsigned int first_bad_m = sh_first_bad_m, last_bad_f = sh_last_bad_f;
-    const int32_t size_c = (a.streams & 1) ? stream_bytes(ncoarse, sh_cbits, sh_cbad != 0) : 0;
-    const int32_t size_mc = (a.streams >> 3 & 1) ? (int32_t)(n16 / 8 + 2) : 0;      // BinaryCoding: one bit per element (mask_coding.py)
-    const int32_t size_mm = (a.streams >> 4 & 1) ? (int32_t)(n8 / 8 + 2) : 0;
+    CurveSorted r;
+    r.kv = kv; r.sf = sf; r.n8 = n8;
+    r.ncoarse = sh_ncoarse; r.thr = thr;
+    r.total_m = (unsigned int)total; r.total_f = (unsigned int)(total >> 32);
+    r.first_bad_m = sh_first_bad_m; r.last_bad_f = sh_last_bad_f;
+    r.size_c = (streams & 1) ? stream_bytes(r.ncoarse, sh_cbits, sh_cbad != 0) : 0;
+    r.size_mc = (streams >> 3 & 1) ? (int32_t)(n16 / 8 + 2) : 0;       // BinaryCoding: one bit per element (mask_coding.py)
+    r.size_mm = (streams >> 4 & 1) ? (int32_t)(n8 / 8 + 2) : 0;
+    return r;
+}
+
+// ---- 4. one rank K in 0 .. n8: five sizes to o[0 .. 5)
+__device__ __forceinline__ void curve_rank_sizes(const CurveSorted &r, int K, int streams, int32_t *o)
+{
+    const unsigned long long *kv = r.kv;
+    const unsigned int zeros = 4u * r.ncoarse;
+    const unsigned int t = (unsigned int)(kv[K ? K - 1 : 0] >> 32);              // sorted[K - 1] (K == 0: index 0, RouterTriple.py:31)
+    int lo = 0, hi = K ? K - 1 : 0;                                              // lower bound of t: the first element not below it
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned int)(kv[mid] >> 32) < t) lo = mid + 1;
+        else hi = mid;
+    }
+    const unsigned int cnt = (unsigned int)lo;                                   // elements with e8 < t; with t > 0 all coarse zeros are among them
+    const unsigned int n_med = t ? cnt - zeros : 0u;
+    const unsigned int n_fine = (unsigned int)r.n8 - zeros - n_med;
+    const unsigned int bits_m = cnt ? (unsigned int)kv[cnt - 1] : 0u;
+    const unsigned int bits_f = r.total_f - (cnt ? r.sf[cnt - 1] : 0u);
+    o[0] = r.size_c;
+    o[1] = (streams >> 1 & 1) ? stream_bytes(n_med, bits_m, r.first_bad_m < cnt) : 0;
+    o[2] = (streams >> 2 & 1) ? stream_bytes(4u * n_fine, bits_f, r.last_bad_f > cnt) : 0;
+    o[3] = r.size_mc;
+    o[4] = r.size_mm;
+}
+
+__device__ __forceinline__ void curve_summary(const CurveSorted &r, int32_t *s)
+{
+    s[0] = (int32_t)r.ncoarse;
+    s[1] = (int32_t)r.thr;
+    s[2] = (int32_t)r.total_m;
+    s[3] = (int32_t)r.total_f;
+}
+
+__global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t b = blockIdx.x;
+    const int n16 = a.h16 * a.w16, n8 = 4 * n16;
+    CurveTile c;
+    c.ind_c = a.ind_c + b * n16; c.ind_m = a.ind_m + b * n8; c.ind_f = a.ind_f + b * 4 * (int64_t)n8;
+    c.e16 = a.e16 + b * n16; c.e8 = a.e8 + b * n8;
+    c.h16 = a.h16; c.w16 = a.w16; c.k_c = a.k_c;
+    const CurveSorted r = curve_sort_scan(c, a.len, a.nsym, a.staged, a.streams, dyn);
     int32_t *out = a.nbytes + b * (int64_t)(n8 + 1) * CGIC_NUM_STREAMS;
-    for (int K = tid; K <= n8; K += nt) {
-        const unsigned int t = (unsigned int)(kv[K ? K - 1 : 0] >> 32);              // sorted[K - 1] (K == 0: index 0, RouterTriple.py:31)
-        int lo = 0, hi = K ? K - 1 : 0;                                              // lower bound of t: the first element not below it
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((unsigned int)(kv[mid] >> 32) < t) lo = mid + 1;
-            else hi = mid;
+    for (int K = tid; K <= n8; K += nt) curve_rank_sizes(r, K, a.streams, out + (int64_t)K * CGIC_NUM_STREAMS);
+    if (tid == 0) curve_summary(r, a.summary + b * kCurveSummary);
+}
+
+// ---- cgic_rate_curve_tiles: T tiles of mixed shapes, the M requested ranks of each tile's shape class ------------------------
+constexpr int kTilesMaxShapes = 16;
+constexpr int kTilesMaxSettings = 65536;
+constexpr int kTilesMaxTiles = 65535;
+constexpr int kFoldThreads = 256;
+constexpr int32_t kTilesBadRank = CGIC_ERR_INVALID - 11;          // a rank outside 0 .. n8 of the tile (negative: folds to -1)
+
+struct RateTilesArgs {
+    const int32_t *len;
+    int nsym;
+    int staged;                                      // the code lengths fit the LDS behind the words of the LARGEST tile
+    const int64_t *ind_c, *ind_m, *ind_f;            // concatenated buffers; a tile's part starts at its descriptor's offsets
+    const float *e16, *e8;
+    const cgic_rate_tile *tiles;                     // device [T]
+    const int32_t *ranks;                            // device [S, M]
+    int M;
+    int streams;
+    int32_t *tile_nbytes;                            // [T, M, 5]
+    int32_t *summary;                                // [T, 4], as rate_curve_kernel's
+};
+
+// One workgroup per tile.  The descriptor is read at a workgroup-uniform address before the kernel stores anything: scalar loads,
+// and everything derived from it (shape, offsets, k_c) lives in scalar registers, like a launch group's argument block
+__global__ __launch_bounds__(kCurveThreads) void rate_curve_tiles_kernel(RateTilesArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t t = blockIdx.x;
+    const cgic_rate_tile d = a.tiles[t];
+    CurveTile c;
+    c.ind_c = a.ind_c + d.off_c; c.ind_m = a.ind_m + d.off_m; c.ind_f = a.ind_f + d.off_f;
+    c.e16 = a.e16 + d.off_e16; c.e8 = a.e8 + d.off_e8;
+    c.h16 = d.h16; c.w16 = d.w16; c.k_c = d.k_c;
+    const CurveSorted r = curve_sort_scan(c, a.len, a.nsym, a.staged, a.streams, dyn);
+    const int32_t *ranks = a.ranks + (int64_t)d.shape * a.M;
+    int32_t *out = a.tile_nbytes + t * (int64_t)a.M * CGIC_NUM_STREAMS;
+    for (int j = tid; j < a.M; j += nt) {
+        const int K = ranks[j];
+        int32_t *o = out + (int64_t)j * CGIC_NUM_STREAMS;
+        if (K < 0 || K > r.n8) {
+#pragma unroll
+            for (int s = 0; s < CGIC_NUM_STREAMS; ++s) o[s] = kTilesBadRank;
+        } else {
+            curve_rank_sizes(r, K, a.streams, o);
         }
-        const unsigned int cnt = (unsigned int)lo;                                   // elements with e8 < t; with t > 0 all coarse zeros are among them
-        const unsigned int n_med = t ? cnt - zeros : 0u;
-        const unsigned int n_fine = (unsigned int)n8 - zeros - n_med;
-        const unsigned int bits_m = cnt ? (unsigned int)kv[cnt - 1] : 0u;
-        const unsigned int bits_f = total_f - (cnt ? sf[cnt - 1] : 0u);
-        int32_t *o = out + (int64_t)K * CGIC_NUM_STREAMS;
-        o[0] = size_c;
-        o[1] = (a.streams >> 1 & 1) ? stream_bytes(n_med, bits_m, first_bad_m < cnt) : 0;
-        o[2] = (a.streams >> 2 & 1) ? stream_bytes(4u * n_fine, bits_f, last_bad_f > cnt) : 0;
-        o[3] = size_mc;
-        o[4] = size_mm;
     }
-    if (tid == 0) {
-        int32_t *s = a.summary + b * kCurveSummary;
-        s[0] = (int32_t)ncoarse;
-        s[1] = (int32_t)thr;
-        s[2] = (int32_t)(unsigned int)total;
-        s[3] = (int32_t)total_f;
+    if (tid == 0) curve_summary(r, a.summary + t * kCurveSummary);
+}
+
+// image_nbytes[n, j, :] = the sum over the tiles of image n (blockIdx.y) of tile_nbytes[t, j, :], in descriptor order, as int64; a
+// negative tile entry (a symbol outside the table, a rank outside the tile) makes all five -1.  One thread per setting; the walk
+// over the descriptors is workgroup-uniform (scalar loads and a scalar branch per tile)
+__global__ __launch_bounds__(kFoldThreads) void rate_fold_tiles_kernel(const cgic_rate_tile *tiles, int T, int M,
+                                                                       const int32_t *tile_nbytes, int64_t *image_nbytes)
+{
+    const int n = blockIdx.y;
+    const int j = blockIdx.x * kFoldThreads + threadIdx.x;
+    if (j >= M) return;
+    int64_t acc[CGIC_NUM_STREAMS] = {0, 0, 0, 0, 0};
+    bool bad = false;
+    for (int t = 0; t < T; ++t) {
+        if (tiles[t].image != n) continue;
+        const int32_t *p = tile_nbytes + ((int64_t)t * M + j) * CGIC_NUM_STREAMS;
+#pragma unroll
+        for (int s = 0; s < CGIC_NUM_STREAMS; ++s) {
+            const int32_t v = p[s];
+            bad |= v < 0;
+            acc[s] += v;
+        }
     }
+    int64_t *o = image_nbytes + ((int64_t)n * M + j) * CGIC_NUM_STREAMS;
+#pragma unroll
+    for (int s = 0; s < CGIC_NUM_STREAMS; ++s) o[s] = bad ? -1 : acc[s];
 }
 
 }  // namespace cgic
@@ -294,4 +413,96 @@ extern "C" int cgic_rate_curve(const cgic_table *t, const int64_t *ind_c, const 
     while (threads > 256 && threads >= n8) threads >>= 1;
     hipLaunchKernelGGL(rate_curve_kernel, dim3((unsigned)B), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
     return launch_check("rate_curve_kernel");
+}
+
+static size_t tiles_summary_bytes(int64_t T)
+{
+    return (((size_t)T * kCurveSummary * sizeof(int32_t)) + 255) & ~(size_t)255;
+}
+
+extern "C" size_t cgic_rate_curve_tiles_workspace_bytes(int64_t T, int64_t M, int tile_nbytes_given)
+{
+    if (T <= 0 || M <= 0 || T > kTilesMaxTiles || M > kTilesMaxSettings) return 0;
+    return tiles_summary_bytes(T) + (tile_nbytes_given ? 0 : (size_t)T * (size_t)M * CGIC_NUM_STREAMS * sizeof(int32_t));
+}
+
+extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
+                                     const float *e16, const float *e8, const int64_t *count, const cgic_rate_tile *tiles,
+                                     const cgic_rate_tile *tiles_dev, int64_t T, int64_t N, double coarse_ratio,
+                                     const int32_t *ranks_dev, int64_t S, int64_t M, int64_t *image_nbytes, int32_t *tile_nbytes,
+                                     void *workspace, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_rate_curve_tiles");
+    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && count && tiles && tiles_dev && ranks_dev && image_nbytes, CGIC_ERR_INVALID,
+                 "rate_curve_tiles: NULL argument");
+    CGIC_REQUIRE(T >= 0 && N >= 1 && S >= 1 && M >= 1, CGIC_ERR_INVALID, "rate_curve_tiles: bad counts (T=%lld, N=%lld, S=%lld, M=%lld)",
+                 (long long)T, (long long)N, (long long)S, (long long)M);
+    CGIC_REQUIRE(coarse_ratio >= 0.0 && coarse_ratio <= 1.0, CGIC_ERR_INVALID, "rate_curve_tiles: coarse ratio %g outside [0, 1]", coarse_ratio);
+    CGIC_REQUIRE(T <= kTilesMaxTiles && N <= kTilesMaxTiles, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tiles of %lld images exceed the grid limit (%d)",
+                 (long long)T, (long long)N, kTilesMaxTiles);
+    CGIC_REQUIRE(S <= kTilesMaxShapes, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tile shapes (at most %d)", (long long)S, kTilesMaxShapes);
+    CGIC_REQUIRE(M <= kTilesMaxSettings, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld settings (at most %d)", (long long)M, kTilesMaxSettings);
+    for (int i = 0; i < 5; ++i) CGIC_REQUIRE(count[i] >= 0, CGIC_ERR_INVALID, "rate_curve_tiles: negative element count");
+    const int nsym = cgic_table_num_symbols(t);
+    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: table of %d symbols", nsym);
+    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: codes of up to %d bits (at most %d)",
+                 cgic_table_max_len(t), kCurveMaxLen);
+    // every descriptor: its shape fits one workgroup, its class has ONE shape, its coarse rank is the one cgic_rate_curve takes,
+    // and its five parts lie inside the buffers
+    int64_t class_h[kTilesMaxShapes], class_w[kTilesMaxShapes];
+    for (int s = 0; s < kTilesMaxShapes; ++s) class_h[s] = class_w[s] = 0;
+    int64_t n8_max = 0;
+    for (int64_t i = 0; i < T; ++i) {
+        const cgic_rate_tile &d = tiles[i];
+        const int64_t h16 = d.h16, w16 = d.w16;
+        CGIC_REQUIRE(h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: bad shape", (long long)i);
+        CGIC_REQUIRE(4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
+                     "rate_curve_tiles: tile %lld of %lld 8x8 patches does not fit one workgroup's LDS (at most %lld: 768x1024 pixels)",
+                     (long long)i, (long long)(4 * h16 * w16), (long long)kCurveMaxN8);
+        const int64_t n16 = h16 * w16, n8 = 4 * n16;
+        CGIC_REQUIRE(d.shape >= 0 && d.shape < S && d.image >= 0 && d.image < N && d.reserved == 0, CGIC_ERR_INVALID,
+                     "rate_curve_tiles: tile %lld: shape class %d of %lld, image %d of %lld", (long long)i, d.shape, (long long)S, d.image, (long long)N);
+        if (class_h[d.shape] == 0) { class_h[d.shape] = h16; class_w[d.shape] = w16; }
+        CGIC_REQUIRE(class_h[d.shape] == h16 && class_w[d.shape] == w16, CGIC_ERR_INVALID,
+                     "rate_curve_tiles: tile %lld: shape class %d holds tiles of two shapes", (long long)i, d.shape);
+        const int64_t k_c = coarse_ratio > 0.0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0;
+        CGIC_REQUIRE(d.k_c == k_c && k_c >= 0 && k_c <= n16, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: k_coarse=%d, the ratio gives %lld of %lld",
+                     (long long)i, d.k_c, (long long)k_c, (long long)n16);
+        const int64_t off[5] = {d.off_c, d.off_m, d.off_f, d.off_e16, d.off_e8};
+        const int64_t len[5] = {n16, n8, 4 * n8, n16, n8};
+        for (int k = 0; k < 5; ++k)
+            CGIC_REQUIRE(off[k] >= 0 && off[k] <= count[k] && len[k] <= count[k] - off[k], CGIC_ERR_INVALID,
+                         "rate_curve_tiles: tile %lld: part %d at offset %lld + %lld elements is outside its buffer of %lld", (long long)i, k,
+                         (long long)off[k], (long long)len[k], (long long)count[k]);
+        if (n8 > n8_max) n8_max = n8;
+    }
+    const size_t need = cgic_rate_curve_tiles_workspace_bytes(T > 0 ? T : 1, M, tile_nbytes != nullptr);
+    CGIC_REQUIRE(workspace, CGIC_ERR_INVALID, "rate_curve_tiles: workspace of %zu bytes required (cgic_rate_curve_tiles_workspace_bytes)", need);
+    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "rate_curve_tiles: the workspace must be 16-byte aligned");
+    TableDev tab;
+    int rc = table_device_view(t, &tab);
+    if (rc) return rc;
+
+    RateTilesArgs a;
+    a.len = tab.len; a.nsym = nsym;
+    const size_t words = (size_t)n8_max * 12;
+    a.staged = words + (size_t)nsym * sizeof(int32_t) <= kCurveLdsBudget;
+    a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
+    a.tiles = tiles_dev; a.ranks = ranks_dev; a.M = (int)M;
+    a.streams = cgic_mode_streams(coarse_ratio > 0.0 ? 0 : 1);
+    a.summary = reinterpret_cast<int32_t *>(workspace);
+    a.tile_nbytes = tile_nbytes ? tile_nbytes
+                                : reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + tiles_summary_bytes(T > 0 ? T : 1));
+    if (T > 0) {
+        const size_t lds = words + (a.staged ? (size_t)nsym * sizeof(int32_t) : 0);
+        if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_curve_tiles_kernel, lds); if (rc) return rc; }
+        int threads = kCurveThreads;                 // (sized by the largest tile; the results do not depend on it)
+        while (threads > 256 && threads >= n8_max) threads >>= 1;
+        hipLaunchKernelGGL(rate_curve_tiles_kernel, dim3((unsigned)T), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
+        rc = launch_check("rate_curve_tiles_kernel");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(rate_fold_tiles_kernel, dim3((unsigned)((M + kFoldThreads - 1) / kFoldThreads), (unsigned)N), dim3(kFoldThreads), 0,
+                       (hipStream_t)stream, tiles_dev, (int)T, (int)M, (const int32_t *)a.tile_nbytes, image_nbytes);
+    return launch_check("rate_fold_tiles_kernel");
 }

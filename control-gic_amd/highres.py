@@ -280,6 +280,12 @@ def compress_tiled_batch(x, encode, codec, tile=TILE, concurrent=False, chain=Fa
         raise ValueError("compress_tiled_batch takes [N,3,H,W] or uint8 [N,H,W,3]")
     N = x.shape[0]
     hw, pad, tiles, groups = _compress_groups(x, encode, codec, tile, concurrent, chain, fuse_maps, frames_fp32)
+    return assemble_tiled(hw, pad, tiles, groups, N)
+
+
+def assemble_tiled(hw, pad, tiles, groups, N):
+    """the N TiledImages of shape groups that hold the tiles of N images of one size image-major ([N * T, ...] per group:
+    (tile indices, CompressedBatch, (ind, masks, mode))), as views of the shared per-group buffers"""
     out = []
     for n in range(N):
         mine = []
@@ -293,6 +299,29 @@ def compress_tiled_batch(x, encode, codec, tile=TILE, concurrent=False, chain=Fa
         t._whole = (groups, n, N)                 # decompress_tiled_batch of the whole list reads the shared buffers in place
         out.append(t)
     return out
+
+
+def cut_groups(x, tile=TILE):
+    """pad and cut N images of one size [N,3,H,W] fp32 as the tiling driver does -> (pad, tiles, order, batches): the centred pad,
+    the row-major tile grid in padded coordinates, the shape groups [((th, tw), tile indices)] largest first, and per group the
+    tile batch [N * T, 3, th, tw], image-major (the layout compress_tiled_batch compresses)"""
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise ValueError(f"cut_groups takes fp32 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
+    N, H, W = x.shape[0], x.shape[2], x.shape[3]
+    pad, _ = compute_padding(H, W)
+    left, right, top, bottom = pad
+    tiles = tile_grid(H + top + bottom, W + left + right, tile)
+    by_shape = {}
+    for i, (_, _, th, tw) in enumerate(tiles):
+        by_shape.setdefault((th, tw), []).append(i)
+    order = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+    if len(tiles) <= 96:
+        cut = _cut_all(x.contiguous(), False, N, H, W, top, left, tiles, order)
+    else:
+        xp = torch.nn.functional.pad(x, pad)
+        cut = [torch.stack([xp[:, :, tiles[i][0]:tiles[i][0] + th, tiles[i][1]:tiles[i][1] + tw] for i in idxs], dim=1)
+               for (th, tw), idxs in order]
+    return pad, tiles, order, [b.reshape(-1, 3, th, tw) for b, ((th, tw), _) in zip(cut, order)]
 
 
 class TiledCall:

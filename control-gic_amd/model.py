@@ -201,6 +201,7 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
     model.compress = types.MethodType(compress, model)
     model.compress_batch = types.MethodType(compress_batch, model)
     model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)
+    model.compress_tiled_to_bpp = types.MethodType(_rate.compress_tiled_to_bpp, model)
     model._cgic_codec = None
     model._cgic_codec_key = None
     return model

@@ -9,6 +9,11 @@ select (include/cgic_hip.h, section I).  `compress_to_bpp` then c
 `rate_curve` answers it for EVERY setting of the medium ratio at one coarse ratio: the medium decision of the router is one
 integer, the rank K of its threshold among the 8x8-patch entropies, and one sort of the image's patches gives the sizes of all
 n8 + 1 ranks (cgic_rate_curve).  `compress_to_bpp(..., search="curve")` picks among all of them.
+
+`rate_curve_tiled` answers it for tiled high-resolution images (highres.py): ONE ratio pair for all tiles of an image, every
+tile routed on its own thresholds, so an image's bytes at (c, m) are the sum of its tiles' curves at the rank m gives a tile of
+that SHAPE (`tiled_settings`: the medium axis of a set of shapes); one call for all tiles of all shapes
+(cgic_rate_curve_tiles).  `compress_tiled_to_bpp` compresses N same-size images at the setting it picks.
 """
 import ctypes
 import functools
@@ -174,6 +179,79 @@ def reachable_ranks(n16, coarse_ratio):
     return tuple(out)
 
 
+def _curve_ranks_vec(coarse_ratio, mediums, n16):
+    """cgic_router_ranks + cgic_router_mode for a float64 tensor of medium ratios at once, in the curve's mode -> (ok bool [M],
+    k_medium int64 [M]): ok where the pair is in the curve's mode (medium != 0 and 1 - coarse - medium != 0) with 0 <= k <= n8.
+    The same float64 operations in the same order as the library's (one product and one sum, round-half-even)"""
+    c, n16 = float(coarse_ratio), int(n16)
+    n8 = 4 * n16
+    m = torch.as_tensor(mediums, dtype=torch.float64)
+    fine = (1.0 - c) - m
+    k = torch.round(float(4 * n16) * c + float(n8) * m) if c > 0.0 else torch.round(float(n8) * m)
+    ok = (m != 0) & (fine != 0) & (k >= 0) & (k <= n8)
+    return ok, k.to(torch.int64)
+
+
+@functools.lru_cache(maxsize=64)
+def reachable_ranks_vec(n16, coarse_ratio):
+    """reachable_ranks as tensors, every rank searched at once -> (K int64 [R], medium float64 [R]): ratio_for_rank's search (start
+    at (K - 4 n16 c) / n8, step one float64 at a time towards the rank) on all n8 + 1 ranks in lockstep.  A 768x768 tile has 9217
+    ranks: the loop's two foreign calls per step become a handful of tensor operations"""
+    n16, c = int(n16), float(coarse_ratio)
+    n8 = 4 * n16
+    tiny = math.nextafter(0.0, 1.0)
+    K = torch.arange(n8 + 1, dtype=torch.int64)
+    m = (K.to(torch.float64) - 4 * n16 * c) / n8
+    m = torch.where(m <= 0.0, torch.full_like(m, tiny), m)
+    found = torch.zeros(n8 + 1, dtype=torch.bool)
+    alive = torch.ones(n8 + 1, dtype=torch.bool)
+    up, down = torch.full_like(m, 2.0), torch.zeros_like(m)
+    for _ in range(64):
+        ok, km = _curve_ranks_vec(c, m, n16)
+        found |= alive & ok & (km == K)
+        alive &= ~found
+        if not bool(alive.any()):
+            break
+        step = torch.nextafter(m, torch.where(ok & (km < K), up, down))
+        m = torch.where(alive, step, m)
+        alive &= (m >= tiny) & (m <= 1.0)
+    return K[found], m[found]
+
+
+def tiled_settings(shapes_n16, coarse_ratio):
+    """the medium axis of a tiled image: shapes_n16 = the number of 16x16 patches of each distinct tile shape ->
+    (mediums float64 [M], ranks int64 [S, M]).  mediums: ascending, the union over the shapes of the ratios that reach each of a
+    shape's medium ranks (reachable_ranks), all in the curve's mode (0, or 1 at coarse ratio 0) with a positive fine ratio;
+    ranks[s, j]: the rank cgic_router_ranks gives a tile of shape s at (coarse_ratio, mediums[j]).  Every shape's row takes every
+    rank that shape can reach: no setting of the image is left out"""
+    shapes = tuple(int(n) for n in shapes_n16)
+    if not shapes or min(shapes) <= 0:
+        raise ValueError(f"tiled_settings: shapes_n16={shapes_n16!r}")
+    return _tiled_settings(shapes, float(coarse_ratio))
+
+
+@functools.lru_cache(maxsize=16)
+def _tiled_settings(shapes, c):
+    per = [reachable_ranks_vec(n, c) for n in shapes]
+    m = torch.unique(torch.cat([p[1] for p in per]))                     # sorted, distinct
+    # a ratio found a step above 1 - coarse (the start of the top rank's search can round up) has a negative fine ratio: the
+    # float64 just below 1 - coarse reaches the same rank
+    top = (1.0 - c) - m <= 0
+    if bool(top.any()):
+        m = torch.unique(torch.where(top, torch.full_like(m, math.nextafter(1.0 - c, 0.0)), m))
+    rows, keep = [], torch.ones_like(m, dtype=torch.bool)
+    for n in shapes:
+        ok, k = _curve_ranks_vec(c, m, n)
+        keep &= ok
+        rows.append(k)
+    keep &= (m > 0) & ((1.0 - c) - m > 0)
+    m, ranks = m[keep], torch.stack(rows)[:, keep]
+    for n, row, (K, _) in zip(shapes, ranks, per):
+        if not torch.equal(torch.unique(row), K):
+            raise RuntimeError(f"tiled_settings: the axis at coarse ratio {c} misses a reachable rank of a shape of {n} patches")
+    return m, ranks
+
+
 class RateCurve:
     """rate_curve's result: per image and medium rank K = 0 .. n8 the sizes of the five .bin streams at one coarse ratio.
     nbytes int32 [B,n8+1,5] (0 = not written), bytes int64 [B,n8+1], bpp float64 [B,n8+1], batch_bpp float64 [n8+1];
@@ -255,6 +333,227 @@ def gather_grain_indices(ind_c, ind_m, ind_f, masks):
     return out
 
 
+class TiledRateCurve:
+    """rate_curve_tiled's result: per image and setting j of the medium axis the sizes of the five .bin streams, summed over the
+    image's tiles, at one coarse ratio.  mediums float64 [M] (ascending), ranks int64 [S, M] (the medium rank of shape class s at
+    setting j), shapes [(h16, w16)] per class; nbytes int64 [N, M, 5], bytes int64 [N, M], bpp float64 [N, M] (bits over the
+    pixels of the UNPADDED image, inference_high_resolution.py:250,256), batch_bpp float64 [M]; tile_nbytes int32 [T, M, 5] on the
+    device, tiles in the order of the groups handed in; tile_shape / tile_image: class and image of each; candidates: the
+    (coarse, medium) pair of each setting, modes: their mode.  ends (set by rate_curve_tiled): the two ends of the axis the
+    curve's mode does not hold, as an object with candidates, modes, nbytes [2, N, 5], bytes, bpp, batch_bpp"""
+
+    def __init__(self, image_nbytes, tile_nbytes, coarse_ratio, mediums, ranks, shapes, num_pixels, tile_shape=None, tile_image=None):
+        self.coarse_ratio = float(coarse_ratio)
+        self.num_pixels = int(num_pixels)
+        self.mediums = torch.as_tensor(mediums, dtype=torch.float64)
+        self.ranks = torch.as_tensor(ranks, dtype=torch.int64)
+        self.shapes = list(shapes)
+        self.tile_nbytes, self.tile_shape, self.tile_image = tile_nbytes, tile_shape, tile_image
+        self.nbytes = image_nbytes.detach().cpu()
+        if self.nbytes.numel() and int(self.nbytes.min()) < 0:
+            raise KeyError("rate_curve_tiled: an index is not in the code table")
+        self.bytes = self.nbytes.sum(dim=2)
+        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
+        N = self.bytes.shape[0]
+        self.batch_bpp = self.bytes.sum(dim=0).to(torch.float64) * 8 / (self.num_pixels * max(N, 1))
+        self.candidates = [(self.coarse_ratio, m) for m in self.mediums.tolist()]
+        self.modes = [0 if self.coarse_ratio > 0.0 else 1] * len(self.candidates)
+        self.ends = None
+
+
+class _FoldedEnds:
+    """the ends of a tiled image's medium axis: per-group rate tables folded per image (fields as RateTable's, nbytes [C, N, 5])"""
+
+    def __init__(self, nbytes, candidates, num_pixels):
+        self.nbytes, self.candidates, self.num_pixels = nbytes, list(candidates), int(num_pixels)
+        self.modes = [int(_lib.lib().cgic_router_mode(c, m)) for c, m in self.candidates]
+        self.bytes = nbytes.sum(dim=2)
+        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
+        self.batch_bpp = self.bytes.sum(dim=1).to(torch.float64) * 8 / (self.num_pixels * max(nbytes.shape[1], 1))
+
+
+def _tile_groups(tiles):
+    out = []
+    for g in tiles:
+        if isinstance(g, dict):
+            g = (g["ind_c"], g["ind_m"], g["ind_f"], g["e16"], g["e8"], g["images"])
+        ind_c, ind_m, ind_f, e16, e8, images = g
+        _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
+        e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
+        B, h16, w16 = e16c.shape
+        if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
+            raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
+        inds = []
+        for t, n in zip((ind_c, ind_m, ind_f), (B * h16 * w16, 4 * B * h16 * w16, 16 * B * h16 * w16)):
+            if t.dtype != torch.int64 or t.numel() != n:
+                raise ValueError("grain indices must be int64 on the three grids of the group's maps")
+            inds.append(t.contiguous())
+        images = [int(i) for i in images]
+        if len(images) != B or (images and min(images) < 0):
+            raise ValueError(f"a group of {B} tiles names the image of {len(images)}")
+        out.append((inds, e16c, e8c, images, (h16, w16)))
+    return out
+
+
+def rate_curve_tiled(codec, tiles, coarse_ratio, image_hw=None, settings=None, ends=True):
+    """exact sizes of the streams of N tiled images for EVERY setting of the medium ratio at `coarse_ratio`: ONE ratio pair for
+    all tiles, every tile routed on its own thresholds on the maps as given (the reference's tiling driver,
+    inference_high_resolution.py:236-251; maps of entropy_maps(tiles, reference_order=True) make that its routing from the pixels).
+    tiles: one entry per shape group, (ind_c, ind_m, ind_f, e16, e8, images) -- or a dict with those keys --: the group's
+    grain_indices and maps ([B_g, ...], as rate_curve takes them) and the image index of each of its tiles.  image_hw: the
+    (H, W) of the unpadded images for the bpp (default: the pixels of an image's tiles); settings: tiled_settings(...) of the
+    groups' shapes in their order, when the caller has it already; ends=False skips the two rate tables per group of the axis' ends.
+    One cgic_rate_curve_tiles call for all tiles of all groups.  -> TiledRateCurve"""
+    groups = _tile_groups(tiles)
+    if not groups:
+        raise ValueError("rate_curve_tiled: no tile group")
+    c = float(coarse_ratio)
+    dev = groups[0][1].device
+    shapes = []
+    for g in groups:
+        if g[4] not in shapes:
+            shapes.append(g[4])
+    mediums, ranks = settings if settings is not None else tiled_settings([h * w for h, w in shapes], c)
+    mediums, ranks = torch.as_tensor(mediums, dtype=torch.float64), torch.as_tensor(ranks, dtype=torch.int64)
+    S, M = len(shapes), int(mediums.numel())
+    if tuple(ranks.shape) != (S, M) or M < 1:
+        raise ValueError(f"rate_curve_tiled: ranks {tuple(ranks.shape)} for {S} shapes and {M} settings")
+    for (h, w), row in zip(shapes, ranks):
+        if int(row.min()) < 0 or int(row.max()) > 4 * h * w:
+            raise ValueError(f"rate_curve_tiled: a rank outside 0 .. {4 * h * w} for tiles of {16 * h}x{16 * w}")
+    N = max(max(g[3]) for g in groups if g[3]) + 1
+    T = sum(len(g[3]) for g in groups)
+    desc = (_lib.RateTile * max(T, 1))()
+    off = [0, 0, 0, 0, 0]
+    tile_shape, tile_image, pixels = [], [], [0] * N
+    t = 0
+    for inds, e16c, e8c, images, (h16, w16) in groups:
+        n16 = h16 * w16
+        k_c = round(n16 * c) if c > 0.0 else 0                          # (cgic_rate_curve's expression: round-half-even of the float64 product)
+        s = shapes.index((h16, w16))
+        for k, n in enumerate(images):
+            desc[t] = _lib.RateTile(h16, w16, k_c, s, n, 0, off[0] + k * n16, off[1] + 4 * k * n16, off[2] + 16 * k * n16,
+                                    off[3] + k * n16, off[4] + 4 * k * n16)
+            tile_shape.append(s)
+            tile_image.append(n)
+            pixels[n] += 256 * n16
+            t += 1
+        B = len(images)
+        for i, per in enumerate((n16, 4 * n16, 16 * n16, n16, 4 * n16)):
+            off[i] += B * per
+    if image_hw is None:
+        if len(set(pixels)) != 1:
+            raise ValueError("rate_curve_tiled: the images differ in size; give image_hw")
+        num_pixels = pixels[0]
+    else:
+        num_pixels = int(image_hw[0]) * int(image_hw[1])
+    cat = lambda i: groups[0][i].reshape(-1) if len(groups) == 1 else torch.cat([g[i].reshape(-1) for g in groups])
+    bufs = [groups[0][0][i].reshape(-1) if len(groups) == 1 else torch.cat([g[0][i].reshape(-1) for g in groups]) for i in range(3)]
+    bufs += [cat(1), cat(2)]
+    count = (ctypes.c_int64 * 5)(*[int(b.numel()) for b in bufs])
+    desc_dev = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8).to(dev)
+    ranks_dev = ranks.to(torch.int32).contiguous().to(dev)
+    image_nbytes = torch.empty((N, M, _lib.NUM_STREAMS), dtype=torch.int64, device=dev)
+    tile_nbytes = torch.empty((T, M, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(_lib.lib().cgic_rate_curve_tiles_workspace_bytes(max(T, 1), M, 1)), 16), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("cgic_rate_curve_tiles", codec.huffman.table.handle, *[_lib.ptr(b) for b in bufs], count, desc, _lib.ptr(desc_dev),
+                  T, N, c, _lib.ptr(ranks_dev), S, M, _lib.ptr(image_nbytes), _lib.ptr(tile_nbytes), _lib.ptr(ws),
+                  _lib.current_stream(dev))
+    curve = TiledRateCurve(image_nbytes, tile_nbytes, c, mediums, ranks, shapes, num_pixels, tile_shape, tile_image)
+    curve.n_coarse = ws[:T * 16].view(torch.int32).view(T, 4)[:, 0].to(torch.int64).cpu()
+    if ends:
+        # medium 0 and fine 0: one two-candidate rate table per shape group, folded per image on the host
+        cand = _curve_ends(c)
+        folded = torch.zeros((len(cand), N, _lib.NUM_STREAMS), dtype=torch.int64)
+        for inds, e16c, e8c, images, _ in groups:
+            nb = rate_table(codec, *inds, e16c, e8c, cand, per_image=True).nbytes.cpu().to(torch.int64)
+            folded.index_add_(1, torch.tensor(images, dtype=torch.int64), nb)
+        curve.ends = _FoldedEnds(folded, cand, num_pixels)
+    return curve
+
+
+def _pick_tiled(curve, target_bpp):
+    """over the settings of the curve and its two ends -> (index into curve.candidates + curve.ends.candidates, fits)"""
+    cand = curve.candidates + (curve.ends.candidates if curve.ends is not None else [])
+    bb = curve.batch_bpp.tolist() + (curve.ends.batch_bpp.tolist() if curve.ends is not None else [])
+    return _pick(bb, cand, float(target_bpp)), cand
+
+
+def compress_tiled_to_bpp(model, x, target_bpp, tile=None, decode=None):
+    """compress tiled high-resolution images at the ONE granularity ratio -- for all images and all tiles, the reference's
+    semantics -- whose exact bpp over the batch is the largest one <= target_bpp, among every medium ratio at the router
+    config's coarse ratio and the two ends of the axis.  x: one [1,3,H,W] image or N of one size.
+    -> (TiledImage, or a list of N; bpp (a list for N > 1): the curve's entry of the chosen setting; (coarse, medium);
+    TiledRateCurve with .fits, .chosen (the setting's index, None: an end was chosen)).
+    Pad and cut as compress_tiled; per shape group ONE model.encode (the encoder heads are taken from it by forward hooks), the
+    maps of entropy_maps(tiles, reference_order=True), grain_indices; one rate_curve_tiled over all groups; then every group
+    is routed (per tile, on the maps as given), gathered and compressed at the chosen pair.  decode: None, or
+    decode(z_q, masks) -> pixels: then [N,3,H,W] reconstructions are returned as .decoded of each TiledImage
+    (decompress_tiled).  Does not touch the usage counter."""
+    from . import highres
+    from .entropy import entropy_maps
+    from .model import _codec_for
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"compress_tiled_to_bpp takes [N,3,H,W], got {tuple(x.shape)}")
+    q = model.quantize
+    if q.training:
+        raise RuntimeError("compress_tiled_to_bpp: the quantiser is in training mode; call model.eval() first")
+    tile = highres.TILE if tile is None else int(tile)
+    enc = model.encoder
+    params = enc.router_config["params"]
+    coarse = float(params["coarse_grain_ratio"])
+    codec = _codec_for(model)
+    N, H, W = x.shape[0], x.shape[2], x.shape[3]
+    pad, grid, order, batches = highres.cut_groups(x, tile)
+    got, hooks = {}, []
+
+    def grab(name):
+        def hook(mod, args, out):
+            got[name] = out
+        return hook
+
+    for name, mod in (("c", enc.conv_out_coarse), ("m", enc.conv_out), ("f", enc.conv_out_fine)):
+        hooks.append(mod.register_forward_hook(grab(name)))
+    saved = params.get("per_image", None)
+    params["per_image"] = True
+    groups = []
+    try:
+        with torch.no_grad():
+            for ((th, tw), idxs), batch in zip(order, batches):
+                model.encode(batch)
+                inds = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
+                e8, e16 = entropy_maps(batch, reference_order=True)
+                groups.append((*inds, e16, e8, [n for n in range(N) for _ in idxs]))
+    finally:
+        for hk in hooks:
+            hk.remove()
+        if saved is None:
+            params.pop("per_image", None)
+        else:
+            params["per_image"] = saved
+    with torch.no_grad():
+        curve = rate_curve_tiled(codec, groups, coarse, image_hw=(H, W))
+        (c, fits), cand = _pick_tiled(curve, target_bpp)
+        cr, mr = cand[c]
+        M = len(curve.candidates)
+        curve.fits, curve.chosen = fits, (c if c < M else None)
+        router = TripleGrainFixedEntropyRouter(cr, mr, per_image=True)
+        comp_groups = []
+        for (_, idxs), (ind_c, ind_m, ind_f, e16, e8, _) in zip(order, groups):
+            masks, _, _, mode = router(e16, e8, want_gate=False)
+            ind = gather_grain_indices(ind_c, ind_m, ind_f, masks)
+            comp_groups.append((idxs, codec.compress(ind, masks, mode), (ind.reshape(-1), masks, mode)))
+        out = highres.assemble_tiled((H, W), pad, grid, comp_groups, N)
+        if decode is not None:
+            for t in out:
+                t.decoded = highres.decompress_tiled(t, codec, decode=decode)[1]
+    bpp = (curve.bpp[:, c] if c < M else curve.ends.bpp[c - M]).tolist()
+    if N == 1:
+        return out[0], bpp[0], (cr, mr), curve
+    return out, bpp, (cr, mr), curve
+
+
 def _pick(bpp, candidates, target):
     """index of the largest bpp <= target (ties: smaller coarse, then smaller medium); none fits: the smallest bpp"""
     idx = list(range(len(candidates)))
@@ -268,9 +567,18 @@ def choose(table, target_bpp, per="batch"):
     """the candidate with the largest bpp that is <= target_bpp (ties: the smaller coarse ratio, then the smaller medium ratio);
     if none fits, the smallest-bpp candidate with fits=False.  per="batch": on batch_bpp -> (c, fits); per="image": on each
     image's bpp -> (c [B] int64, fits [B] bool) numpy-free lists as tensors, for callers that compress image by image.
-    table: a RateTable (c = the candidate's index) or a RateCurve (c = the medium rank K, among the ranks a ratio reaches; the
-    curve is not monotone in K, so this is a search over all of them, not a bisection)"""
+    table: a RateTable (c = the candidate's index), a RateCurve (c = the medium rank K, among the ranks a ratio reaches; the
+    curve is not monotone in K, so this is a search over all of them, not a bisection) or a TiledRateCurve (c = the index of
+    the setting on its medium axis)"""
     target = float(target_bpp)
+    if isinstance(table, TiledRateCurve):
+        # c = the index of the setting (ties: the smaller medium ratio, as above)
+        if per == "batch":
+            return _pick(table.batch_bpp.tolist(), table.candidates, target)
+        if per == "image":
+            picks = [_pick(row.tolist(), table.candidates, target) for row in table.bpp]
+            return torch.tensor([c for c, _ in picks], dtype=torch.int64), torch.tensor([f for _, f in picks], dtype=torch.bool)
+        raise ValueError(f"choose: per={per!r}; 'batch' or 'image'")
     curve = isinstance(table, RateCurve)
     if curve:
         if not table.ranks:

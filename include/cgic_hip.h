@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 10
+#define CGIC_ABI_VERSION 11
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -568,7 +568,7 @@ int cgic_compress_tiled(const cgic_table *t, const float *codebook, int K, int e
                         int decoder, int *mode_out, cgic_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * I. Rate tables (ABI 9) and rate curves (ABI 10): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
+ * I. Rate tables (ABI 9), rate curves (ABI 10) and rate curves of tiled images (ABI 11): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
  * ratios, without writing a stream -- the "which ratio gives which bpp on THIS image" question of a controllable codec.
  *
  * Exactness.  In the encoder's merge h = up4(h_c)*up4(m_c) + up2(h_m)*up2(m_m) + h_f*m_f (vqvae_blocks.py:361-366) every
@@ -643,6 +643,51 @@ int cgic_rate_curve(const cgic_table *t, const int64_t *ind_c, const int64_t *in
                     const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio, int32_t *nbytes, void *workspace,
                     cgic_stream_t stream);
 int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64_t n16, int64_t *k_coarse, int64_t *k_medium);
+
+/* Rate curves of tiled images (ABI 11): the curve of T tiles of MIXED shapes at M requested settings, folded per image -- rate
+ * control for the tiling driver (section H; inference_high_resolution.py).  The reference applies ONE ratio pair to all tiles of an
+ * image and routes every tile on its own thresholds (:236-251), so the bytes of the image at (c, m) are the sum over its tiles of
+ * the tile's curve at K_tile = round(4 n16_tile c + n8_tile m): the medium rank depends on the tile's SHAPE only.
+ *
+ * cgic_rate_tile: one tile.  h16, w16: its shape in 16x16 patches; k_c: its coarse rank, round(n16 * coarse_ratio) (0 at coarse
+ *   ratio 0), the expression cgic_rate_curve uses -- checked; shape: its shape class, 0 .. S - 1 (all tiles of a class have ONE
+ *   shape); image: the image it belongs to, 0 .. N - 1; reserved: 0; off_*: where its ind_c / ind_m / ind_f / e16 / e8 start
+ *   inside the concatenated buffers, in elements (each part dense: [h16,w16], [2h16,2w16], [4h16,4w16], [h16,w16], [2h16,2w16]).
+ *
+ * cgic_rate_curve_tiles:
+ *   t, ind_c / ind_m / ind_f, e16, e8   device: the code table and the concatenated buffers of all tiles (types as cgic_rate_curve)
+ *   count    host int64 [5]: the elements of ind_c, ind_m, ind_f, e16, e8 -- every tile's parts must lie inside
+ *   tiles    host [T]: the descriptors, CHECKED here;  tiles_dev  device [T]: the same bytes, READ by the kernels (the caller's
+ *            upload: it may be made once and reused while the geometry stays).  0 <= T <= 65535, 1 <= N <= 65535
+ *   coarse_ratio   as cgic_rate_curve (the stream set: mode 0, or mode 1 at 0)
+ *   ranks_dev   device int32 [S, M]: ranks[s, j] = the medium rank a tile of shape class s takes at setting j, 0 .. n8 of the
+ *            class (host arithmetic: cgic_router_ranks).  1 <= S <= 16, 1 <= M <= 65536
+ *   image_nbytes  device int64 [N, M, 5]: the five stream sizes of image n at setting j, summed over its tiles; all five -1 when a
+ *            tile of the image has a negative entry there.  An image without tiles: zeros
+ *   tile_nbytes   device int32 [T, M, 5] or NULL (then part of the workspace): tile_nbytes[t, j, :] == nbytes[b, ranks[s, j], :]
+ *            of cgic_rate_curve for that tile; <= -10: a selected symbol outside the table (as there), or a rank outside 0 .. n8
+ *   workspace device, cgic_rate_curve_tiles_workspace_bytes(T, M, tile_nbytes != NULL) bytes, 16-byte aligned; on return it starts
+ *            with int32 [T, 4] per tile, as cgic_rate_curve's per image
+ * Two launches: one workgroup per tile (steps 1-3 of cgic_rate_curve -- ONE device body for both entry points --, dynamic LDS
+ * sized to the largest tile, the descriptor read with scalar loads; then the M ranks of the tile's class: a binary search and two
+ * prefix reads each), and the fold (one thread per image and setting, int64 sums in descriptor order).  No workgroup waits on
+ * another, no atomics on global memory: the results do not depend on T, on the order of the descriptors or on which tiles share a
+ * call.  LIMITS per tile as cgic_rate_curve (n8 <= 12288, codes of at most 4095 bits, finite non-negative maps).  Every argument
+ * and every descriptor is checked before anything is enqueued: CGIC_ERR_INVALID / _UNSUPPORTED with nothing written.  Not inside
+ * a launch group. */
+typedef struct cgic_rate_tile {
+    int32_t h16, w16;
+    int32_t k_c;
+    int32_t shape;
+    int32_t image;
+    int32_t reserved;
+    int64_t off_c, off_m, off_f, off_e16, off_e8;
+} cgic_rate_tile;
+size_t cgic_rate_curve_tiles_workspace_bytes(int64_t T, int64_t M, int tile_nbytes_given);
+int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f, const float *e16,
+                          const float *e8, const int64_t *count, const cgic_rate_tile *tiles, const cgic_rate_tile *tiles_dev,
+                          int64_t T, int64_t N, double coarse_ratio, const int32_t *ranks_dev, int64_t S, int64_t M,
+                          int64_t *image_nbytes, int32_t *tile_nbytes, void *workspace, cgic_stream_t stream);
 
 #ifdef __cplusplus
 }
