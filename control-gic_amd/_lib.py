@@ -149,6 +149,8 @@ PROTOTYPES = {
     "cgic_rate_curve_tiles_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "cgic_rate_curve_tiles": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(RateTile), _vp, _i64, _i64, _f64, _vp, _i64,
                                      _i64, _vp, _vp, _vp, _vp]),
+    "cgic_route_to_budget_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "cgic_route_to_budget": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

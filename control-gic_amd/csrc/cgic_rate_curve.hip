@@ -339,6 +339,194 @@ __global__ __launch_bounds__(kFoldThreads) void rate_fold_tiles_kernel(const cgi
     for (int s = 0; s < CGIC_NUM_STREAMS; ++s) o[s] = bad ? -1 : acc[s];
 }
 
+// ---- cgic_route_to_budget: curve at R requested ranks -> pick under a byte budget read from the device -> masks and indices -----
+constexpr int kPickThreads = 1024;
+constexpr int kApplyThreads = 256;
+
+struct RateRanksArgs {
+    const int32_t *len;
+    int nsym;
+    int staged;
+    const int64_t *ind_c, *ind_m, *ind_f;
+    const float *e16, *e8;
+    int h16, w16;
+    int k_c;
+    int streams;
+    const int32_t *ranks;                            // device [R], ascending
+    int R;
+    int32_t *total;                                  // [B, R]: the five sizes summed; negative: a selected symbol outside the table
+    uint32_t *tkey;                                  // [B, R]: the medium threshold's key at that rank
+    int32_t *summary;                                // [B, 4], as rate_curve_kernel's
+};
+
+// One workgroup per image: steps 1-3 of rate_curve_kernel, then the R requested ranks -- per rank the image's bytes and the key the
+// medium mask compares against
+__global__ __launch_bounds__(kCurveThreads) void rate_curve_ranks_kernel(RateRanksArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t b = blockIdx.x;
+    const int n16 = a.h16 * a.w16, n8 = 4 * n16;
+    CurveTile c;
+    c.ind_c = a.ind_c + b * n16; c.ind_m = a.ind_m + b * n8; c.ind_f = a.ind_f + b * 4 * (int64_t)n8;
+    c.e16 = a.e16 + b * n16; c.e8 = a.e8 + b * n8;
+    c.h16 = a.h16; c.w16 = a.w16; c.k_c = a.k_c;
+    const CurveSorted r = curve_sort_scan(c, a.len, a.nsym, a.staged, a.streams, dyn);
+    int32_t *total = a.total + b * a.R;
+    uint32_t *tkey = a.tkey + b * a.R;
+    for (int j = tid; j < a.R; j += nt) {
+        const int K = a.ranks[j];
+        int32_t sum = kTilesBadRank;                 // (a rank outside 0 .. n8: the caller's list is wrong; counts as unusable)
+        uint32_t t = 0;
+        if (K >= 0 && K <= n8) {
+            int32_t o[CGIC_NUM_STREAMS];
+            curve_rank_sizes(r, K, a.streams, o);
+            bool bad = false;
+            sum = 0;
+#pragma unroll
+            for (int s = 0; s < CGIC_NUM_STREAMS; ++s) { bad |= o[s] < 0; sum += o[s]; }
+            if (bad) sum = (int32_t)(CGIC_ERR_INVALID - 10);
+            t = (uint32_t)(r.kv[K ? K - 1 : 0] >> 32);
+        }
+        total[j] = sum;
+        tkey[j] = t;
+    }
+    if (tid == 0) curve_summary(r, a.summary + b * kCurveSummary);
+}
+
+// a candidate of the pick: better = the larger (fit) or the smaller (no fit) batch size, then the smaller index (= the smaller rank)
+struct PickBest {
+    int64_t s;
+    int j;                                           // -1: none
+};
+
+__device__ __forceinline__ PickBest pick_better(PickBest x, PickBest y, bool larger)
+{
+    if (x.j < 0) return y;
+    if (y.j < 0) return x;
+    if (x.s != y.s) return ((x.s > y.s) == larger) ? x : y;
+    return x.j < y.j ? x : y;
+}
+
+// S[j] = the batch's bytes at requested rank j (int64, integer sums: any order gives the same value), then rate._pick's rule on
+// S against the budget.  ONE workgroup: with fewer ranks than threads the images are dealt over `parts` thread rows per rank
+// and the rows are added in LDS in row order
+__global__ __launch_bounds__(kPickThreads) void rate_pick_kernel(const int32_t *total, const int32_t *ranks, int B, int R,
+                                                                 const int64_t *budget_dev, int64_t *choice)
+{
+    __shared__ int64_t part_s[kPickThreads];
+    __shared__ int part_bad[kPickThreads];
+    __shared__ PickBest red[2][kPickThreads];
+    const int tid = threadIdx.x;
+    int cols = kPickThreads;
+    while (cols > 1 && (cols >> 1) >= R) cols >>= 1;
+    const int parts = kPickThreads / cols, q = tid & (cols - 1), p = tid / cols;
+    const int64_t budget = *budget_dev;
+    PickBest fit = {0, -1}, low = {0, -1};
+    int bad = 0;
+    for (int j0 = 0; j0 < R; j0 += cols) {           // (workgroup-uniform trip count; parts > 1 only when one trip covers R)
+        const int j = j0 + q;
+        int64_t s = 0;
+        if (j < R)
+            for (int b = p; b < B; b += parts) {
+                const int32_t v = total[(int64_t)b * R + j];
+                bad |= v < 0;
+                s += v;
+            }
+        if (parts > 1) {
+            part_s[tid] = s;
+            __syncthreads();
+            if (p == 0)
+                for (int k = 1; k < parts; ++k) s += part_s[k * cols + q];
+            __syncthreads();
+        }
+        if (p == 0 && j < R) {
+            const PickBest me = {s, j};
+            if (s <= budget) fit = pick_better(fit, me, true);
+            low = pick_better(low, me, false);
+        }
+    }
+    part_bad[tid] = bad;
+    red[0][tid] = fit;
+    red[1][tid] = low;
+    __syncthreads();
+    for (int d = kPickThreads >> 1; d > 0; d >>= 1) {
+        if (tid < d) {
+            red[0][tid] = pick_better(red[0][tid], red[0][tid + d], true);
+            red[1][tid] = pick_better(red[1][tid], red[1][tid + d], false);
+            part_bad[tid] |= part_bad[tid + d];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const bool any_bad = part_bad[0] != 0;
+        const bool fits = red[0][0].j >= 0;
+        const PickBest w = fits ? red[0][0] : red[1][0];
+        choice[0] = any_bad ? -1 : w.j;
+        choice[1] = any_bad ? -1 : ranks[w.j];
+        choice[2] = any_bad ? 0 : (fits ? 1 : 0);
+        choice[3] = any_bad ? -1 : w.s;
+    }
+}
+
+struct RateApplyArgs {
+    const int64_t *choice;                           // device [4]
+    const uint32_t *tkey;                            // [B, R]
+    const int32_t *summary;                          // [B, 4]
+    const int64_t *ind_c, *ind_m, *ind_f;
+    const float *e16, *e8;
+    int B, h16, w16, R;
+    int32_t *mc, *mm, *mf;
+    int64_t *ind;
+};
+
+// One thread per row of a 4x4 fine block (= one 16x16 pixel patch): four fine mask elements and four merged indices in 16-byte
+// stores, the two medium elements of even rows, the coarse element of the block's first row.  The comparisons are the sort's
+// (entropy_key): coarse = e16 < thr_c, medium = not coarse and e8 < t, fine = the rest (RouterTriple.py:25,32,34)
+__global__ __launch_bounds__(kApplyThreads) void rate_apply_kernel(RateApplyArgs a)
+{
+    const int64_t j = a.choice[0];
+    const int w16 = a.w16, h4 = 4 * a.h16, w8 = 2 * w16, w4 = 4 * w16;
+    const int64_t rows = (int64_t)a.B * h4 * w16;
+    for (int64_t i = (int64_t)blockIdx.x * kApplyThreads + threadIdx.x; i < rows; i += (int64_t)gridDim.x * kApplyThreads) {
+        const int64_t by = i / w16;
+        const int xc = (int)(i - by * w16);
+        const int64_t b = by / h4;
+        const int y = (int)(by - b * h4);
+        const int64_t o4 = by * w4 + 4 * xc;                             // (b, y, 4 xc) on the fine grid
+        const int64_t o8 = (b * (h4 >> 1) + (y >> 1)) * w8 + 2 * xc;     // (b, y / 2, 2 xc) on the medium grid
+        const int64_t o16 = (b * a.h16 + (y >> 2)) * w16 + xc;
+        int4 f = make_int4(0, 0, 0, 0);
+        int2 m = make_int2(0, 0);
+        int c = 0;
+        longlong2 v0 = {0, 0}, v1 = {0, 0};
+        if (j >= 0) {
+            const unsigned int thr = (unsigned int)a.summary[b * kCurveSummary + 1];
+            const unsigned int t = a.tkey[b * a.R + j];
+            c = entropy_key(a.e16[o16]) < thr;
+            const float2 e = *reinterpret_cast<const float2 *>(a.e8 + o8);
+            m.x = !c && entropy_key(e.x) < t;
+            m.y = !c && entropy_key(e.y) < t;
+            const int f0 = !c && !m.x, f1 = !c && !m.y;
+            f = make_int4(f0, f0, f1, f1);
+            if (c) {
+                const int64_t s = a.ind_c[o16];
+                v0 = {s, s}; v1 = {s, s};
+            } else {
+                const longlong2 sm = *reinterpret_cast<const longlong2 *>(a.ind_m + o8);
+                v0 = {sm.x, sm.x}; v1 = {sm.y, sm.y};
+                if (f0) v0 = *reinterpret_cast<const longlong2 *>(a.ind_f + o4);
+                if (f1) v1 = *reinterpret_cast<const longlong2 *>(a.ind_f + o4 + 2);
+            }
+        }
+        *reinterpret_cast<int4 *>(a.mf + o4) = f;
+        *reinterpret_cast<longlong2 *>(a.ind + o4) = v0;
+        *reinterpret_cast<longlong2 *>(a.ind + o4 + 2) = v1;
+        if ((y & 1) == 0) *reinterpret_cast<int2 *>(a.mm + o8) = m;
+        if ((y & 3) == 0) a.mc[o16] = c;
+    }
+}
+
 }  // namespace cgic
 
 using namespace cgic;
@@ -505,4 +693,88 @@ extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, 
     hipLaunchKernelGGL(rate_fold_tiles_kernel, dim3((unsigned)((M + kFoldThreads - 1) / kFoldThreads), (unsigned)N), dim3(kFoldThreads), 0,
                        (hipStream_t)stream, tiles_dev, (int)T, (int)M, (const int32_t *)a.tile_nbytes, image_nbytes);
     return launch_check("rate_fold_tiles_kernel");
+}
+
+static size_t route_slab(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+extern "C" size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int64_t R)
+{
+    if (B <= 0 || h16 <= 0 || w16 <= 0 || R <= 0 || B > 65535 || h16 > kCurveMaxN8 || w16 > kCurveMaxN8 || 4 * h16 * w16 > kCurveMaxN8
+        || R > 4 * h16 * w16 + 1)
+        return 0;
+    // the per-image summary, then per image and requested rank the bytes (int32) and the medium threshold's key (uint32)
+    return route_slab((size_t)B * kCurveSummary * sizeof(int32_t)) + 2 * route_slab((size_t)B * (size_t)R * sizeof(int32_t));
+}
+
+extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
+                                    const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio,
+                                    const int32_t *ranks_dev, int64_t R, const int64_t *budget_dev, int32_t *mask_c, int32_t *mask_m,
+                                    int32_t *mask_f, int64_t *ind, int64_t *choice_dev, void *workspace, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_route_to_budget");
+    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && ranks_dev && budget_dev && mask_c && mask_m && mask_f && ind && choice_dev,
+                 CGIC_ERR_INVALID, "route_to_budget: NULL argument");
+    CGIC_REQUIRE(B >= 1 && h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "route_to_budget: bad shape");
+    CGIC_REQUIRE(coarse_ratio >= 0.0 && coarse_ratio < 1.0, CGIC_ERR_INVALID,
+                 "route_to_budget: coarse ratio %g outside [0, 1): the curve's mode is 0, or 1 at coarse ratio 0", coarse_ratio);
+    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "route_to_budget: batch %lld exceeds the grid limit", (long long)B);
+    CGIC_REQUIRE(h16 <= kCurveMaxN8 && w16 <= kCurveMaxN8 && 4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
+                 "route_to_budget: an image of %lld 8x8 patches does not fit one workgroup's LDS (at most %lld: 768x1024 pixels)",
+                 (long long)(4 * h16 * w16), (long long)kCurveMaxN8);
+    const int64_t n16 = h16 * w16, n8 = 4 * n16;
+    CGIC_REQUIRE(R >= 1 && R <= n8 + 1, CGIC_ERR_INVALID, "route_to_budget: %lld requested ranks (1 .. %lld)", (long long)R, (long long)(n8 + 1));
+    const int nsym = cgic_table_num_symbols(t);
+    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "route_to_budget: table of %d symbols", nsym);
+    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "route_to_budget: codes of up to %d bits (at most %d)",
+                 cgic_table_max_len(t), kCurveMaxLen);
+    const int mode = coarse_ratio > 0.0 ? 0 : 1;
+    const int64_t k_c = mode == 0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0;
+    CGIC_REQUIRE(k_c >= 0 && k_c <= n16, CGIC_ERR_INVALID, "route_to_budget: k_coarse=%lld of %lld", (long long)k_c, (long long)n16);
+    const size_t need = cgic_route_to_budget_workspace_bytes(B, h16, w16, R);
+    CGIC_REQUIRE(need > 0 && workspace, CGIC_ERR_INVALID, "route_to_budget: workspace of %zu bytes required (cgic_route_to_budget_workspace_bytes)", need);
+    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "route_to_budget: the workspace must be 16-byte aligned");
+    CGIC_REQUIRE((((uintptr_t)ind_m | (uintptr_t)ind_f | (uintptr_t)mask_m | (uintptr_t)mask_f | (uintptr_t)ind) & 15u) == 0 && ((uintptr_t)e8 & 7u) == 0
+                     && ((uintptr_t)budget_dev & 7u) == 0 && ((uintptr_t)choice_dev & 7u) == 0,
+                 CGIC_ERR_INVALID, "route_to_budget: ind_m, ind_f, mask_m, mask_f and ind must be 16-byte aligned, e8, the budget and the choice 8-byte aligned");
+    TableDev tab;
+    int rc = table_device_view(t, &tab);
+    if (rc) return rc;
+
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    const size_t per_rank = route_slab((size_t)B * (size_t)R * sizeof(int32_t));
+    RateRanksArgs a;
+    a.len = tab.len; a.nsym = nsym;
+    const size_t words = (size_t)n8 * 12;
+    a.staged = words + (size_t)nsym * sizeof(int32_t) <= kCurveLdsBudget;
+    a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
+    a.h16 = (int)h16; a.w16 = (int)w16;
+    a.k_c = (int)k_c;
+    a.streams = cgic_mode_streams(mode);
+    a.ranks = ranks_dev; a.R = (int)R;
+    a.summary = reinterpret_cast<int32_t *>(ws);
+    a.total = reinterpret_cast<int32_t *>(ws + route_slab((size_t)B * kCurveSummary * sizeof(int32_t)));
+    a.tkey = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(a.total) + per_rank);
+    const size_t lds = words + (a.staged ? (size_t)nsym * sizeof(int32_t) : 0);
+    if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_curve_ranks_kernel, lds); if (rc) return rc; }
+    int threads = kCurveThreads;
+    while (threads > 256 && threads >= n8) threads >>= 1;
+    hipLaunchKernelGGL(rate_curve_ranks_kernel, dim3((unsigned)B), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
+    rc = launch_check("rate_curve_ranks_kernel");
+    if (rc) return rc;
+
+    hipLaunchKernelGGL(rate_pick_kernel, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, (const int32_t *)a.total, ranks_dev, (int)B, (int)R,
+                       budget_dev, choice_dev);
+    rc = launch_check("rate_pick_kernel");
+    if (rc) return rc;
+
+    RateApplyArgs p;
+    p.choice = choice_dev; p.tkey = a.tkey; p.summary = a.summary;
+    p.ind_c = ind_c; p.ind_m = ind_m; p.ind_f = ind_f; p.e16 = e16; p.e8 = e8;
+    p.B = (int)B; p.h16 = (int)h16; p.w16 = (int)w16; p.R = (int)R;
+    p.mc = mask_c; p.mm = mask_m; p.mf = mask_f; p.ind = ind;
+    const int64_t rows = B * 4 * h16 * w16;
+    int64_t grid = (rows + kApplyThreads - 1) / kApplyThreads;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(rate_apply_kernel, dim3((unsigned)grid), dim3(kApplyThreads), 0, (hipStream_t)stream, p);
+    return launch_check("rate_apply_kernel");
 }

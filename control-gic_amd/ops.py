@@ -10,6 +10,7 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     h = torch.ops.cgic.grain_merge(h_c, h_m, h_f, mc, mm, mf)                                     # differentiable (vqvae_blocks.py:361-366)
     nbytes = torch.ops.cgic.rate_table(ind_c, ind_m, ind_f, e16, e8, [0.1, 0.2], [0.8, 0.5], True, table)   # [C,B,5] bytes per ratio
     nbytes = torch.ops.cgic.rate_curve(ind_c, ind_m, ind_f, e16, e8, 0.1, table)                          # [B,n8+1,5] bytes per medium rank
+    mc, mm, mf, ind, choice = torch.ops.cgic.route_to_bpp(ind_c, ind_m, ind_f, e16, e8, 0.1, budget, table)  # the rank picked on the device
     ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
@@ -228,6 +229,31 @@ def rate_curve(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e1
 @rate_curve.register_fake
 def _(ind_c, ind_m, ind_f, e16, e8, coarse, table):
     return e16.new_empty((e16.shape[0], 4 * e16.shape[1] * e16.shape[2] + 1, _lib.NUM_STREAMS), dtype=torch.int32)
+
+
+@torch.library.custom_op("cgic::route_to_bpp", mutates_args=(), device_types=_DEV)
+def route_to_bpp(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e16: torch.Tensor, e8: torch.Tensor, coarse: float,
+                 budget: torch.Tensor, table: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """route the batch at the medium rank whose batch size is the largest one within `budget` bytes (int64 [1] on the device),
+    decided on the device without a host synchronisation (cgic_route_to_budget): (mask_c, mask_m, mask_f int32 in the router's
+    layouts, ind int64 [B,h,w], choice int64 [4] = {j, K, fits, batch bytes}; all -1, fits 0 and zero outputs when a requested
+    entry holds a symbol outside the table)"""
+    from .rate import route_to_bpp as _route_to_bpp
+
+    class _Codec:            # the op carries the table as its handle
+        class huffman:
+            class table:
+                handle = _table(table)
+    r = _route_to_bpp(_Codec, ind_c, ind_m, ind_f, e16, e8, coarse, budget=budget)
+    return r.masks[0], r.masks[1], r.masks[2], r.ind, r.choice
+
+
+@route_to_bpp.register_fake
+def _(ind_c, ind_m, ind_f, e16, e8, coarse, budget, table):
+    B, h16, w16 = e16.shape
+    return (e16.new_empty((B, 1, h16, w16), dtype=torch.int32), e16.new_empty((B, 1, 2 * h16, 2 * w16), dtype=torch.int32),
+            e16.new_empty((B, 1, 4 * h16, 4 * w16), dtype=torch.int32), e16.new_empty((B, 4 * h16, 4 * w16), dtype=torch.int64),
+            e16.new_empty((4,), dtype=torch.int64))
 
 
 _DECODERS = {"auto": 0, "latency": 1, "throughput": 2}

@@ -10,6 +10,11 @@ select (include/cgic_hip.h, section I).  `compress_to_bpp` then c
 integer, the rank K of its threshold among the 8x8-patch entropies, and one sort of the image's patches gives the sizes of all
 n8 + 1 ranks (cgic_rate_curve).  `compress_to_bpp(..., search="curve")` picks among all of them.
 
+`route_to_bpp` keeps the decision of that search on the device: the curve at the ranks a ratio reaches, the pick under a byte
+budget read from device memory, and the masks and merged indices of the picked rank, in one launch chain without a host
+synchronisation (cgic_route_to_budget) -- so a rate-controlled batch can sit inside a captured graph.
+`compress_to_bpp(..., search="device")` compresses what it routes.
+
 `rate_curve_tiled` answers it for tiled high-resolution images (highres.py): ONE ratio pair for all tiles of an image, every
 tile routed on its own thresholds, so an image's bytes at (c, m) are the sum of its tiles' curves at the rank m gives a tile of
 that SHAPE (`tiled_settings`: the medium axis of a set of shapes); one call for all tiles of all shapes
@@ -309,6 +314,137 @@ def rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, ranks=None):
                   _lib.current_stream(dev))
     n_coarse = ws[:B * 16].view(torch.int32).view(B, 4)[:, 0].to(torch.int64).cpu()
     return RateCurve(nbytes, coarse_ratio, 256 * h16 * w16, ranks=ranks, n_coarse=n_coarse)
+
+
+def _batch_bpp(S, num_pixels, B):
+    """RateCurve.batch_bpp's float64 expression for a batch of S bytes"""
+    return float(S) * 8 / (int(num_pixels) * max(int(B), 1))
+
+
+def budget_bytes(target_bpp, num_pixels, B):
+    """the largest integer S with float64(S) * 8 / (num_pixels * B) <= target_bpp, in the float64 expression of
+    RateCurve.batch_bpp: the byte budget under which an integer comparison S[K] <= budget picks exactly what `choose` picks on
+    batch_bpp <= target_bpp.  -1 when not even S = 0 fits (a negative target); capped at 2^62.  Pure host arithmetic"""
+    target, P, B = float(target_bpp), int(num_pixels), max(int(B), 1)
+    if P <= 0:
+        raise ValueError(f"budget_bytes: {num_pixels} pixels")
+    if math.isnan(target):
+        raise ValueError("budget_bytes: the target is NaN")
+    cap = 1 << 62
+    if _batch_bpp(cap, P, B) <= target:
+        return cap
+    if not _batch_bpp(0, P, B) <= target:
+        return -1
+    S = min(max(int(math.floor(target * (P * B) / 8)), 0), cap)
+    while S > 0 and not _batch_bpp(S, P, B) <= target:
+        S -= 1
+    while S < cap and _batch_bpp(S + 1, P, B) <= target:
+        S += 1
+    return S
+
+
+_RANKS_DEV = {}
+
+
+def _ranks_on_device(dev, n16, c):
+    """(K int32 [R] on `dev`, K int64 [R] and medium float64 [R] on the host) of reachable_ranks_vec(n16, c): the ranks
+    RateCurve.ranks holds; uploaded once per (device, n16, c)"""
+    key = (str(dev), int(n16), float(c))
+    hit = _RANKS_DEV.get(key)
+    if hit is None:
+        K, m = reachable_ranks_vec(int(n16), float(c))
+        if len(_RANKS_DEV) >= 64:
+            _RANKS_DEV.clear()
+        hit = _RANKS_DEV[key] = (K.to(torch.int32).to(dev), K, m)
+    return hit
+
+
+class BppRoute:
+    """route_to_bpp's result.  masks: [mask_c, mask_m, mask_f] int32 in the router's layouts, ind int64 [B,h,w], mode: the
+    curve's mode (host int: 0, or 1 at coarse ratio 0), choice: the device record int64 [4] = {j, K, fits, batch bytes} (all
+    -1 with fits 0 when a requested entry holds a symbol outside the code table; masks and ind are zeros then).
+    .rank, .ratio, .fits, .batch_bytes read the record -- the first access synchronises; a captured graph's replays rewrite the
+    record: refresh() drops what was read -- and raise KeyError on the -1 record"""
+
+    def __init__(self, masks, ind, mode, choice, coarse_ratio, ranks, mediums):
+        self.masks, self.ind, self.mode, self.choice = masks, ind, int(mode), choice
+        self.coarse_ratio = float(coarse_ratio)
+        self._ranks, self._mediums = ranks, mediums
+        self._rec = None
+
+    def refresh(self):
+        self._rec = None
+        return self
+
+    def _record(self):
+        if self._rec is None:
+            self._rec = [int(v) for v in self.choice.cpu().tolist()]
+        if self._rec[0] < 0:
+            raise KeyError("route_to_bpp: an index is not in the code table")
+        return self._rec
+
+    @property
+    def rank(self):
+        return self._record()[1]
+
+    @property
+    def ratio(self):
+        """the (coarse, medium) pair that reaches the chosen rank"""
+        return self.coarse_ratio, float(self._mediums[self._record()[0]])
+
+    @property
+    def fits(self):
+        return bool(self._record()[2])
+
+    @property
+    def batch_bytes(self):
+        return self._record()[3]
+
+
+def route_to_bpp(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, target_bpp=None, budget=None):
+    """route a same-size batch at the medium rank whose exact batch bpp is the largest one <= target_bpp, decided ON THE DEVICE
+    (cgic_route_to_budget): among the ranks a medium ratio reaches at `coarse_ratio` in the curve's mode (0, or 1 at coarse
+    ratio 0; the two ends of the medium axis are other modes: compress_to_bpp(search="curve") covers them), what
+    choose(rate_curve(...), target_bpp) picks, then the masks of TripleGrainFixedEntropyRouter(per_image=True) at that rank on
+    the maps as given and gather_grain_indices of them.  Arguments as rate_curve's.  budget: an int64 device tensor of one
+    element, the byte budget of the batch (budget_bytes), used as it is -- a captured graph is replayed with a new target by
+    writing into it; else it is made from target_bpp.  The call does not synchronise and copies nothing to the host.
+    -> BppRoute"""
+    _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
+    e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
+    B, h16, w16 = e16c.shape
+    if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
+        raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
+    want = ((B, h16, w16), (B, 2 * h16, 2 * w16), (B, 4 * h16, 4 * w16))
+    inds = []
+    for t, shp in zip((ind_c, ind_m, ind_f), want):
+        if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
+            raise ValueError(f"grain indices must be int64 with shapes {want}")
+        inds.append(t.contiguous())
+    dev = e16c.device
+    c = float(coarse_ratio)
+    if (target_bpp is None) == (budget is None):
+        raise ValueError("route_to_bpp: give target_bpp or budget (one of them)")
+    ranks_dev, ranks, mediums = _ranks_on_device(dev, h16 * w16, c)
+    R = int(ranks.numel())
+    if R < 1:
+        raise ValueError(f"route_to_bpp: no medium ratio reaches a rank at coarse ratio {c}")
+    if budget is None:
+        budget = torch.full((1,), budget_bytes(target_bpp, 256 * h16 * w16, B), dtype=torch.int64, device=dev)
+    elif not (isinstance(budget, torch.Tensor) and budget.dtype == torch.int64 and budget.numel() == 1 and budget.device == dev
+              and budget.is_contiguous()):
+        raise ValueError("route_to_bpp: budget must be an int64 tensor of one element on the maps' device")
+    mc = torch.empty((B, 1, h16, w16), dtype=torch.int32, device=dev)
+    mm = torch.empty((B, 1, 2 * h16, 2 * w16), dtype=torch.int32, device=dev)
+    mf = torch.empty((B, 1, 4 * h16, 4 * w16), dtype=torch.int32, device=dev)
+    ind = torch.empty((B, 4 * h16, 4 * w16), dtype=torch.int64, device=dev)
+    choice = torch.empty((4,), dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(_lib.lib().cgic_route_to_budget_workspace_bytes(B, h16, w16, R)), 16), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("cgic_route_to_budget", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+                  _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, c, _lib.ptr(ranks_dev), R, _lib.ptr(budget), _lib.ptr(mc), _lib.ptr(mm),
+                  _lib.ptr(mf), _lib.ptr(ind), _lib.ptr(choice), _lib.ptr(ws), _lib.current_stream(dev))
+    return BppRoute([mc, mm, mf], ind, 0 if c > 0.0 else 1, choice, c, ranks, mediums)
 
 
 def gather_grain_indices(ind_c, ind_m, ind_f, masks):
@@ -617,13 +753,19 @@ def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True, sear
     medium ranks plus the two ends of the axis (medium 0, fine 0) from a rate table, on the maps of
     entropy_maps(input, reference_order=True), on which routing on the maps as given is the reference's routing from the pixels.
     Returns a RateCurve in place of the table, with .fits, .chosen_rank (None: an end was chosen) and .ends (their RateTable);
-    the returned bpp is the curve's entry of the chosen rank."""
+    the returned bpp is the curve's entry of the chosen rank.
+    search="device": the curve search with the decision kept on the GPU (route_to_bpp): on the same maps, the curve at every
+    rank a medium ratio reaches, the pick, the masks and the merged indices in one launch chain without a host synchronisation;
+    the host reads the choice only after the coder has been enqueued.  It covers the INTERIOR of the medium axis only -- the
+    curve's mode, medium > 0 and fine > 0: the two ends are other routing modes, and which streams a mode writes is a host
+    argument of the coder; search="curve" remains the way to include them.  Returns the BppRoute in place of the table (.rank,
+    .ratio, .fits, .batch_bytes); KeyError if an index is not in the code table."""
     from .model import _codec_for, _decode
     assert len(input.shape) == 4
-    if search not in ("candidates", "curve"):
-        raise ValueError(f"compress_to_bpp: search={search!r}; 'candidates' or 'curve'")
-    if search == "curve" and candidates is not None:
-        raise ValueError("compress_to_bpp: search='curve' takes no candidates (it covers every medium ratio of the router config's coarse ratio)")
+    if search not in ("candidates", "curve", "device"):
+        raise ValueError(f"compress_to_bpp: search={search!r}; 'candidates', 'curve' or 'device'")
+    if search != "candidates" and candidates is not None:
+        raise ValueError(f"compress_to_bpp: search={search!r} takes no candidates (it covers every medium ratio of the router config's coarse ratio)")
     q = model.quantize
     if q.training:
         raise RuntimeError("compress_to_bpp: the quantiser is in training mode; call model.eval() first")
@@ -660,6 +802,15 @@ def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True, sear
             params["per_image"] = saved
     with torch.no_grad():
         ind_c, ind_m, ind_f = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
+        if search == "device":
+            from .entropy import entropy_maps
+            e8, e16 = entropy_maps(input, reference_order=True)
+            route = route_to_bpp(codec, ind_c, ind_m, ind_f, e16, e8, float(params["coarse_grain_ratio"]), target_bpp=target_bpp)
+            comp = codec.compress(route.ind, route.masks, route.mode)
+            ratio = route.ratio                                          # (the first read of the choice: KeyError on the -1 record)
+            bpp = comp.bpp(input.shape[2] * input.shape[3])
+            dec = _decode(model, codec, comp) if decode else None
+            return dec, bpp, comp, ratio, route
         if search == "curve":
             from .entropy import entropy_maps
             coarse = float(params["coarse_grain_ratio"])

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 11
+#define CGIC_ABI_VERSION 12
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -568,7 +568,7 @@ int cgic_compress_tiled(const cgic_table *t, const float *codebook, int K, int e
                         int decoder, int *mode_out, cgic_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * I. Rate tables (ABI 9), rate curves (ABI 10) and rate curves of tiled images (ABI 11): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
+ * I. Rate tables (ABI 9), rate curves (ABI 10), rate curves of tiled images (ABI 11) and the device-side rate pick (ABI 12): the .bin sizes CGIC.compress (model.py:217-262) would write for each of C candidate granularity
  * ratios, without writing a stream -- the "which ratio gives which bpp on THIS image" question of a controllable codec.
  *
  * Exactness.  In the encoder's merge h = up4(h_c)*up4(m_c) + up2(h_m)*up2(m_m) + h_f*m_f (vqvae_blocks.py:361-366) every
@@ -688,6 +688,39 @@ int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64
                           const float *e8, const int64_t *count, const cgic_rate_tile *tiles, const cgic_rate_tile *tiles_dev,
                           int64_t T, int64_t N, double coarse_ratio, const int32_t *ranks_dev, int64_t S, int64_t M,
                           int64_t *image_nbytes, int32_t *tile_nbytes, void *workspace, cgic_stream_t stream);
+
+/* Device-side rate pick (ABI 12): route a same-size batch at the medium rank whose batch size is the largest one within a byte
+ * budget -- curve, decision, masks and merged indices in one launch chain, the budget read from DEVICE memory: no host
+ * synchronisation, no device-to-host copy and no launch parameter that depends on device results, so the chain can be captured in
+ * a graph and replayed with another budget.  A same-size batch shares ONE medium rank per ratio pair (cgic_router_ranks does not
+ * depend on the image), so the batch pick is a sum over the images per rank and an argmax under the budget.
+ *
+ * cgic_route_to_budget:
+ *   t, ind_c / ind_m / ind_f, e16, e8, B, h16, w16, coarse_ratio   as cgic_rate_curve, with B >= 1 and coarse_ratio in [0, 1):
+ *            the curve's mode -- 0, or 1 at coarse ratio 0.  ind_m, ind_f 16-byte aligned, e8 8-byte aligned
+ *   ranks_dev   device int32 [R], 1 <= R <= n8 + 1: the medium ranks to choose among, ASCENDING, each one a rank a medium ratio
+ *            reaches at this coarse ratio in the curve's mode (host arithmetic: cgic_router_ranks).  The CALLER owns this: the
+ *            library cannot check a device list without a synchronisation.  (A rank outside 0 .. n8 is not dereferenced; it
+ *            makes the choice -1.)
+ *   budget_dev  device int64 [1]: the byte budget of the whole batch, read by the pick launch
+ *   mask_c / mask_m / mask_f   device int32 [B,1,h16,w16] / [B,1,2h16,2w16] / [B,1,4h16,4w16], mask_m and mask_f 16-byte aligned:
+ *            the masks cgic_router_f32 writes with per_image = 1 and refine = NULL at a ratio pair whose ranks are
+ *            (k_c, the chosen K): coarse = e16 < s16[k_c - 1], medium = not coarse and e8 < t, fine = the rest
+ *   ind      device int64 [B,4h16,4w16], 16-byte aligned: cgic_gather_grain_indices of those masks
+ *   choice_dev  device int64 [4]: { j, K = ranks[j], fits, S[j] } with S[j] = the sum over the images of the five stream sizes at
+ *            ranks[j] -- among the j with S[j] <= budget the largest S, on a tie the smaller j; if none fits the smallest S, on a tie
+ *            the smaller j, and fits = 0.  If ANY requested entry of any image is negative (a selected symbol outside the table:
+ *            what makes cgic_rate_curve's table negative there): { -1, -1, 0, -1 }, and the masks and ind are all zeros
+ *   workspace device, cgic_route_to_budget_workspace_bytes(B, h16, w16, R) bytes, 16-byte aligned
+ * Three launches ordered by the stream alone: the curve (one workgroup per image, steps 1-3 of cgic_rate_curve -- the same
+ * device body -- then per requested rank the image's bytes and the medium threshold's key), the pick (one workgroup; integer
+ * sums, so the result does not depend on any order) and the apply (elementwise, 16-byte stores).  No workgroup waits on another.
+ * LIMITS as cgic_rate_curve.  Every host argument is checked before anything is enqueued.  Not inside a launch group. */
+size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int64_t R);
+int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f, const float *e16,
+                         const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio, const int32_t *ranks_dev, int64_t R,
+                         const int64_t *budget_dev, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, int64_t *ind,
+                         int64_t *choice_dev, void *workspace, cgic_stream_t stream);
 
 #ifdef __cplusplus
 }

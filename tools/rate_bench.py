@@ -20,7 +20,16 @@ Device time by HIP events per call over --iters calls, and wall time to the fold
 over --rounds rounds; median round and [min, max].  Also the host time of tiled_settings, and compress_tiled_to_bpp of a
 stand-in model against one compress_tiled_batch at a fixed ratio.
 
+--device: the device-side rate pick against the host's, to the point where the masks and merged indices of the picked rank
+exist on the device:
+  host:    rate_curve (the [B, n8+1, 5] table to the host) -> choose -> router at the picked ratio -> gather_grain_indices
+  device:  route_to_bpp (cgic_route_to_budget: curve at the reachable ranks, pick, masks + indices; nothing read back)
+Wall time per call with a synchronisation after each (the host leg counts), and HIP-event device time of the entry points
+called back to back on preallocated buffers: the host path's three launches (curve, router, gather) one by one, and the
+chain.  The variants alternate over --rounds rounds; median round and [min, max].
+
     python tools/rate_bench.py [--B 64] [--H 256] [--C 16] [--iters 20]
+    python tools/rate_bench.py --device [--B 64] [--H 256] [--iters 200] [--rounds 5]
     python tools/rate_bench.py --tiled [--iters 50] [--rounds 5]
     python tools/rate_bench.py --curve [--B 64] [--H 256] [--iters 200] [--rounds 5]
 """
@@ -91,6 +100,88 @@ def curve_bench(a, dev, codec, inds, e16, e8, x):
     for name, v in times.items():
         out[name] = round(sorted(v)[len(v) // 2], 1)
         out[name.replace("_us", "_spread_us")] = [round(min(v), 1), round(max(v), 1)]
+    print(json.dumps(out))
+
+
+def device_bench(a, dev, codec, inds, e16, e8):
+    """the host's rate pick (curve -> choose -> router -> gather) against route_to_bpp"""
+    import time
+    from control_gic_amd import rate
+    l = _lib.lib()
+    B, h16, w16 = e16.shape
+    n16, n8, coarse = h16 * w16, 4 * h16 * w16, 0.1
+    tab = codec.huffman.table.handle
+    stream = _lib.current_stream(dev)
+    ptrs = [_lib.ptr(t) for t in (*inds, e16, e8)]
+    K, m = rate.reachable_ranks_vec(n16, coarse)
+    ranks = tuple(zip(K.tolist(), m.tolist()))
+    curve = cg.rate_curve(codec, *inds, e16, e8, coarse, ranks=ranks)
+    bb = curve.batch_bpp[K]
+    target = float(bb.median())
+
+    def host_path():
+        cv = cg.rate_curve(codec, *inds, e16, e8, coarse, ranks=ranks)
+        k, _ = cg.choose(cv, target)
+        c, md = cv.ratio(k)
+        masks, _, _, _ = cg.TripleGrainFixedEntropyRouter(c, md, per_image=True)(e16, e8, want_gate=False)
+        return k, masks, cg.gather_grain_indices(*inds, masks)
+
+    def device_path():
+        return cg.route_to_bpp(codec, *inds, e16, e8, coarse, target_bpp=target)
+
+    k, masks, ind = host_path()
+    route = device_path()
+    exact = route.rank == k and all(torch.equal(x, y) for x, y in zip(route.masks + [route.ind], masks + [ind]))
+
+    # the entry points on preallocated buffers
+    R = int(K.numel())
+    ranks_dev = K.to(torch.int32).to(dev)
+    budget = torch.tensor([cg.budget_bytes(target, 256 * n16, B)], dtype=torch.int64, device=dev)
+    mc, mm, mf = (torch.empty_like(t) for t in masks)
+    out_ind, choice = torch.empty_like(ind), torch.empty(4, dtype=torch.int64, device=dev)
+    nbc = torch.empty((B, n8 + 1, 5), dtype=torch.int32, device=dev)
+    wsc = torch.empty(l.cgic_rate_curve_workspace_bytes(B, h16, w16), dtype=torch.uint8, device=dev)
+    wsr = torch.empty(l.cgic_route_to_budget_workspace_bytes(B, h16, w16, R), dtype=torch.uint8, device=dev)
+    mode = ctypes.c_int(0)
+    md = curve.ratio(k)[1]
+    launches = {
+        "host_curve_launch_us": lambda: _lib.call("cgic_rate_curve", tab, *ptrs, B, h16, w16, coarse, _lib.ptr(nbc), _lib.ptr(wsc), stream),
+        "host_router_launch_us": lambda: _lib.call("cgic_router_f32", ptrs[3], ptrs[4], B, h16, w16, coarse, md, 1, _lib.ptr(mc), _lib.ptr(mm),
+                                                   _lib.ptr(mf), None, ctypes.byref(mode), None, stream),
+        "host_gather_launch_us": lambda: _lib.call("cgic_gather_grain_indices", ptrs[0], ptrs[1], ptrs[2], _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf),
+                                                   B, 4 * h16, 4 * w16, _lib.ptr(out_ind), stream),
+        "device_chain_us": lambda: _lib.call("cgic_route_to_budget", tab, *ptrs, B, h16, w16, coarse, _lib.ptr(ranks_dev), R, _lib.ptr(budget),
+                                             _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), _lib.ptr(out_ind), _lib.ptr(choice), _lib.ptr(wsr), stream),
+    }
+    walls = {"host_path_wall_us": host_path, "device_path_wall_us": device_path}
+    times = {n: [] for n in list(launches) + list(walls)}
+    for fn in list(launches.values()) + list(walls.values()):
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for name, fn in launches.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(a.iters):
+                fn()
+            t1.record()
+            torch.cuda.synchronize()
+            times[name].append(t0.elapsed_time(t1) * 1000.0 / a.iters)
+        for name, fn in walls.items():
+            iters = max(a.iters // 4, 3)
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+                torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - w0) * 1e6 / iters)
+    out = {"metric": "route_to_bpp_vs_host_pick", "B": B, "H": 16 * h16, "W": 16 * w16, "ranks": R, "exact": bool(exact), "picked_rank": int(k),
+           "iters": a.iters, "rounds": a.rounds}
+    for name, v in times.items():
+        out[name] = round(sorted(v)[len(v) // 2], 1)
+        out[name.replace("_us", "_spread_us")] = [round(min(v), 1), round(max(v), 1)]
+    out["host_launches_sum_us"] = round(out["host_curve_launch_us"] + out["host_router_launch_us"] + out["host_gather_launch_us"], 1)
     print(json.dumps(out))
 
 
@@ -284,6 +375,7 @@ def main():
     ap.add_argument("--curve", action="store_true", help="cgic_rate_curve next to cgic_rate_table (entry points only)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--tiled", action="store_true", help="cgic_rate_curve_tiles against one cgic_rate_curve per shape group + host fold")
+    ap.add_argument("--device", action="store_true", help="route_to_bpp (the rate pick on the device) against rate_curve -> choose -> router -> gather")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.tiled:
@@ -303,6 +395,10 @@ def main():
         if a.curve:
             inds = cg.grain_indices(vq, *heads, quant_conv=qc)
             return curve_bench(a, dev, codec, inds, e16, e8, x)
+        if a.device:
+            e8r, e16r = cg.entropy_maps(x, reference_order=True)
+            inds = cg.grain_indices(vq, *heads, quant_conv=qc)
+            return device_bench(a, dev, codec, inds, e16r.detach().clone(), e8r.detach().clone())
 
         def rate():
             inds = cg.grain_indices(vq, *heads, quant_conv=qc)
