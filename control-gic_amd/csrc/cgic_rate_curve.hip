@@ -550,68 +550,113 @@ extern "C" int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64
     return CGIC_OK;
 }
 
+// ---- the host side of the three curve entry points: ONE set of checks, ONE LDS / launch plan ---------------------------------------
+// cgic_rate_curve, cgic_rate_curve_tiles and cgic_route_to_budget launch the same steps 1-3 under the same limits; what differs between
+// them is stated at the call: `who` (the name at the front of every message), whether coarse ratio 1 is allowed, the smallest batch
+
+// the coarse ratio's range (its top end included or not) and the table
+static int curve_setup_check(const char *who, const cgic_table *t, double coarse_ratio, bool one_allowed)
+{
+    CGIC_REQUIRE(coarse_ratio >= 0.0 && (one_allowed ? coarse_ratio <= 1.0 : coarse_ratio < 1.0), CGIC_ERR_INVALID, "%s: coarse ratio %g outside [0, 1%s",
+                 who, coarse_ratio, one_allowed ? "]" : "): the curve's mode is 0, or 1 at coarse ratio 0");
+    const int nsym = cgic_table_num_symbols(t);
+    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "%s: table of %d symbols", who, nsym);
+    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "%s: codes of up to %d bits (at most %d)", who,
+                 cgic_table_max_len(t), kCurveMaxLen);
+    return CGIC_OK;
+}
+
+// the coarse rank of mode 0 (coarse ratio > 0); coarse ratio == 0 is mode 1: no coarse patch
+static int64_t curve_coarse_rank(int64_t n16, double coarse_ratio) { return coarse_ratio > 0.0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0; }
+
+static const char *curve_item(char (&buf)[32], int64_t tile)
+{
+    if (tile < 0) snprintf(buf, sizeof buf, "an image");
+    else snprintf(buf, sizeof buf, "tile %lld", (long long)tile);
+    return buf;
+}
+
+// one shape (tile >= 0: that tile's; else the batch's): positive, within one workgroup's LDS, and the coarse rank the ratio gives it
+static int curve_shape_check(const char *who, int64_t tile, int64_t h16, int64_t w16, double coarse_ratio, int64_t *k_c)
+{
+    char item[32];
+    CGIC_REQUIRE(h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "%s: %s: bad shape", who, curve_item(item, tile));
+    CGIC_REQUIRE(h16 <= kCurveMaxN8 && w16 <= kCurveMaxN8 && 4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
+                 "%s: %s of %lld x %lld coarse patches does not fit one workgroup's LDS (at most %lld 8x8 patches: 768x1024 pixels)", who,
+                 curve_item(item, tile), (long long)h16, (long long)w16, (long long)kCurveMaxN8);
+    const int64_t n16 = h16 * w16;
+    *k_c = curve_coarse_rank(n16, coarse_ratio);
+    CGIC_REQUIRE(*k_c >= 0 && *k_c <= n16, CGIC_ERR_INVALID, "%s: %s: k_coarse=%lld of %lld", who, curve_item(item, tile), (long long)*k_c,
+                 (long long)n16);
+    return CGIC_OK;
+}
+
+static int curve_workspace_check(const char *who, const void *workspace, size_t need)
+{
+    CGIC_REQUIRE(need > 0 && workspace, CGIC_ERR_INVALID, "%s: workspace of %zu bytes required (cgic_%s_workspace_bytes)", who, need, who);
+    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    return CGIC_OK;
+}
+
+// every part of a workspace starts on a 256-byte boundary
+static size_t slab(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+static size_t summary_slab(int64_t n) { return slab((size_t)n * kCurveSummary * sizeof(int32_t)); }
+
+// THE launch plan of steps 1-3: one workgroup per image / tile, LDS and threads by the call's largest (n8_max 8x8 patches); fills what the
+// three argument blocks share (table, mode's streams, staging) and launches
+template <class A>
+static int curve_launch(void (*kernel)(A), const char *name, const cgic_table *t, double coarse_ratio, int64_t grid, int64_t n8_max, A a,
+                        hipStream_t stream)
+{
+    TableDev tab;
+    int rc = table_device_view(t, &tab);
+    if (rc) return rc;
+    a.len = tab.len; a.nsym = cgic_table_num_symbols(t);
+    a.streams = cgic_mode_streams(coarse_ratio > 0.0 ? 0 : 1);
+    const size_t words = (size_t)n8_max * 12, lens = (size_t)a.nsym * sizeof(int32_t);
+    a.staged = words + lens <= kCurveLdsBudget;      // the code lengths fit the LDS behind the words
+    const size_t lds = words + (a.staged ? lens : 0);
+    if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)kernel, lds); if (rc) return rc; }
+    int threads = kCurveThreads;                     // one comparator per thread and pass while the image is small; whole waves
+    while (threads > 256 && threads >= n8_max) threads >>= 1;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, a);
+    return launch_check(name);
+}
+
 extern "C" size_t cgic_rate_curve_workspace_bytes(int64_t B, int64_t h16, int64_t w16)
 {
     if (B <= 0 || h16 <= 0 || w16 <= 0) return 0;
-    return (((size_t)B * kCurveSummary * sizeof(int32_t)) + 255) & ~(size_t)255;
+    return summary_slab(B);
 }
 
 extern "C" int cgic_rate_curve(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
                                const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio,
                                int32_t *nbytes, void *workspace, cgic_stream_t stream)
 {
+    static const char who[] = "rate_curve";
     CGIC_NOT_IN_GROUP("cgic_rate_curve");
-    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && nbytes, CGIC_ERR_INVALID, "rate_curve: NULL argument");
-    CGIC_REQUIRE(B >= 0 && h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "rate_curve: bad shape");
-    CGIC_REQUIRE(coarse_ratio >= 0.0 && coarse_ratio <= 1.0, CGIC_ERR_INVALID, "rate_curve: coarse ratio %g outside [0, 1]", coarse_ratio);
-    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "rate_curve: batch %lld exceeds the grid limit", (long long)B);
-    CGIC_REQUIRE(h16 <= kCurveMaxN8 && w16 <= kCurveMaxN8 && 4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
-                 "rate_curve: an image of %lld 8x8 patches does not fit one workgroup's LDS (at most %lld: 768x1024 pixels)",
-                 (long long)(4 * h16 * w16), (long long)kCurveMaxN8);
-    const int64_t n16 = h16 * w16, n8 = 4 * n16;
-    const int nsym = cgic_table_num_symbols(t);
-    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "rate_curve: table of %d symbols", nsym);
-    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "rate_curve: codes of up to %d bits (at most %d)",
-                 cgic_table_max_len(t), kCurveMaxLen);
-    // the coarse rank of mode 0 (coarse ratio > 0); coarse ratio == 0 is mode 1: no coarse patch
-    const int64_t k_c = coarse_ratio > 0.0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0;
-    CGIC_REQUIRE(k_c >= 0 && k_c <= n16, CGIC_ERR_INVALID, "rate_curve: k_coarse=%lld of %lld", (long long)k_c, (long long)n16);
-    const size_t need = cgic_rate_curve_workspace_bytes(B > 0 ? B : 1, h16, w16);
-    CGIC_REQUIRE(workspace, CGIC_ERR_INVALID, "rate_curve: workspace of %zu bytes required (cgic_rate_curve_workspace_bytes)", need);
-    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "rate_curve: the workspace must be 16-byte aligned");
-    if (B == 0) return CGIC_OK;
-    TableDev tab;
-    int rc = table_device_view(t, &tab);
-    if (rc) return rc;
+    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && nbytes, CGIC_ERR_INVALID, "%s: NULL argument", who);
+    int64_t k_c;
+    int rc;
+    if ((rc = curve_setup_check(who, t, coarse_ratio, true))) return rc;
+    CGIC_REQUIRE(B >= 0, CGIC_ERR_INVALID, "%s: bad shape", who);
+    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "%s: batch %lld exceeds the grid limit", who, (long long)B);
+    if ((rc = curve_shape_check(who, -1, h16, w16, coarse_ratio, &k_c))) return rc;
+    if ((rc = curve_workspace_check(who, workspace, cgic_rate_curve_workspace_bytes(B > 0 ? B : 1, h16, w16)))) return rc;
+    if (B == 0) return CGIC_OK;                      // (an empty batch is not an error here; cgic_route_to_budget has nothing to pick from)
 
     RateCurveArgs a;
-    a.len = tab.len; a.nsym = nsym;
-    const size_t words = (size_t)n8 * 12;
-    a.staged = words + (size_t)nsym * sizeof(int32_t) <= kCurveLdsBudget;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
-    a.h16 = (int)h16; a.w16 = (int)w16;
-    a.k_c = (int)k_c;
-    a.streams = cgic_mode_streams(coarse_ratio > 0.0 ? 0 : 1);
+    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)k_c;
     a.nbytes = nbytes;
     a.summary = reinterpret_cast<int32_t *>(workspace);
-    const size_t lds = words + (a.staged ? (size_t)nsym * sizeof(int32_t) : 0);
-    if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_curve_kernel, lds); if (rc) return rc; }
-    // one comparator per thread and pass while the image is small; whole waves
-    int threads = kCurveThreads;
-    while (threads > 256 && threads >= n8) threads >>= 1;
-    hipLaunchKernelGGL(rate_curve_kernel, dim3((unsigned)B), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
-    return launch_check("rate_curve_kernel");
-}
-
-static size_t tiles_summary_bytes(int64_t T)
-{
-    return (((size_t)T * kCurveSummary * sizeof(int32_t)) + 255) & ~(size_t)255;
+    return curve_launch(rate_curve_kernel, "rate_curve_kernel", t, coarse_ratio, B, 4 * h16 * w16, a, (hipStream_t)stream);
 }
 
 extern "C" size_t cgic_rate_curve_tiles_workspace_bytes(int64_t T, int64_t M, int tile_nbytes_given)
 {
     if (T <= 0 || M <= 0 || T > kTilesMaxTiles || M > kTilesMaxSettings) return 0;
-    return tiles_summary_bytes(T) + (tile_nbytes_given ? 0 : (size_t)T * (size_t)M * CGIC_NUM_STREAMS * sizeof(int32_t));
+    return summary_slab(T) + (tile_nbytes_given ? 0 : (size_t)T * (size_t)M * CGIC_NUM_STREAMS * sizeof(int32_t));
 }
 
 extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
@@ -620,21 +665,19 @@ extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, 
                                      const int32_t *ranks_dev, int64_t S, int64_t M, int64_t *image_nbytes, int32_t *tile_nbytes,
                                      void *workspace, cgic_stream_t stream)
 {
+    static const char who[] = "rate_curve_tiles";
     CGIC_NOT_IN_GROUP("cgic_rate_curve_tiles");
     CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && count && tiles && tiles_dev && ranks_dev && image_nbytes, CGIC_ERR_INVALID,
-                 "rate_curve_tiles: NULL argument");
+                 "%s: NULL argument", who);
     CGIC_REQUIRE(T >= 0 && N >= 1 && S >= 1 && M >= 1, CGIC_ERR_INVALID, "rate_curve_tiles: bad counts (T=%lld, N=%lld, S=%lld, M=%lld)",
                  (long long)T, (long long)N, (long long)S, (long long)M);
-    CGIC_REQUIRE(coarse_ratio >= 0.0 && coarse_ratio <= 1.0, CGIC_ERR_INVALID, "rate_curve_tiles: coarse ratio %g outside [0, 1]", coarse_ratio);
+    int rc;
+    if ((rc = curve_setup_check(who, t, coarse_ratio, true))) return rc;
     CGIC_REQUIRE(T <= kTilesMaxTiles && N <= kTilesMaxTiles, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tiles of %lld images exceed the grid limit (%d)",
                  (long long)T, (long long)N, kTilesMaxTiles);
     CGIC_REQUIRE(S <= kTilesMaxShapes, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tile shapes (at most %d)", (long long)S, kTilesMaxShapes);
     CGIC_REQUIRE(M <= kTilesMaxSettings, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld settings (at most %d)", (long long)M, kTilesMaxSettings);
     for (int i = 0; i < 5; ++i) CGIC_REQUIRE(count[i] >= 0, CGIC_ERR_INVALID, "rate_curve_tiles: negative element count");
-    const int nsym = cgic_table_num_symbols(t);
-    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: table of %d symbols", nsym);
-    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: codes of up to %d bits (at most %d)",
-                 cgic_table_max_len(t), kCurveMaxLen);
     // every descriptor: its shape fits one workgroup, its class has ONE shape, its coarse rank is the one cgic_rate_curve takes,
     // and its five parts lie inside the buffers
     int64_t class_h[kTilesMaxShapes], class_w[kTilesMaxShapes];
@@ -643,19 +686,16 @@ extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, 
     for (int64_t i = 0; i < T; ++i) {
         const cgic_rate_tile &d = tiles[i];
         const int64_t h16 = d.h16, w16 = d.w16;
-        CGIC_REQUIRE(h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: bad shape", (long long)i);
-        CGIC_REQUIRE(4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
-                     "rate_curve_tiles: tile %lld of %lld 8x8 patches does not fit one workgroup's LDS (at most %lld: 768x1024 pixels)",
-                     (long long)i, (long long)(4 * h16 * w16), (long long)kCurveMaxN8);
+        int64_t k_c;
+        if ((rc = curve_shape_check(who, i, h16, w16, coarse_ratio, &k_c))) return rc;
         const int64_t n16 = h16 * w16, n8 = 4 * n16;
         CGIC_REQUIRE(d.shape >= 0 && d.shape < S && d.image >= 0 && d.image < N && d.reserved == 0, CGIC_ERR_INVALID,
                      "rate_curve_tiles: tile %lld: shape class %d of %lld, image %d of %lld", (long long)i, d.shape, (long long)S, d.image, (long long)N);
         if (class_h[d.shape] == 0) { class_h[d.shape] = h16; class_w[d.shape] = w16; }
         CGIC_REQUIRE(class_h[d.shape] == h16 && class_w[d.shape] == w16, CGIC_ERR_INVALID,
                      "rate_curve_tiles: tile %lld: shape class %d holds tiles of two shapes", (long long)i, d.shape);
-        const int64_t k_c = coarse_ratio > 0.0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0;
-        CGIC_REQUIRE(d.k_c == k_c && k_c >= 0 && k_c <= n16, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: k_coarse=%d, the ratio gives %lld of %lld",
-                     (long long)i, d.k_c, (long long)k_c, (long long)n16);
+        CGIC_REQUIRE(d.k_c == k_c, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: k_coarse=%d, the ratio gives %lld of %lld", (long long)i, d.k_c,
+                     (long long)k_c, (long long)n16);
         const int64_t off[5] = {d.off_c, d.off_m, d.off_f, d.off_e16, d.off_e8};
         const int64_t len[5] = {n16, n8, 4 * n8, n16, n8};
         for (int k = 0; k < 5; ++k)
@@ -664,38 +704,18 @@ extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, 
                          (long long)off[k], (long long)len[k], (long long)count[k]);
         if (n8 > n8_max) n8_max = n8;
     }
-    const size_t need = cgic_rate_curve_tiles_workspace_bytes(T > 0 ? T : 1, M, tile_nbytes != nullptr);
-    CGIC_REQUIRE(workspace, CGIC_ERR_INVALID, "rate_curve_tiles: workspace of %zu bytes required (cgic_rate_curve_tiles_workspace_bytes)", need);
-    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "rate_curve_tiles: the workspace must be 16-byte aligned");
-    TableDev tab;
-    int rc = table_device_view(t, &tab);
-    if (rc) return rc;
+    if ((rc = curve_workspace_check(who, workspace, cgic_rate_curve_tiles_workspace_bytes(T > 0 ? T : 1, M, tile_nbytes != nullptr)))) return rc;
 
     RateTilesArgs a;
-    a.len = tab.len; a.nsym = nsym;
-    const size_t words = (size_t)n8_max * 12;
-    a.staged = words + (size_t)nsym * sizeof(int32_t) <= kCurveLdsBudget;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
     a.tiles = tiles_dev; a.ranks = ranks_dev; a.M = (int)M;
-    a.streams = cgic_mode_streams(coarse_ratio > 0.0 ? 0 : 1);
     a.summary = reinterpret_cast<int32_t *>(workspace);
-    a.tile_nbytes = tile_nbytes ? tile_nbytes
-                                : reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + tiles_summary_bytes(T > 0 ? T : 1));
-    if (T > 0) {
-        const size_t lds = words + (a.staged ? (size_t)nsym * sizeof(int32_t) : 0);
-        if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_curve_tiles_kernel, lds); if (rc) return rc; }
-        int threads = kCurveThreads;                 // (sized by the largest tile; the results do not depend on it)
-        while (threads > 256 && threads >= n8_max) threads >>= 1;
-        hipLaunchKernelGGL(rate_curve_tiles_kernel, dim3((unsigned)T), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
-        rc = launch_check("rate_curve_tiles_kernel");
-        if (rc) return rc;
-    }
+    a.tile_nbytes = tile_nbytes ? tile_nbytes : reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + summary_slab(T > 0 ? T : 1));
+    if (T > 0 && (rc = curve_launch(rate_curve_tiles_kernel, "rate_curve_tiles_kernel", t, coarse_ratio, T, n8_max, a, (hipStream_t)stream))) return rc;
     hipLaunchKernelGGL(rate_fold_tiles_kernel, dim3((unsigned)((M + kFoldThreads - 1) / kFoldThreads), (unsigned)N), dim3(kFoldThreads), 0,
                        (hipStream_t)stream, tiles_dev, (int)T, (int)M, (const int32_t *)a.tile_nbytes, image_nbytes);
     return launch_check("rate_fold_tiles_kernel");
 }
-
-static size_t route_slab(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 extern "C" size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int64_t R)
 {
@@ -703,7 +723,7 @@ extern "C" size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, i
         || R > 4 * h16 * w16 + 1)
         return 0;
     // the per-image summary, then per image and requested rank the bytes (int32) and the medium threshold's key (uint32)
-    return route_slab((size_t)B * kCurveSummary * sizeof(int32_t)) + 2 * route_slab((size_t)B * (size_t)R * sizeof(int32_t));
+    return summary_slab(B) + 2 * slab((size_t)B * (size_t)R * sizeof(int32_t));
 }
 
 extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
@@ -711,70 +731,46 @@ extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, c
                                     const int32_t *ranks_dev, int64_t R, const int64_t *budget_dev, int32_t *mask_c, int32_t *mask_m,
                                     int32_t *mask_f, int64_t *ind, int64_t *choice_dev, void *workspace, cgic_stream_t stream)
 {
+    static const char who[] = "route_to_budget";
     CGIC_NOT_IN_GROUP("cgic_route_to_budget");
     CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && ranks_dev && budget_dev && mask_c && mask_m && mask_f && ind && choice_dev,
-                 CGIC_ERR_INVALID, "route_to_budget: NULL argument");
-    CGIC_REQUIRE(B >= 1 && h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "route_to_budget: bad shape");
-    CGIC_REQUIRE(coarse_ratio >= 0.0 && coarse_ratio < 1.0, CGIC_ERR_INVALID,
-                 "route_to_budget: coarse ratio %g outside [0, 1): the curve's mode is 0, or 1 at coarse ratio 0", coarse_ratio);
-    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "route_to_budget: batch %lld exceeds the grid limit", (long long)B);
-    CGIC_REQUIRE(h16 <= kCurveMaxN8 && w16 <= kCurveMaxN8 && 4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
-                 "route_to_budget: an image of %lld 8x8 patches does not fit one workgroup's LDS (at most %lld: 768x1024 pixels)",
-                 (long long)(4 * h16 * w16), (long long)kCurveMaxN8);
-    const int64_t n16 = h16 * w16, n8 = 4 * n16;
+                 CGIC_ERR_INVALID, "%s: NULL argument", who);
+    int64_t k_c;
+    int rc;
+    if ((rc = curve_setup_check(who, t, coarse_ratio, false))) return rc;       // (coarse ratio 1 leaves the curve's mode)
+    CGIC_REQUIRE(B >= 1, CGIC_ERR_INVALID, "%s: bad shape", who);           // (no image: nothing to pick from)
+    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "%s: batch %lld exceeds the grid limit", who, (long long)B);
+    if ((rc = curve_shape_check(who, -1, h16, w16, coarse_ratio, &k_c))) return rc;
+    const int64_t n8 = 4 * h16 * w16;
     CGIC_REQUIRE(R >= 1 && R <= n8 + 1, CGIC_ERR_INVALID, "route_to_budget: %lld requested ranks (1 .. %lld)", (long long)R, (long long)(n8 + 1));
-    const int nsym = cgic_table_num_symbols(t);
-    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "route_to_budget: table of %d symbols", nsym);
-    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "route_to_budget: codes of up to %d bits (at most %d)",
-                 cgic_table_max_len(t), kCurveMaxLen);
-    const int mode = coarse_ratio > 0.0 ? 0 : 1;
-    const int64_t k_c = mode == 0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0;
-    CGIC_REQUIRE(k_c >= 0 && k_c <= n16, CGIC_ERR_INVALID, "route_to_budget: k_coarse=%lld of %lld", (long long)k_c, (long long)n16);
-    const size_t need = cgic_route_to_budget_workspace_bytes(B, h16, w16, R);
-    CGIC_REQUIRE(need > 0 && workspace, CGIC_ERR_INVALID, "route_to_budget: workspace of %zu bytes required (cgic_route_to_budget_workspace_bytes)", need);
-    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "route_to_budget: the workspace must be 16-byte aligned");
+    if ((rc = curve_workspace_check(who, workspace, cgic_route_to_budget_workspace_bytes(B, h16, w16, R)))) return rc;
     CGIC_REQUIRE((((uintptr_t)ind_m | (uintptr_t)ind_f | (uintptr_t)mask_m | (uintptr_t)mask_f | (uintptr_t)ind) & 15u) == 0 && ((uintptr_t)e8 & 7u) == 0
                      && ((uintptr_t)budget_dev & 7u) == 0 && ((uintptr_t)choice_dev & 7u) == 0,
                  CGIC_ERR_INVALID, "route_to_budget: ind_m, ind_f, mask_m, mask_f and ind must be 16-byte aligned, e8, the budget and the choice 8-byte aligned");
-    TableDev tab;
-    int rc = table_device_view(t, &tab);
-    if (rc) return rc;
 
     unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
-    const size_t per_rank = route_slab((size_t)B * (size_t)R * sizeof(int32_t));
     RateRanksArgs a;
-    a.len = tab.len; a.nsym = nsym;
-    const size_t words = (size_t)n8 * 12;
-    a.staged = words + (size_t)nsym * sizeof(int32_t) <= kCurveLdsBudget;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
-    a.h16 = (int)h16; a.w16 = (int)w16;
-    a.k_c = (int)k_c;
-    a.streams = cgic_mode_streams(mode);
+    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)k_c;
     a.ranks = ranks_dev; a.R = (int)R;
     a.summary = reinterpret_cast<int32_t *>(ws);
-    a.total = reinterpret_cast<int32_t *>(ws + route_slab((size_t)B * kCurveSummary * sizeof(int32_t)));
-    a.tkey = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(a.total) + per_rank);
-    const size_t lds = words + (a.staged ? (size_t)nsym * sizeof(int32_t) : 0);
-    if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_curve_ranks_kernel, lds); if (rc) return rc; }
-    int threads = kCurveThreads;
-    while (threads > 256 && threads >= n8) threads >>= 1;
-    hipLaunchKernelGGL(rate_curve_ranks_kernel, dim3((unsigned)B), dim3((unsigned)threads), lds, (hipStream_t)stream, a);
-    rc = launch_check("rate_curve_ranks_kernel");
-    if (rc) return rc;
+    a.total = reinterpret_cast<int32_t *>(ws + summary_slab(B));
+    a.tkey = reinterpret_cast<uint32_t *>(ws + summary_slab(B) + slab((size_t)B * (size_t)R * sizeof(int32_t)));
+    if ((rc = curve_launch(rate_curve_ranks_kernel, "rate_curve_ranks_kernel", t, coarse_ratio, B, n8, a, (hipStream_t)stream))) return rc;
 
     hipLaunchKernelGGL(rate_pick_kernel, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, (const int32_t *)a.total, ranks_dev, (int)B, (int)R,
                        budget_dev, choice_dev);
     rc = launch_check("rate_pick_kernel");
     if (rc) return rc;
 
-    RateApplyArgs p;
-    p.choice = choice_dev; p.tkey = a.tkey; p.summary = a.summary;
-    p.ind_c = ind_c; p.ind_m = ind_m; p.ind_f = ind_f; p.e16 = e16; p.e8 = e8;
-    p.B = (int)B; p.h16 = (int)h16; p.w16 = (int)w16; p.R = (int)R;
-    p.mc = mask_c; p.mm = mask_m; p.mf = mask_f; p.ind = ind;
+    RateApplyArgs q;
+    q.choice = choice_dev; q.tkey = a.tkey; q.summary = a.summary;
+    q.ind_c = ind_c; q.ind_m = ind_m; q.ind_f = ind_f; q.e16 = e16; q.e8 = e8;
+    q.B = (int)B; q.h16 = (int)h16; q.w16 = (int)w16; q.R = (int)R;
+    q.mc = mask_c; q.mm = mask_m; q.mf = mask_f; q.ind = ind;
     const int64_t rows = B * 4 * h16 * w16;
     int64_t grid = (rows + kApplyThreads - 1) / kApplyThreads;
     if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL(rate_apply_kernel, dim3((unsigned)grid), dim3(kApplyThreads), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(rate_apply_kernel, dim3((unsigned)grid), dim3(kApplyThreads), 0, (hipStream_t)stream, q);
     return launch_check("rate_apply_kernel");
 }

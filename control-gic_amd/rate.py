@@ -82,38 +82,11 @@ def default_candidates(coarse_ratio, n=16):
     return [(c, top * i / (n - 1) if i < n - 1 else top) for i in range(n)]
 
 
-class RateTable:
-    """rate_table's result: per candidate and image the sizes of the five .bin streams.
-    nbytes int32 [C,B,5] (0 = not written), bytes int64 [C,B], bpp float64 [C,B] (bytes * 8 / pixels, model.py:233),
-    batch_bpp float64 [C] (all bits of the batch over all its pixels); candidates: the (coarse, medium) list, modes: their modes"""
-
-    def __init__(self, nbytes, candidates, num_pixels):
-        self.nbytes = nbytes
-        self.candidates = list(candidates)
-        self.num_pixels = int(num_pixels)
-        self.modes = [int(_lib.lib().cgic_router_mode(c, m)) for c, m in self.candidates]
-        nb = nbytes.detach().cpu()
-        if int(nb.min()) < 0:
-            raise KeyError("rate_table: an index is not in the code table")
-        self.bytes = nb.to(torch.int64).sum(dim=2)
-        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
-        B = self.bytes.shape[1]
-        self.batch_bpp = self.bytes.sum(dim=1).to(torch.float64) * 8 / (self.num_pixels * B)
-
-
-def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, pixels=None, flat8=None):
-    """exact sizes of the streams GrainCodec.compress would write after routing at each candidate (coarse, medium) ratio
-    (cgic_rate_table).  ind_*: grain_indices(...); e16 / e8: the entropy maps; pixels: the image batch behind them (fp32
-    [B,3,H,W] or uint8 [B,H,W,3]) for the router's threshold-band refinement -- taken from the maps' tags when they come from
-    control_gic_amd.Entropy / entropy_maps, like the router does.  per_image as the router's.  -> RateTable"""
-    cand = _check_candidates(candidates)
+def _curve_inputs(ind_c, ind_m, ind_f, e16, e8):
+    """the input contract of every rate call: everything on one device, the maps as contiguous fp32 [B, h16, w16] and
+    [B, 2 h16, 2 w16], the grain indices int64 with the element counts of the three grids
+    -> ([ind_c, ind_m, ind_f] contiguous, e16, e8, (B, h16, w16))"""
     _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
-    explicit = pixels is not None
-    if pixels is None:
-        p16, p8 = getattr(e16, "_cgic_pixels", None), getattr(e8, "_cgic_pixels", None)
-        pixels = p16 if (p16 is not None and p16 is p8) else None
-    if flat8 is None and pixels is not None:
-        flat8 = _flat_of(pixels, e8, e16)
     e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
     B, h16, w16 = e16c.shape
     if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
@@ -124,6 +97,56 @@ def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, 
         if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
             raise ValueError(f"grain indices must be int64 with shapes {want}")
         inds.append(t.contiguous())
+    return inds, e16c, e8c, (B, h16, w16)
+
+
+class _Rates:
+    """what the four results share: bytes (the five streams summed), bpp = bytes * 8 / num_pixels, batch_bpp (all bits of the batch
+    over all its pixels), with the images along `image_axis` of bytes; who: the caller's name for the KeyError of a negative entry
+    (a symbol outside the code table), None: the entries were checked before"""
+
+    def _set_rates(self, nbytes, num_pixels, image_axis, who):
+        self.num_pixels = int(num_pixels)
+        self._image_axis = image_axis
+        nb = nbytes.detach().cpu()
+        if who is not None and nb.numel() and int(nb.min()) < 0:
+            raise KeyError(f"{who}: an index is not in the code table")
+        self.bytes = nb.to(torch.int64).sum(dim=2)
+        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
+        B = self.bytes.shape[image_axis]
+        self.batch_bpp = self.bytes.sum(dim=image_axis).to(torch.float64) * 8 / (self.num_pixels * max(B, 1))
+
+    def _choices(self):
+        """for choose: (batch_bpp of each candidate, per image the bpp of each candidate, candidate index -> what choose returns)"""
+        return self.batch_bpp, (self.bpp.t() if self._image_axis == 1 else self.bpp), int
+
+
+class RateTable(_Rates):
+    """rate_table's result: per candidate and image the sizes of the five .bin streams.
+    nbytes int32 [C,B,5] (0 = not written), bytes int64 [C,B], bpp float64 [C,B] (bytes * 8 / pixels, model.py:233),
+    batch_bpp float64 [C] (all bits of the batch over all its pixels); candidates: the (coarse, medium) list, modes: their modes"""
+    _who = "rate_table"                              # the name in the KeyError of a negative entry (None: not checked)
+
+    def __init__(self, nbytes, candidates, num_pixels):
+        self.nbytes = nbytes
+        self.candidates = list(candidates)
+        self.modes = [int(_lib.lib().cgic_router_mode(c, m)) for c, m in self.candidates]
+        self._set_rates(nbytes, num_pixels, 1, self._who)
+
+
+def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, pixels=None, flat8=None):
+    """exact sizes of the streams GrainCodec.compress would write after routing at each candidate (coarse, medium) ratio
+    (cgic_rate_table).  ind_*: grain_indices(...); e16 / e8: the entropy maps; pixels: the image batch behind them (fp32
+    [B,3,H,W] or uint8 [B,H,W,3]) for the router's threshold-band refinement -- taken from the maps' tags when they come from
+    control_gic_amd.Entropy / entropy_maps, like the router does.  per_image as the router's.  -> RateTable"""
+    cand = _check_candidates(candidates)
+    inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
+    explicit = pixels is not None
+    if pixels is None:
+        p16, p8 = getattr(e16, "_cgic_pixels", None), getattr(e8, "_cgic_pixels", None)
+        pixels = p16 if (p16 is not None and p16 is p8) else None
+    if flat8 is None and pixels is not None:
+        flat8 = _flat_of(pixels, e8, e16)
     dev = e16c.device
     C = len(cand)
     cr = (ctypes.c_double * C)(*[c for c, _ in cand])
@@ -175,13 +198,10 @@ def ratio_for_rank(K, n16, coarse_ratio):
 
 @functools.lru_cache(maxsize=64)
 def reachable_ranks(n16, coarse_ratio):
-    """((K, medium ratio), ...) for every medium rank K in 0 .. n8 a ratio reaches at this coarse ratio (ratio_for_rank)"""
-    out = []
-    for K in range(4 * int(n16) + 1):
-        m = ratio_for_rank(K, n16, coarse_ratio)
-        if m is not None:
-            out.append((K, m))
-    return tuple(out)
+    """((K, medium ratio), ...) for every medium rank K in 0 .. n8 a ratio reaches at this coarse ratio: what ratio_for_rank
+    returns for each K, from the one search over all of them (reachable_ranks_vec)"""
+    K, m = reachable_ranks_vec(n16, coarse_ratio)
+    return tuple(zip(K.tolist(), m.tolist()))
 
 
 def _curve_ranks_vec(coarse_ratio, mediums, n16):
@@ -199,9 +219,9 @@ def _curve_ranks_vec(coarse_ratio, mediums, n16):
 
 @functools.lru_cache(maxsize=64)
 def reachable_ranks_vec(n16, coarse_ratio):
-    """reachable_ranks as tensors, every rank searched at once -> (K int64 [R], medium float64 [R]): ratio_for_rank's search (start
-    at (K - 4 n16 c) / n8, step one float64 at a time towards the rank) on all n8 + 1 ranks in lockstep.  A 768x768 tile has 9217
-    ranks: the loop's two foreign calls per step become a handful of tensor operations"""
+    """every rank searched at once -> (K int64 [R], medium float64 [R]): ratio_for_rank's search (start at (K - 4 n16 c) / n8, step
+    one float64 at a time towards the rank) on all n8 + 1 ranks in lockstep, pinned to it bit for bit by a test.  A 768x768 tile
+    has 9217 ranks: a loop over ratio_for_rank makes two foreign calls per step, this a handful of tensor operations"""
     n16, c = int(n16), float(coarse_ratio)
     n8 = 4 * n16
     tiny = math.nextafter(0.0, 1.0)
@@ -257,7 +277,7 @@ def _tiled_settings(shapes, c):
     return m, ranks
 
 
-class RateCurve:
+class RateCurve(_Rates):
     """rate_curve's result: per image and medium rank K = 0 .. n8 the sizes of the five .bin streams at one coarse ratio.
     nbytes int32 [B,n8+1,5] (0 = not written), bytes int64 [B,n8+1], bpp float64 [B,n8+1], batch_bpp float64 [n8+1];
     ranks: the K a medium ratio reaches (ascending), candidates: the (coarse, medium) pair of each, rank by rank, modes: their
@@ -268,16 +288,9 @@ class RateCurve:
     def __init__(self, nbytes, coarse_ratio, num_pixels, ranks=None, n_coarse=None):
         self.nbytes = nbytes
         self.coarse_ratio = float(coarse_ratio)
-        self.num_pixels = int(num_pixels)
-        nb = nbytes.detach().cpu()
-        if int(nb.min()) < 0:
-            raise KeyError("rate_curve: an index is not in the code table")
-        self.bytes = nb.to(torch.int64).sum(dim=2)
-        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
-        B, nk = self.bytes.shape
-        self.batch_bpp = self.bytes.sum(dim=0).to(torch.float64) * 8 / (self.num_pixels * max(B, 1))
+        self._set_rates(nbytes, num_pixels, 0, "rate_curve")
         if ranks is None:
-            ranks = reachable_ranks((nk - 1) // 4, self.coarse_ratio)
+            ranks = reachable_ranks((self.bytes.shape[1] - 1) // 4, self.coarse_ratio)
         self.ranks = [int(k) for k, _ in ranks]
         self.candidates = [(self.coarse_ratio, float(m)) for _, m in ranks]
         self.modes = [0 if self.coarse_ratio > 0.0 else 1] * len(self.ranks)
@@ -287,23 +300,18 @@ class RateCurve:
         """the (coarse, medium) pair that reaches rank K"""
         return self.candidates[self.ranks.index(int(K))]
 
+    def _choices(self):
+        # among the ranks a ratio reaches; choose returns the rank
+        sel = torch.tensor(self.ranks, dtype=torch.int64)
+        return self.batch_bpp[sel], self.bpp[:, sel], self.ranks.__getitem__
+
 
 def rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, ranks=None):
     """exact sizes of the streams GrainCodec.compress would write for EVERY medium rank at `coarse_ratio`, every image routed on
     its own thresholds on the maps as given (cgic_rate_curve; no threshold-band refinement: maps of
     entropy_maps(x, reference_order=True) make that the reference's routing from the pixels).  Arguments as rate_table's;
     ranks: ((K, medium ratio), ...) to carry instead of reachable_ranks(n16, coarse_ratio).  -> RateCurve"""
-    _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
-    e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
-    B, h16, w16 = e16c.shape
-    if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
-        raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
-    want = ((B, h16, w16), (B, 2 * h16, 2 * w16), (B, 4 * h16, 4 * w16))
-    inds = []
-    for t, shp in zip((ind_c, ind_m, ind_f), want):
-        if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
-            raise ValueError(f"grain indices must be int64 with shapes {want}")
-        inds.append(t.contiguous())
+    inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
     dev = e16c.device
     n8 = 4 * h16 * w16
     nbytes = torch.empty((B, n8 + 1, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
@@ -410,17 +418,7 @@ def route_to_bpp(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, target_bpp=N
     element, the byte budget of the batch (budget_bytes), used as it is -- a captured graph is replayed with a new target by
     writing into it; else it is made from target_bpp.  The call does not synchronise and copies nothing to the host.
     -> BppRoute"""
-    _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
-    e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
-    B, h16, w16 = e16c.shape
-    if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
-        raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
-    want = ((B, h16, w16), (B, 2 * h16, 2 * w16), (B, 4 * h16, 4 * w16))
-    inds = []
-    for t, shp in zip((ind_c, ind_m, ind_f), want):
-        if t.dtype != torch.int64 or t.numel() != shp[0] * shp[1] * shp[2]:
-            raise ValueError(f"grain indices must be int64 with shapes {want}")
-        inds.append(t.contiguous())
+    inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
     dev = e16c.device
     c = float(coarse_ratio)
     if (target_bpp is None) == (budget is None):
@@ -469,7 +467,7 @@ def gather_grain_indices(ind_c, ind_m, ind_f, masks):
     return out
 
 
-class TiledRateCurve:
+class TiledRateCurve(_Rates):
     """rate_curve_tiled's result: per image and setting j of the medium axis the sizes of the five .bin streams, summed over the
     image's tiles, at one coarse ratio.  mediums float64 [M] (ascending), ranks int64 [S, M] (the medium rank of shape class s at
     setting j), shapes [(h16, w16)] per class; nbytes int64 [N, M, 5], bytes int64 [N, M], bpp float64 [N, M] (bits over the
@@ -480,32 +478,21 @@ class TiledRateCurve:
 
     def __init__(self, image_nbytes, tile_nbytes, coarse_ratio, mediums, ranks, shapes, num_pixels, tile_shape=None, tile_image=None):
         self.coarse_ratio = float(coarse_ratio)
-        self.num_pixels = int(num_pixels)
         self.mediums = torch.as_tensor(mediums, dtype=torch.float64)
         self.ranks = torch.as_tensor(ranks, dtype=torch.int64)
         self.shapes = list(shapes)
         self.tile_nbytes, self.tile_shape, self.tile_image = tile_nbytes, tile_shape, tile_image
         self.nbytes = image_nbytes.detach().cpu()
-        if self.nbytes.numel() and int(self.nbytes.min()) < 0:
-            raise KeyError("rate_curve_tiled: an index is not in the code table")
-        self.bytes = self.nbytes.sum(dim=2)
-        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
-        N = self.bytes.shape[0]
-        self.batch_bpp = self.bytes.sum(dim=0).to(torch.float64) * 8 / (self.num_pixels * max(N, 1))
+        self._set_rates(self.nbytes, num_pixels, 0, "rate_curve_tiled")
         self.candidates = [(self.coarse_ratio, m) for m in self.mediums.tolist()]
         self.modes = [0 if self.coarse_ratio > 0.0 else 1] * len(self.candidates)
         self.ends = None
 
 
-class _FoldedEnds:
-    """the ends of a tiled image's medium axis: per-group rate tables folded per image (fields as RateTable's, nbytes [C, N, 5])"""
-
-    def __init__(self, nbytes, candidates, num_pixels):
-        self.nbytes, self.candidates, self.num_pixels = nbytes, list(candidates), int(num_pixels)
-        self.modes = [int(_lib.lib().cgic_router_mode(c, m)) for c, m in self.candidates]
-        self.bytes = nbytes.sum(dim=2)
-        self.bpp = self.bytes.to(torch.float64) * 8 / self.num_pixels
-        self.batch_bpp = self.bytes.sum(dim=1).to(torch.float64) * 8 / (self.num_pixels * max(nbytes.shape[1], 1))
+class _FoldedEnds(RateTable):
+    """the ends of a tiled image's medium axis: per-group rate tables folded per image on the host (nbytes int64 [C, N, 5]; their
+    entries were checked group by group)"""
+    _who = None
 
 
 def _tile_groups(tiles):
@@ -514,16 +501,7 @@ def _tile_groups(tiles):
         if isinstance(g, dict):
             g = (g["ind_c"], g["ind_m"], g["ind_f"], g["e16"], g["e8"], g["images"])
         ind_c, ind_m, ind_f, e16, e8, images = g
-        _lib.require_device(ind_c, ind_m, ind_f, e16, e8)
-        e16c, e8c = e16.contiguous().float(), e8.contiguous().float()
-        B, h16, w16 = e16c.shape
-        if tuple(e8c.shape) != (B, 2 * h16, 2 * w16):
-            raise ValueError(f"e8 {tuple(e8.shape)} must be [B, 2*h16, 2*w16] of {tuple(e16.shape)}")
-        inds = []
-        for t, n in zip((ind_c, ind_m, ind_f), (B * h16 * w16, 4 * B * h16 * w16, 16 * B * h16 * w16)):
-            if t.dtype != torch.int64 or t.numel() != n:
-                raise ValueError("grain indices must be int64 on the three grids of the group's maps")
-            inds.append(t.contiguous())
+        inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
         images = [int(i) for i in images]
         if len(images) != B or (images and min(images) < 0):
             raise ValueError(f"a group of {B} tiles names the image of {len(images)}")
@@ -609,11 +587,39 @@ def rate_curve_tiled(codec, tiles, coarse_ratio, image_hw=None, settings=None, e
     return curve
 
 
-def _pick_tiled(curve, target_bpp):
-    """over the settings of the curve and its two ends -> (index into curve.candidates + curve.ends.candidates, fits)"""
-    cand = curve.candidates + (curve.ends.candidates if curve.ends is not None else [])
-    bb = curve.batch_bpp.tolist() + (curve.ends.batch_bpp.tolist() if curve.ends is not None else [])
-    return _pick(bb, cand, float(target_bpp)), cand
+def _pick_with_ends(curve, target_bpp):
+    """_pick over the entries of a curve (RateCurve: the ranks a ratio reaches, TiledRateCurve: its settings) and the two ends of
+    its axis (curve.ends) -> (index into cand, fits, cand = curve.candidates + curve.ends.candidates)"""
+    ends = getattr(curve, "ends", None)
+    cand = curve.candidates + (ends.candidates if ends is not None else [])
+    bb = curve._choices()[0].tolist() + (ends.batch_bpp.tolist() if ends is not None else [])
+    return (*_pick(bb, cand, float(target_bpp)), cand)
+
+
+def _encode_captured(model, x, entropy=False):
+    """one model.encode(x) with per-image routing forced in the router config and forward hooks on the three encoder heads
+    (entropy=True: on the two entropy modules as well); config and hooks are restored whatever encode does
+    -> {"c", "m", "f"[, "e8", "e16"]: that module's output}"""
+    enc = model.encoder
+    params = enc.router_config["params"]
+    mods = {"c": enc.conv_out_coarse, "m": enc.conv_out, "f": enc.conv_out_fine}
+    if entropy:
+        mods.update(e8=model.entropy_calculation_p8, e16=model.entropy_calculation_p16)
+    got = {}
+    hooks = [mod.register_forward_hook(lambda mod, args, out, name=name: got.__setitem__(name, out)) for name, mod in mods.items()]
+    saved = params.get("per_image", None)
+    params["per_image"] = True
+    try:
+        with torch.no_grad():
+            model.encode(x)
+    finally:
+        for hk in hooks:
+            hk.remove()
+        if saved is None:
+            params.pop("per_image", None)
+        else:
+            params["per_image"] = saved
+    return got
 
 
 def compress_tiled_to_bpp(model, x, target_bpp, tile=None, decode=None):
@@ -636,41 +642,19 @@ def compress_tiled_to_bpp(model, x, target_bpp, tile=None, decode=None):
     if q.training:
         raise RuntimeError("compress_tiled_to_bpp: the quantiser is in training mode; call model.eval() first")
     tile = highres.TILE if tile is None else int(tile)
-    enc = model.encoder
-    params = enc.router_config["params"]
-    coarse = float(params["coarse_grain_ratio"])
+    coarse = float(model.encoder.router_config["params"]["coarse_grain_ratio"])
     codec = _codec_for(model)
     N, H, W = x.shape[0], x.shape[2], x.shape[3]
     pad, grid, order, batches = highres.cut_groups(x, tile)
-    got, hooks = {}, []
-
-    def grab(name):
-        def hook(mod, args, out):
-            got[name] = out
-        return hook
-
-    for name, mod in (("c", enc.conv_out_coarse), ("m", enc.conv_out), ("f", enc.conv_out_fine)):
-        hooks.append(mod.register_forward_hook(grab(name)))
-    saved = params.get("per_image", None)
-    params["per_image"] = True
     groups = []
-    try:
-        with torch.no_grad():
-            for ((th, tw), idxs), batch in zip(order, batches):
-                model.encode(batch)
-                inds = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
-                e8, e16 = entropy_maps(batch, reference_order=True)
-                groups.append((*inds, e16, e8, [n for n in range(N) for _ in idxs]))
-    finally:
-        for hk in hooks:
-            hk.remove()
-        if saved is None:
-            params.pop("per_image", None)
-        else:
-            params["per_image"] = saved
     with torch.no_grad():
+        for (_, idxs), batch in zip(order, batches):
+            got = _encode_captured(model, batch)
+            inds = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
+            e8, e16 = entropy_maps(batch, reference_order=True)
+            groups.append((*inds, e16, e8, [n for n in range(N) for _ in idxs]))
         curve = rate_curve_tiled(codec, groups, coarse, image_hw=(H, W))
-        (c, fits), cand = _pick_tiled(curve, target_bpp)
+        c, fits, cand = _pick_with_ends(curve, target_bpp)
         cr, mr = cand[c]
         M = len(curve.candidates)
         curve.fits, curve.chosen = fits, (c if c < M else None)
@@ -707,32 +691,15 @@ def choose(table, target_bpp, per="batch"):
     curve is not monotone in K, so this is a search over all of them, not a bisection) or a TiledRateCurve (c = the index of
     the setting on its medium axis)"""
     target = float(target_bpp)
-    if isinstance(table, TiledRateCurve):
-        # c = the index of the setting (ties: the smaller medium ratio, as above)
-        if per == "batch":
-            return _pick(table.batch_bpp.tolist(), table.candidates, target)
-        if per == "image":
-            picks = [_pick(row.tolist(), table.candidates, target) for row in table.bpp]
-            return torch.tensor([c for c, _ in picks], dtype=torch.int64), torch.tensor([f for _, f in picks], dtype=torch.bool)
-        raise ValueError(f"choose: per={per!r}; 'batch' or 'image'")
-    curve = isinstance(table, RateCurve)
-    if curve:
-        if not table.ranks:
-            raise ValueError(f"choose: no medium ratio reaches a rank at coarse ratio {table.coarse_ratio}")
-        sel = torch.tensor(table.ranks, dtype=torch.int64)
-        batch_bpp, bpp = table.batch_bpp[sel], table.bpp[:, sel].t()
-    else:
-        batch_bpp, bpp = table.batch_bpp, table.bpp
+    if not table.candidates:
+        raise ValueError("choose: no candidate (a curve: no medium ratio reaches a rank at its coarse ratio)")
+    batch_bpp, image_bpp, value = table._choices()
     if per == "batch":
         c, f = _pick(batch_bpp.tolist(), table.candidates, target)
-        return (table.ranks[c] if curve else c), f
+        return value(c), f
     if per == "image":
-        cs, fs = [], []
-        for b in range(bpp.shape[1]):
-            c, f = _pick(bpp[:, b].tolist(), table.candidates, target)
-            cs.append(table.ranks[c] if curve else c)
-            fs.append(f)
-        return torch.tensor(cs, dtype=torch.int64), torch.tensor(fs, dtype=torch.bool)
+        picks = [_pick(row.tolist(), table.candidates, target) for row in image_bpp]
+        return torch.tensor([value(c) for c, _ in picks], dtype=torch.int64), torch.tensor([f for _, f in picks], dtype=torch.bool)
     raise ValueError(f"choose: per={per!r}; 'batch' or 'image'")
 
 
@@ -769,37 +736,13 @@ def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True, sear
     q = model.quantize
     if q.training:
         raise RuntimeError("compress_to_bpp: the quantiser is in training mode; call model.eval() first")
-    enc = model.encoder
-    rc = enc.router_config
-    params = rc["params"]
+    params = model.encoder.router_config["params"]
     if search == "candidates":
         if candidates is None:
             candidates = default_candidates(params["coarse_grain_ratio"])
         cand = _check_candidates(candidates)
     codec = _codec_for(model)
-    got = {}
-    hooks = []
-
-    def grab(name):
-        def hook(mod, args, out):
-            got[name] = out
-        return hook
-
-    for name, mod in (("c", enc.conv_out_coarse), ("m", enc.conv_out), ("f", enc.conv_out_fine),
-                      ("e8", model.entropy_calculation_p8), ("e16", model.entropy_calculation_p16)):
-        hooks.append(mod.register_forward_hook(grab(name)))
-    saved = params.get("per_image", None)
-    params["per_image"] = True
-    try:
-        with torch.no_grad():
-            model.encode(input)
-    finally:
-        for hk in hooks:
-            hk.remove()
-        if saved is None:
-            params.pop("per_image", None)
-        else:
-            params["per_image"] = saved
+    got = _encode_captured(model, input, entropy=search == "candidates")
     with torch.no_grad():
         ind_c, ind_m, ind_f = grain_indices(q, got["c"], got["m"], got["f"], getattr(model, "quant_conv", None))
         if search == "device":
@@ -817,9 +760,7 @@ def compress_to_bpp(model, input, target_bpp, candidates=None, decode=True, sear
             e8, e16 = entropy_maps(input, reference_order=True)
             table = rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse)
             table.ends = rate_table(codec, ind_c, ind_m, ind_f, e16, e8, _curve_ends(coarse), per_image=True)
-            cand = table.candidates + table.ends.candidates
-            bb = table.batch_bpp[torch.tensor(table.ranks, dtype=torch.int64)].tolist() + table.ends.batch_bpp.tolist()
-            c, fits = _pick(bb, cand, float(target_bpp))
+            c, fits, cand = _pick_with_ends(table, target_bpp)
             table.chosen_rank = table.ranks[c] if c < len(table.ranks) else None
         else:
             e16, e8 = got["e16"], got["e8"]

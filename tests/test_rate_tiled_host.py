@@ -52,7 +52,8 @@ def test_tiled_settings(hw, c):
 @pytest.mark.parametrize("n16", [1, 34, 96, 816, 1776, 2304])
 def test_vectorised_rank_search_equals_the_loop(n16, c):
     K, m = rate.reachable_ranks_vec(n16, c)
-    loop = rate.reachable_ranks(n16, c)
+    # the loop side: the scalar search (the specification), one rank at a time -- reachable_ranks is a view of the vectorised one
+    loop = [(k, v) for k in range(4 * n16 + 1) for v in [cg.ratio_for_rank(k, n16, c)] if v is not None]
     assert K.tolist() == [k for k, _ in loop]
     assert m.tolist() == [v for _, v in loop]                       # the same float64, bit for bit
     ok, k = rate._curve_ranks_vec(c, m, n16)
