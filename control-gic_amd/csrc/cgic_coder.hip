@@ -719,7 +719,7 @@ extern "C" int cgic_compress_streams(const cgic_table *t, const int64_t *ind, co
     a.parts[0] = a.parts[1] = a.parts[2] = 1;
     a.tick = nullptr;
     int64_t longest = 0;                  // positions the longest workgroup stages
-    const bool split = B * 6 <= (int64_t)(16384 / 4);
+    const bool split = B * 6 <= kTicketRequestMax;
     for (int g = 0; g < 3; ++g) {
         const int64_t npos = (h >> (2 - g)) * (w >> (2 - g));
         int64_t P = split && npos > kLdsPos ? (npos + kEncPartPos - 1) / kEncPartPos : 1;
@@ -758,17 +758,8 @@ extern "C" int cgic_compress_streams(const cgic_table *t, const int64_t *ind, co
         return launch_check("compress_streams_kernel"); });
 }
 
-static int compress_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
-{
-    Grouped<CompressArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    if (lds) { rc = ensure_dynamic_lds((const void *)compress_streams_grouped_kernel, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(compress_streams_grouped_kernel, dim3(g.start[kMaxGroups]), dim3(kEncThreads), lds, s, g);
-    return launch_check("compress_streams_grouped_kernel");
-}
-static GroupedRegistrar reg_compress(KID_COMPRESS, compress_grouped_launch);
+static GroupedRegistrar reg_compress(KID_COMPRESS, [](const GroupRec *const *recs, int n, hipStream_t s) {
+    return launch_grouped(compress_streams_grouped_kernel, "compress_streams_grouped_kernel", dim3(kEncThreads), LDS_IF_ANY, recs, n, s); });
 
 extern "C" int cgic_encode_stream(const cgic_table *t, const void *syms, int elem_bytes, int64_t n, uint8_t *out,
                                   int64_t cap, int32_t *nbytes, void *workspace, cgic_stream_t stream)

@@ -3,6 +3,7 @@
 // self-synchronising decoder of the throughput mode).
 #pragma once
 #include "cgic_common.h"
+#include "cgic_decode_plan.h"      // kDecThreads, kSsThreadsSmall, kTicketRequestMax and the decode side's launch decisions
 
 namespace cgic {
 
@@ -17,7 +18,6 @@ constexpr int kCapCompress = 48;     // 49 uncapped, no spills at 48: 4 waves x 
 
 constexpr int kDecLutMax = 1 << kLutBitsMax;        // 13-bit LUT
 
-constexpr int kDecThreads = 1024;
 constexpr int kDecWaves = kDecThreads / kWave;
 constexpr int kSegWin = 1024;                      // LDS window of stream bytes per wave
 constexpr int kSegWinWords = kSegWin / 4 + 4;           // 65 x 16 B: one uint4 per lane + one tail
@@ -48,7 +48,6 @@ struct DecodeArgs {
 };
 
 // the self-synchronising one-workgroup-per-image decoder (cgic_decode_ss.hip); launched by cgic_decompress_streams
-constexpr int kSsThreadsSmall = 256;      // its workgroup for small streams (large ones: kDecThreads)
 __global__ void decode_image_kernel(DecodeArgs a, int stage_cap, int chunk_cap);
 struct DecodeImageArgs { DecodeArgs a; int stage_cap, chunk_cap; };      // its argument block in a grouped launch
 

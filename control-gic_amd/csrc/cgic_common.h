@@ -72,6 +72,8 @@ int acquire_tickets(hipStream_t stream, int n, unsigned int **ptr, int kind = 0)
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (function, device) and size -- not on every launch
 int ensure_dynamic_lds(const void *fn, size_t bytes);
+// ... and only where the launch needs it: up to 48 KB a kernel gets without the attribute
+inline int ensure_lds_above_48k(const void *fn, size_t bytes) { return bytes > 48 * 1024 ? ensure_dynamic_lds(fn, bytes) : CGIC_OK; }
 
 // compute units of the current device (cached per device): persistent-workgroup kernels size their grids by it
 int device_cu_count(int *out);
@@ -153,6 +155,32 @@ inline int fill_grouped(const GroupRec *const *recs, int n, Grouped<A> *g, size_
     }
     for (int i = n; i <= kMaxGroups; ++i) g->start[i] = at;
     return CGIC_OK;
+}
+
+// The grouped launch of one position: every GroupedLauncher is this with its kernel, its workgroup and the rule by which it sets
+// the kernel's dynamic-LDS attribute (the groups' largest footprint).  launch_filled is the part after fill_grouped, for a
+// launcher that picks its kernel from the filled block.
+enum LdsPolicy { LDS_NEVER, LDS_IF_ANY, LDS_ABOVE_48K, LDS_ALWAYS };     // LDS_NEVER: the kernel has no dynamic LDS
+template <class A>
+inline int launch_filled(void (*kernel)(Grouped<A>), const char *name, dim3 block, LdsPolicy policy, const Grouped<A> &g, size_t lds,
+                         hipStream_t s)
+{
+    if (policy == LDS_NEVER) lds = 0;
+    if (policy == LDS_ALWAYS || (policy == LDS_IF_ANY && lds > 0) || (policy == LDS_ABOVE_48K && lds > 48 * 1024)) {
+        const int rc = ensure_dynamic_lds((const void *)kernel, lds);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(kernel, dim3(g.start[kMaxGroups]), block, lds, s, g);
+    return launch_check(name);
+}
+template <class A>
+inline int launch_grouped(void (*kernel)(Grouped<A>), const char *name, dim3 block, LdsPolicy policy, const GroupRec *const *recs, int n,
+                          hipStream_t s)
+{
+    Grouped<A> g;
+    size_t lds;
+    const int rc = fill_grouped(recs, n, &g, &lds);
+    return rc ? rc : launch_filled(kernel, name, block, policy, g, lds, s);
 }
 
 struct Table;  // host object behind cgic_table

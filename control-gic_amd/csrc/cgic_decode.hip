@@ -777,10 +777,6 @@ __global__ __launch_bounds__(kDecThreads) void decode_split_grouped_kernel(Group
     decode_split_body(g.a[group_locate(g, &blk)], blk);
 }
 
-constexpr int kMergeThreads = 512;
-constexpr int kMergeOneBandThreads = 512;       // throughput mode: one band per image (1024 until round 3: 512 measured ~0.5-1 us per step better in flight)
-constexpr int kMergeBands = 4;          // row bands per image at least; more for few large images (gridDim.x)
-
 struct MergeArgs {
     const uint8_t *in;
     int64_t slot;
@@ -1246,6 +1242,17 @@ __global__ void gather_kernel(const int64_t *__restrict__ ind, int64_t B, int64_
 
 using namespace cgic;
 
+// dynamic LDS of this file's prefix decoders: LUT, one window per wave, the segment state and the staged trie -- with the per-position
+// caches (FastTables: decode_split_kernel, decode_streams_kernel) or without (decode_stream_kernel) -- and never less than the one-wave
+// decoder's LUT and window
+static size_t decoder_lds_bytes(bool fast_tables)
+{
+    const size_t seg = sizeof(uint32_t) * (kDecLutMax + kDecWaves * kSegWinWords) + sizeof(SegShared) + sizeof(int32_t) * 2 * kLdsTrieNodes
+                       + (fast_tables ? sizeof(FastTables) : 0);
+    const size_t one_wave = sizeof(uint32_t) * (kDecLutMax + kWinWords);
+    return seg > one_wave ? seg : one_wave;
+}
+
 extern "C" int cgic_decode_stream(const cgic_table *t, const uint8_t *in, int64_t nbytes, int64_t *syms,
                                   int64_t cap, int64_t *count, cgic_stream_t stream)
 {
@@ -1256,20 +1263,13 @@ extern "C" int cgic_decode_stream(const cgic_table *t, const uint8_t *in, int64_
     int rc = table_device_view(t, &a.tab);
     if (rc) return rc;
     a.in = in; a.nbytes = nbytes; a.syms = syms; a.cap = cap; a.count = count;
-    size_t lds = sizeof(uint32_t) * (kDecLutMax + kDecWaves * kSegWinWords) + sizeof(SegShared) + sizeof(int32_t) * 2 * kLdsTrieNodes;
-    if (lds < sizeof(uint32_t) * (kDecLutMax + kWinWords)) lds = sizeof(uint32_t) * (kDecLutMax + kWinWords);
-    { int rc_ = ensure_dynamic_lds((const void *)decode_stream_kernel, (size_t)lds); if (rc_) return rc_; }
+    const size_t lds = decoder_lds_bytes(false);
+    rc = ensure_dynamic_lds((const void *)decode_stream_kernel, lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(decode_stream_kernel, dim3(1), dim3(kDecThreads), lds, (hipStream_t)stream, a);
     return launch_check("decode_stream_kernel");
 }
 
-static const size_t kLdsBudget = 150 * 1024;
-
-// decoder workgroups per image (decode_split_kernel): grids up to 64x64 | beyond | beyond when the merge rides in the launch -- 16 are
-// as fast as 24 per call, and the CUs they leave go to merge bands (2040x1356 chain 0.105 -> 0.104 ms; 12 falls off the fast path)
-constexpr unsigned int kDecWgsSmall = 4, kDecWgsLarge = 24, kDecWgsFusedLarge = 16;
-// merge bands per image are doubled while the launch has fewer than kMergeWgs workgroups and a band keeps 2 x kMergeMinRows coarse rows
-constexpr int64_t kMergeWgs = 256, kMergeMinRows = 1;
 static std::atomic<int> g_decode_mode{CGIC_DECODE_AUTO};
 static std::atomic<unsigned int *> g_decode_stats{nullptr};
 extern "C" int cgic_decode_stats(unsigned int *device_counters)
@@ -1319,120 +1319,72 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
                    reinterpret_cast<uintptr_t>(mask_f_out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask_m_out) & 7) == 0,
                  CGIC_ERR_INVALID, "decompress_streams: outputs must be 16-byte aligned");
     if (B == 0) return CGIC_OK;
-    const size_t per = (size_t)((h / 4) * (w / 4) + (h / 2) * (w / 2) + h * w);
     hipStream_t s = (hipStream_t)stream;
     DecodeArgs d;
     rc = table_device_view(t, &d.tab);
     if (rc) return rc;
+
+    // ---- plan: every decision of this call is taken in cgic_decode_plan.h, before a ticket is requested or an attribute set ----
+    DecodeShape shape;
+    shape.B = B; shape.h = h; shape.w = w; shape.slot = slot; shape.K = K; shape.has_zq = z_q != nullptr;
+    shape.max_len = d.tab.max_len; shape.lut_bits = d.tab.lut_bits; shape.dec_mode = dec_mode;
+    rc = device_cu_count(&shape.cus);
+    if (rc) return rc;
+    shape.cu_share = group_cu_share();
+    shape.no_fuse = dev_knob("CGIC_NO_DECODE_MERGE") != 0;
+    shape.lds_decoder = decoder_lds_bytes(true);
+    DecodePlan plan;
+    const char *why = "";
+    rc = decode_plan(shape, &plan, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+
+    // ---- issue: the argument blocks, then tickets, attributes and launches of the planned path only ----
+    const size_t per = (size_t)((h / 4) * (w / 4) + (h / 2) * (w / 2) + h * w);
+    const size_t lds_d = plan.lds_d, lds_m = plan.lds_m;
     d.in = in; d.slot = slot; d.nbytes = nbytes; d.h = h; d.w = w; d.stream_mask = kModeStreams[mode];
     d.dsym = (uint16_t *)workspace;
     d.dcount = (int32_t *)((char *)workspace + align16((size_t)B * per * sizeof(uint16_t)));
     d.status = status;
-    // Streams are split over workgroups that exchange range functions (decode_split_kernel): 4 workgroups per image for grids
-    // up to 64x64 (a 256x256 image), 24 beyond, dealt to the streams by length on the device.  Tables with codes longer than
-    // 64 bits take the one-wave path of decode_streams_kernel; batches beyond one ticket request are cut into several launches.
-    const bool large = h * w > 64 * 64;
     d.bf = (uint32_t *)((char *)d.dcount + align16((size_t)B * 3 * sizeof(int32_t)));
-    size_t lds_d = sizeof(uint32_t) * (kDecLutMax + kDecWaves * kSegWinWords) + sizeof(SegShared) + sizeof(int32_t) * 2 * kLdsTrieNodes
-                   + sizeof(FastTables);
-    if (lds_d < sizeof(uint32_t) * (kDecLutMax + kWinWords)) lds_d = sizeof(uint32_t) * (kDecLutMax + kWinWords);
-    if (lds_d > 48 * 1024)
-        { int rc_ = ensure_dynamic_lds((const void *)decode_streams_kernel, (size_t)lds_d); if (rc_) return rc_; }
     d.tick = nullptr;
     d.stats = g_decode_stats.load(std::memory_order_relaxed);
-    // The self-synchronising one-workgroup-per-image decoder when the worst case of the grid fits its LDS: bits <= symbols
-    // the three grids can hold x the longest code.  (Longer inputs are an overflow on any path.)
     MergeArgs m;
     m.in = in; m.slot = slot; m.nbytes = nbytes; m.h = h; m.w = w; m.mode = mode;
     m.dsym = d.dsym; m.dcount = d.dcount; m.ind_out = ind_out;
     m.mc_out = mask_c_out; m.mm_out = mask_m_out; m.mf_out = mask_f_out;
     m.codebook = codebook; m.K = K; m.zq = z_q; m.codebook2 = codebook2; m.zq2 = z_q2; m.status = status;
-    const size_t wc = (size_t)(((h / 4) * (w / 4) + 31) / 32), wm = (size_t)(((h / 2) * (w / 2) + 31) / 32);
-    size_t lds_m = (3 * (wc + wm) + 4) * sizeof(uint32_t);
-    CGIC_REQUIRE(lds_m <= kLdsBudget, CGIC_ERR_UNSUPPORTED, "decompress_streams: grid too large for the mask bitsets");
-    m.stage_cb = (z_q && lds_m + (size_t)K * 16 <= 64 * 1024) ? 1 : 0;
-    if (m.stage_cb) lds_m += (size_t)K * 16;
-    m.stage_sym = (per % 2 == 0 && lds_m + per * 2 + 4 <= 64 * 1024) ? 1 : 0;
-    if (m.stage_sym) lds_m += ((per + 1) / 2) * 4;
-    // mask-stream slots must cover the word-wise staging reads
-    CGIC_REQUIRE((size_t)slot >= (wm + 2) * 4, CGIC_ERR_CAPACITY, "decompress_streams: slot smaller than a mask stream");
-    // 4 bands per image fill the GPU at B = 64; a few large tiles get more (every band re-derives the mask prefixes,
-    // so not more than needed): ~256 workgroups in all, at least 2 coarse rows per band
-    // Decoder and merge go out as ONE launch when every workgroup of both gets a CU of its own (B = 1 .. a few dozen images, or
-    // a few tiles; inside a launch group: within the group's share of the chip)
-    const unsigned int ndec = large ? kDecWgsFusedLarge : kDecWgsSmall;
-    int cus = 0;
-    rc = device_cu_count(&cus);
-    if (rc) return rc;
-    const int64_t cu_share = (int64_t)((double)cus * group_cu_share() + 0.5);
-    // The fused launch's merge bands SPIN on the decoder workgroups of the same launch (wait_decoded).  Alone on the chip that cannot
-    // hang: the decoders sit in front of the bands in the grid and every one gets a CU at once.  With other launches of this kind in
-    // flight on other queues (up to four hardware queues by default), an XCD could in principle fill up with spinning bands of
-    // several launches whose decoders are queued behind each other's bands.  The chip holds two of these 1024-thread workgroups per
-    // CU: as long as FOUR such launches together fit (each at most half the CUs' worth of workgroups), every workgroup of every one
-    // of them is resident at once and nobody waits for a slot.  CGIC_DECODE_LATENCY is the caller's statement that this call has
-    // the GPU to itself (one batch at a time): it keeps the whole chip as its budget.
-    const int64_t cu_budget = dec_mode == CGIC_DECODE_LATENCY ? cu_share : cu_share / 2;
-    const bool fuse_base = dec_mode != CGIC_DECODE_THROUGHPUT && d.tab.max_len <= 64 && B * 3 <= (int64_t)(16384 / 4) && !dev_knob("CGIC_NO_DECODE_MERGE");
-    int64_t nbands = kMergeBands;
-    {
-        const int64_t h4 = h >> 2;
-        while (nbands * B < kMergeWgs && nbands * 2 <= h4 / kMergeMinRows) {
-            // (keep a small launch fusable with its decoder: see below)
-            if (fuse_base && B * (int64_t)(ndec + 2 * nbands) > cu_budget && B * (int64_t)(ndec + nbands) <= cu_budget) break;
-            nbands *= 2;
-        }
+    m.stage_cb = plan.stage_cb; m.stage_sym = plan.stage_sym; m.band_syms = plan.band_syms;
+
+    if (plan.decoder == DECODER_FUSED) {
+        DecodeMergeArgs p;
+        p.c = d; p.m = m; p.ndec = plan.ndec; p.nbands = (unsigned int)plan.nbands; p.active_bands = plan.active_bands; p.B = (unsigned int)B;
+        rc = acquire_tickets(s, (int)(B * 3), &p.c.tick);
+        if (rc) return rc;
+        rc = acquire_tickets(s, (int)B, &p.done);
+        if (rc) return rc;
+        const size_t lds_f = plan.lds_f;
+        rc = ensure_dynamic_lds((const void *)decode_merge_kernel, lds_f);
+        if (rc) return rc;
+        const dim3 grid_f((unsigned int)(B * (plan.ndec + plan.nbands)));
+        return launch_or_record(KID_DECODE_MERGE, grid_f, dim3(kDecThreads), lds_f, p, s, [=] {
+            hipLaunchKernelGGL(decode_merge_kernel, grid_f, dim3(kDecThreads), lds_f, s, p);
+            return launch_check("decode_merge_kernel"); });
     }
-    // the image's symbols do not fit LDS: every band stages its own three rank ranges (at most 21/16 symbols per position)
-    m.band_syms = 0;
-    if (!m.stage_sym) {
-        const int64_t rows_per = (((h >> 2) + nbands - 1) / nbands) * 4;
-        const int64_t need = rows_per * w * 21 / 16 + 8;
-        if (lds_m + (size_t)need * 2 <= 64 * 1024) { m.band_syms = need; lds_m += (size_t)need * 2; }
-    }
-    // ---- decoder and merge as ONE launch ----
-    {
-        const int64_t rows_per = (((h >> 2) + nbands - 1) / nbands) * 4;
-        const unsigned int active = (unsigned int)((h + rows_per - 1) / rows_per);
-        const size_t lds_f = lds_d > lds_m ? lds_d : lds_m;
-        if (fuse_base && B * (int64_t)(ndec + nbands) <= cu_budget) {
-            DecodeMergeArgs p;
-            p.c = d; p.m = m; p.ndec = ndec; p.nbands = (unsigned int)nbands; p.active_bands = active; p.B = (unsigned int)B;
-            rc = acquire_tickets(s, (int)(B * 3), &p.c.tick);
-            if (rc) return rc;
-            rc = acquire_tickets(s, (int)B, &p.done);
-            if (rc) return rc;
-            rc = ensure_dynamic_lds((const void *)decode_merge_kernel, lds_f);
-            if (rc) return rc;
-            const dim3 grid_f((unsigned int)(B * (ndec + nbands)));
-            return launch_or_record(KID_DECODE_MERGE, grid_f, dim3(kDecThreads), lds_f, p, s, [=] {
-                hipLaunchKernelGGL(decode_merge_kernel, grid_f, dim3(kDecThreads), lds_f, s, p);
-                return launch_check("decode_merge_kernel"); });
-        }
-    }
-    bool ss = false;
-    if (d.tab.max_len <= 64 && dec_mode == CGIC_DECODE_THROUGHPUT) {
-        const size_t bits_cap = per * (size_t)d.tab.max_len + 3 * 64;
-        const size_t stage_cap = align16(bits_cap / 8 + 3 * 48), chunk_cap = align16(bits_cap / 64 + 8);
-        const size_t lds_ss = sizeof(uint32_t) * ((size_t)1 << d.tab.lut_bits) + stage_cap + 3 * chunk_cap;
-        if (lds_ss <= kLdsBudget) {
-            ss = true;
-            { int rc_ = ensure_dynamic_lds((const void *)decode_image_kernel, lds_ss); if (rc_) return rc_; }
-            const int T = large ? kDecThreads : kSsThreadsSmall;
-            const int sc_ = (int)stage_cap, cc_ = (int)chunk_cap;
-            DecodeImageArgs dia;
-            dia.a = d; dia.stage_cap = sc_; dia.chunk_cap = cc_;
-            rc = launch_or_record(KID_DECODE_IMAGE, dim3((unsigned)B), dim3(T), lds_ss, dia, s, [=] {
-                hipLaunchKernelGGL(decode_image_kernel, dim3((unsigned)B), dim3(T), lds_ss, s, d, sc_, cc_);
-                return launch_check("decode_image_kernel"); });
-        }
-    }
-    if (ss) {
-    } else if (d.tab.max_len <= 64) {
-        if (lds_d > 48 * 1024)
-            { int rc_ = ensure_dynamic_lds((const void *)decode_split_kernel, (size_t)lds_d); if (rc_) return rc_; }
-        // one ticket request covers 3 slots per image: larger batches are cut into several launches of the same kernel
-        const int64_t per_launch = (int64_t)(16384 / 4) / 3;
+    if (plan.decoder == DECODER_IMAGE) {
+        const size_t lds_ss = plan.lds_ss;
+        rc = ensure_dynamic_lds((const void *)decode_image_kernel, lds_ss);
+        if (rc) return rc;
+        const int T = plan.image_threads;
+        const int sc_ = (int)plan.stage_cap, cc_ = (int)plan.chunk_cap;
+        DecodeImageArgs dia;
+        dia.a = d; dia.stage_cap = sc_; dia.chunk_cap = cc_;
+        rc = launch_or_record(KID_DECODE_IMAGE, dim3((unsigned)B), dim3(T), lds_ss, dia, s, [=] {
+            hipLaunchKernelGGL(decode_image_kernel, dim3((unsigned)B), dim3(T), lds_ss, s, d, sc_, cc_);
+            return launch_check("decode_image_kernel"); });
+    } else if (plan.decoder == DECODER_SPLIT) {
+        rc = ensure_lds_above_48k((const void *)decode_split_kernel, lds_d);
+        if (rc) return rc;
+        const int64_t per_launch = plan.split_batch;
         for (int64_t b0 = 0; b0 < B && rc == CGIC_OK; b0 += per_launch) {
             const int64_t nb = B - b0 < per_launch ? B - b0 : per_launch;
             DecodeArgs c = d;
@@ -1444,67 +1396,42 @@ extern "C" int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, i
             c.bf = d.bf + (size_t)b0 * 3 * kDecPartsMax * kWave;
             rc = acquire_tickets(s, (int)(nb * 3), &c.tick);
             if (rc) return rc;
-            const dim3 grid_c(large ? kDecWgsLarge : kDecWgsSmall, (unsigned)nb);
+            const dim3 grid_c(plan.ndec, (unsigned)nb);
             rc = launch_or_record(KID_DECODE_SPLIT, grid_c, dim3(kDecThreads), lds_d, c, s, [=] {
                 hipLaunchKernelGGL(decode_split_kernel, grid_c, dim3(kDecThreads), lds_d, s, c);
                 return launch_check("decode_split_kernel"); });
         }
     } else {
-        rc = launch_or_record(KID_NONE, dim3((unsigned)B, 3), dim3(kDecThreads), lds_d, d, s, [=] {
-            hipLaunchKernelGGL(decode_streams_kernel, dim3((unsigned)B, 3), dim3(kDecThreads), lds_d, s, d);
+        rc = ensure_lds_above_48k((const void *)decode_streams_kernel, lds_d);
+        if (rc) return rc;
+        const dim3 grid_s((unsigned)B, plan.ndec);
+        rc = launch_or_record(KID_NONE, grid_s, dim3(kDecThreads), lds_d, d, s, [=] {
+            hipLaunchKernelGGL(decode_streams_kernel, grid_s, dim3(kDecThreads), lds_d, s, d);
             return launch_check("decode_streams_kernel"); });
     }
     if (rc) return rc;
-    if (dec_mode == CGIC_DECODE_THROUGHPUT && !large && m.stage_sym) {
-        // several batches in flight: one band of 1024 threads per image (see merge_kernel)
-        if (lds_m > 48 * 1024)
-            { int rc_ = ensure_dynamic_lds((const void *)merge_kernel<kMergeOneBandThreads>, (size_t)lds_m); if (rc_) return rc_; }
+
+    if (plan.merge == MERGE_ONE_BAND) {
+        rc = ensure_lds_above_48k((const void *)merge_kernel<kMergeOneBandThreads>, lds_m);
+        if (rc) return rc;
         return launch_or_record(KID_NONE, dim3(1u, (unsigned)B), dim3(kMergeOneBandThreads), lds_m, m, s, [=] {
             hipLaunchKernelGGL(merge_kernel<kMergeOneBandThreads>, dim3(1u, (unsigned)B), dim3(kMergeOneBandThreads), lds_m, s, m);
             return launch_check("merge_kernel"); });
     }
-    if (lds_m > 48 * 1024)
-        { int rc_ = ensure_dynamic_lds((const void *)merge_kernel<kMergeThreads>, (size_t)lds_m); if (rc_) return rc_; }
-    const dim3 grid_m((unsigned)nbands, (unsigned)B);
+    rc = ensure_lds_above_48k((const void *)merge_kernel<kMergeThreads>, lds_m);
+    if (rc) return rc;
+    const dim3 grid_m((unsigned)plan.nbands, (unsigned)B);
     return launch_or_record(KID_MERGE, grid_m, dim3(kMergeThreads), lds_m, m, s, [=] {
         hipLaunchKernelGGL(merge_kernel<kMergeThreads>, grid_m, dim3(kMergeThreads), lds_m, s, m);
         return launch_check("merge_kernel"); });
 }
 
-static int decode_split_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
-{
-    Grouped<DecodeArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    if (lds > 48 * 1024) { rc = ensure_dynamic_lds((const void *)decode_split_grouped_kernel, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(decode_split_grouped_kernel, dim3(g.start[kMaxGroups]), dim3(kDecThreads), lds, s, g);
-    return launch_check("decode_split_grouped_kernel");
-}
-static int merge_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
-{
-    Grouped<MergeArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    if (lds > 48 * 1024) { rc = ensure_dynamic_lds((const void *)merge_grouped_kernel, lds); if (rc) return rc; }
-    hipLaunchKernelGGL(merge_grouped_kernel, dim3(g.start[kMaxGroups]), dim3(kMergeThreads), lds, s, g);
-    return launch_check("merge_grouped_kernel");
-}
-static int decode_merge_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
-{
-    Grouped<DecodeMergeArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    rc = ensure_dynamic_lds((const void *)decode_merge_grouped_kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(decode_merge_grouped_kernel, dim3(g.start[kMaxGroups]), dim3(kDecThreads), lds, s, g);
-    return launch_check("decode_merge_grouped_kernel");
-}
-static GroupedRegistrar reg_decode_merge(KID_DECODE_MERGE, decode_merge_grouped_launch);
-static GroupedRegistrar reg_decode_split(KID_DECODE_SPLIT, decode_split_grouped_launch);
-static GroupedRegistrar reg_merge(KID_MERGE, merge_grouped_launch);
+static GroupedRegistrar reg_decode_merge(KID_DECODE_MERGE, [](const GroupRec *const *recs, int n, hipStream_t s) {
+    return launch_grouped(decode_merge_grouped_kernel, "decode_merge_grouped_kernel", dim3(kDecThreads), LDS_ALWAYS, recs, n, s); });
+static GroupedRegistrar reg_decode_split(KID_DECODE_SPLIT, [](const GroupRec *const *recs, int n, hipStream_t s) {
+    return launch_grouped(decode_split_grouped_kernel, "decode_split_grouped_kernel", dim3(kDecThreads), LDS_ABOVE_48K, recs, n, s); });
+static GroupedRegistrar reg_merge(KID_MERGE, [](const GroupRec *const *recs, int n, hipStream_t s) {
+    return launch_grouped(merge_grouped_kernel, "merge_grouped_kernel", dim3(kMergeThreads), LDS_ABOVE_48K, recs, n, s); });
 
 extern "C" int cgic_embedding_gather_f32(const int64_t *ind, int64_t B, int64_t hw, const float *codebook, int K,
                                          int e_dim, float *out, int32_t *status, cgic_stream_t stream)

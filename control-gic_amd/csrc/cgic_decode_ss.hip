@@ -490,15 +490,5 @@ __global__ __launch_bounds__(kDecThreads) void decode_image_grouped_kernel(Group
 }  // namespace cgic
 
 using namespace cgic;
-static int decode_image_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
-{
-    Grouped<DecodeImageArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    rc = ensure_dynamic_lds((const void *)decode_image_grouped_kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(decode_image_grouped_kernel, dim3(g.start[kMaxGroups]), recs[0]->block, lds, s, g);
-    return launch_check("decode_image_grouped_kernel");
-}
-static GroupedRegistrar reg_decode_image(KID_DECODE_IMAGE, decode_image_grouped_launch);
+static GroupedRegistrar reg_decode_image(KID_DECODE_IMAGE, [](const GroupRec *const *recs, int n, hipStream_t s) {
+    return launch_grouped(decode_image_grouped_kernel, "decode_image_grouped_kernel", recs[0]->block, LDS_ALWAYS, recs, n, s); });

@@ -542,12 +542,7 @@ static int entropy_maps_launch(const void *x, bool u8, int64_t B, int64_t H, int
 template <bool U8>
 static int entropy_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
 {
-    Grouped<EntArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(entropy_maps_grouped_kernel<U8>, dim3(g.start[kMaxGroups]), dim3(kEntThreads), 0, s, g);
-    return launch_check("entropy_maps_grouped_kernel");
+    return launch_grouped(entropy_maps_grouped_kernel<U8>, "entropy_maps_grouped_kernel", dim3(kEntThreads), LDS_NEVER, recs, n, s);
 }
 static GroupedRegistrar reg_ent_f32(KID_ENTROPY_F32, entropy_grouped_launch<false>);
 static GroupedRegistrar reg_ent_u8(KID_ENTROPY_U8, entropy_grouped_launch<true>);
@@ -555,12 +550,7 @@ static GroupedRegistrar reg_ent_u8(KID_ENTROPY_U8, entropy_grouped_launch<true>)
 template <bool U8>
 static int entropy_tiles_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
 {
-    Grouped<EntWinArgs> g;
-    size_t lds;
-    int rc = fill_grouped(recs, n, &g, &lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(entropy_tiles_grouped_kernel<U8>, dim3(g.start[kMaxGroups]), dim3(kEntThreads), 0, s, g);
-    return launch_check("entropy_tiles_grouped_kernel");
+    return launch_grouped(entropy_tiles_grouped_kernel<U8>, "entropy_tiles_grouped_kernel", dim3(kEntThreads), LDS_NEVER, recs, n, s);
 }
 static GroupedRegistrar reg_ent_win_f32(KID_ENTROPY_WIN_F32, entropy_tiles_grouped_launch<false>);
 static GroupedRegistrar reg_ent_win_u8(KID_ENTROPY_WIN_U8, entropy_tiles_grouped_launch<true>);

@@ -11,6 +11,7 @@
 // priority queue gives a different (equally optimal, but not bit-identical)
 // code.  Also errors, the thread-local message, and ABI/version queries.
 #include "cgic_common.h"
+#include "cgic_decode_plan.h"      // kTicketRequestMax
 
 #include <stdarg.h>
 
@@ -53,6 +54,7 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
 // Pools and rings are created by EAGER calls (allocation is illegal in capture): call an entry point once eagerly on a
 // device -- and on a stream whose eager launches will need tickets -- before capturing.
 constexpr size_t kRingSlots = 16384, kChunkSlots = 262144;
+static_assert((size_t)kTicketRequestMax == kRingSlots / 4, "callers size their requests by kTicketRequestMax");
 struct TicketRange { size_t start, count; };
 struct TicketPool {
     std::map<hipStream_t, std::pair<unsigned int *, size_t>> rings;     // stream -> (memory, next slot)
@@ -87,7 +89,7 @@ static void free_range(TicketPool &p, TicketRange r)
 
 int acquire_tickets(hipStream_t s, int n, unsigned int **ptr, int kind)
 {
-    CGIC_REQUIRE(n > 0 && (size_t)n <= kRingSlots / 4, CGIC_ERR_INVALID, "acquire_tickets: bad count %d", n);
+    CGIC_REQUIRE(n > 0 && n <= kTicketRequestMax, CGIC_ERR_INVALID, "acquire_tickets: bad count %d", n);
     int dev = 0;
     CGIC_HIP_TRY(hipGetDevice(&dev));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;

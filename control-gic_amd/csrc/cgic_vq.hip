@@ -1552,16 +1552,10 @@ static int vqfr_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s
     if (rc) return rc;
     bool split = false;
     for (int i = 0; i < n; ++i) split = split || g.a[i].r.rq.nq != 0;
-    if (split) {
-        rc = ensure_dynamic_lds((const void *)vq_filter_router_grouped_kernel<ALIGNED, true>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((vq_filter_router_grouped_kernel<ALIGNED, true>), dim3(g.start[kMaxGroups]), dim3(kVqfThreads), lds, s, g);
-        return launch_check("vq_filter_router_grouped_kernel(split)");
-    }
-    rc = ensure_dynamic_lds((const void *)vq_filter_router_grouped_kernel<ALIGNED>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((vq_filter_router_grouped_kernel<ALIGNED>), dim3(g.start[kMaxGroups]), dim3(kVqfThreads), lds, s, g);
-    return launch_check("vq_filter_router_grouped_kernel");
+    if (split)
+        return launch_filled(vq_filter_router_grouped_kernel<ALIGNED, true>, "vq_filter_router_grouped_kernel(split)", dim3(kVqfThreads),
+                             LDS_ALWAYS, g, lds, s);
+    return launch_filled(vq_filter_router_grouped_kernel<ALIGNED>, "vq_filter_router_grouped_kernel", dim3(kVqfThreads), LDS_ALWAYS, g, lds, s);
 }
 static GroupedRegistrar reg_vqfr_al(KID_VQF_ROUTER_AL, vqfr_grouped_launch<true>);
 static GroupedRegistrar reg_vqfr_un(KID_VQF_ROUTER_UN, vqfr_grouped_launch<false>);

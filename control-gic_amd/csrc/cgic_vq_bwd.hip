@@ -151,10 +151,10 @@ extern "C" int cgic_vq_backward_f32(const float *z, int64_t B, int64_t hw, const
     a.z = z; a.hw = hw; a.N = N; a.cb = codebook; a.K = K; a.idx = indices; a.g_zq = g_zq; a.g_loss = g_loss;
     a.coef_z = (float)(-scale * w_z); a.g_z = g_z; a.partial = g_codebook ? (double *)workspace : nullptr; a.status = nullptr;
     const size_t lds = (size_t)K * 16 + (g_codebook ? (size_t)K * 32 : 0);
-    if (lds > 48 * 1024)
-        { int rc_ = ensure_dynamic_lds((const void *)vq_backward_kernel, (size_t)lds); if (rc_) return rc_; }
+    int rc = ensure_lds_above_48k((const void *)vq_backward_kernel, lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(vq_backward_kernel, dim3(nblk), dim3(kBwdThreads), lds, s, a);
-    int rc = launch_check("vq_backward_kernel");
+    rc = launch_check("vq_backward_kernel");
     if (rc || !g_codebook) return rc;
     const int n_out = 4 * K;
     hipLaunchKernelGGL(vq_backward_finish_kernel, dim3((n_out + 255) / 256), dim3(256), 0, s, (const double *)workspace, nblk, n_out,

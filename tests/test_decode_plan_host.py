@@ -1,0 +1,120 @@
+"""The launch plan of cgic_decompress_streams (csrc/cgic_decode_plan.h) without a GPU: which decoder path and merge form a shape
+takes, the grids and the LDS sizes.  The header is plain C++17: tests/host/decode_plan_main.cpp is compiled with the host compiler
+alone and run over the table below, whose rows were worked out by hand from the arithmetic of the host path."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+AUTO, LATENCY, THROUGHPUT = 0, 1, 2
+ERR_UNSUPPORTED, ERR_CAPACITY = -2, -5
+LDS_DECODER = 90000            # stands for decoder_lds_bytes(true); the plan only passes it on (lds_d) and takes the maximum (lds_f)
+
+# 256 CUs, share 1.0, K = 1024, z_q given, max_len 20, lut_bits 13 unless a row says otherwise; h x w are latent grids
+DEFAULTS = dict(slot=1 << 20, K=1024, has_zq=1, max_len=20, lut_bits=13, cus=256, share=1.0, no_fuse=0, lds_decoder=LDS_DECODER)
+
+
+def _case(name, B, h, w, mode, want, **shape):
+    return pytest.param(dict(DEFAULTS, B=B, h=h, w=w, mode=mode, **shape), want, id=name)
+
+
+def _merge(nbands, active, stage_cb, stage_sym, band_syms, lds_m):
+    return dict(nbands=nbands, active=active, stage_cb=stage_cb, stage_sym=stage_sym, band_syms=band_syms, lds_m=lds_m)
+
+
+def _fused(grid, ndec, *merge):
+    return dict(decoder="fused", grid=grid, ndec=ndec, **_merge(*merge))
+
+
+def _split(ndec, form, *merge):
+    return dict(decoder="split", merge=form, ndec=ndec, split_batch=1365, **_merge(*merge))
+
+
+def _image(threads, stage_cap, chunk_cap, lds_ss, form, *merge):
+    return dict(decoder="image", merge=form, ndec=1, image_threads=threads, stage_cap=stage_cap, chunk_cap=chunk_cap, lds_ss=lds_ss,
+                **_merge(*merge))
+
+
+CASES = [
+    _case("64x64x64-auto", 64, 64, 64, AUTO, _split(4, "bands", 4, 4, 1, 1, 0, 27632)),
+    _case("64x64x64-latency", 64, 64, 64, LATENCY, _split(4, "bands", 4, 4, 1, 1, 0, 27632)),
+    _case("64x64x64-throughput", 64, 64, 64, THROUGHPUT, _image(256, 13616, 1696, 51472, "one_band", 4, 4, 1, 1, 0, 27632)),
+    _case("1x64x64-auto", 1, 64, 64, AUTO, _fused(20, 4, 16, 16, 1, 1, 0, 27632)),
+    _case("1x64x64-latency", 1, 64, 64, LATENCY, _fused(20, 4, 16, 16, 1, 1, 0, 27632)),
+    _case("8x64x64-auto", 8, 64, 64, AUTO, _fused(96, 4, 8, 8, 1, 1, 0, 27632)),
+    _case("8x64x64-latency", 8, 64, 64, LATENCY, _fused(160, 4, 16, 16, 1, 1, 0, 27632)),
+    _case("16x64x64-auto", 16, 64, 64, AUTO, _fused(128, 4, 4, 4, 1, 1, 0, 27632)),
+    _case("16x64x64-latency", 16, 64, 64, LATENCY, _fused(192, 4, 8, 8, 1, 1, 0, 27632)),
+    _case("1x192x192-auto", 1, 192, 192, AUTO, _fused(48, 16, 32, 24, 1, 0, 2024, 24768)),
+    _case("1x192x192-latency", 1, 192, 192, LATENCY, _fused(48, 16, 32, 24, 1, 0, 2024, 24768)),
+    _case("1x192x192-throughput", 1, 192, 192, THROUGHPUT, _split(24, "bands", 32, 24, 1, 0, 2024, 24768)),
+    _case("4x192x192-auto", 4, 192, 192, AUTO, _fused(128, 16, 16, 16, 1, 0, 3032, 26784)),
+    _case("4x192x192-latency", 4, 192, 192, LATENCY, _fused(192, 16, 32, 24, 1, 0, 2024, 24768)),
+    _case("6x128x192-auto", 6, 128, 192, AUTO, _fused(120, 16, 4, 4, 1, 0, 8072, 35424)),
+    _case("6x128x192-latency", 6, 128, 192, LATENCY, _fused(192, 16, 16, 16, 1, 0, 2024, 23328)),
+    _case("6x128x192-throughput", 6, 128, 192, THROUGHPUT, _image(1024, 80816, 10096, 143872, "bands", 32, 32, 1, 0, 1016, 21312)),
+    _case("1x340x512-auto", 1, 340, 512, AUTO, _fused(80, 16, 64, 43, 1, 0, 5384, 47568)),
+    # the self-synchronising decoder's LDS does not fit: the split-stream decoder
+    _case("1x340x512-throughput", 1, 340, 512, THROUGHPUT, _split(24, "bands", 64, 43, 1, 0, 5384, 47568)),
+    _case("1x4x4-auto", 1, 4, 4, AUTO, _fused(8, 4, 4, 1, 1, 0, 29, 16482)),
+    _case("1x8x4-throughput", 1, 8, 4, THROUGHPUT, _image(256, 288, 32, 33152, "one_band", 4, 2, 1, 1, 0, 16508)),
+    _case("2x12x20-auto", 2, 12, 20, AUTO, _fused(16, 4, 4, 3, 1, 0, 113, 16662)),
+    # beyond one ticket request: never fused, the split path in launches of 1365 images (1365 + 35)
+    _case("1400x16x16-auto", 1400, 16, 16, AUTO, _split(4, "bands", 4, 4, 1, 1, 0, 17108)),
+    _case("1x64x64-max_len70", 1, 64, 64, AUTO, dict(decoder="serial", merge="bands", ndec=3, **_merge(16, 16, 1, 1, 0, 27632)), max_len=70),
+    _case("2x64x64-share0.25", 2, 64, 64, AUTO, _fused(24, 4, 8, 8, 1, 1, 0, 27632), share=0.25),
+    # the dev knob: nothing fuses, the bands are doubled as far as the rows allow
+    _case("1x64x64-latency-knob", 1, 64, 64, LATENCY, _split(4, "bands", 16, 16, 1, 1, 0, 27632), no_fuse=1),
+    # no z_q: no codebook in LDS (496 bytes of bitsets + 5376 symbols of 2 bytes)
+    _case("1x64x64-no_zq", 1, 64, 64, AUTO, _fused(20, 4, 16, 16, 0, 1, 0, 11248), has_zq=0),
+    # a decoder that needs less LDS than the merge: the fused launch takes the merge's
+    _case("1x64x64-small-decoder", 1, 64, 64, AUTO, dict(_fused(20, 4, 16, 16, 1, 1, 0, 27632), lds_f=27632), lds_decoder=1000),
+    # 3 x (2813 + 11250) words of bitsets + 4 = 168772 bytes > 150 KB
+    _case("1x1200x1200-bitsets", 1, 1200, 1200, AUTO, dict(err=ERR_UNSUPPORTED, why="grid too large for the mask bitsets")),
+    # a 64x64 grid's medium mask stream is staged as 32 + 2 words = 136 bytes
+    _case("1x64x64-slot128", 1, 64, 64, AUTO, dict(err=ERR_CAPACITY, why="slot smaller than a mask stream"), slot=128),
+    _case("1x64x64-slot144", 1, 64, 64, AUTO, _fused(20, 4, 16, 16, 1, 1, 0, 27632), slot=144),
+]
+FIELDS = ("B", "h", "w", "slot", "K", "has_zq", "max_len", "lut_bits", "mode", "cus", "share", "no_fuse", "lds_decoder")
+
+
+@pytest.fixture(scope="module")
+def plans(tmp_path_factory):
+    """every case of the table through ONE run of the compiled program: {case id: parsed output line}"""
+    cxx = os.environ.get("CXX") or next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+    assert cxx, "no host C++ compiler found (the build needs one too)"
+    exe = str(tmp_path_factory.mktemp("decode_plan") / "decode_plan_main")
+    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Wextra", "-O1", os.path.join(ROOT, "tests", "host", "decode_plan_main.cpp"), "-o", exe])
+    text = "\n".join(" ".join(str(c.values[0][f]) for f in FIELDS) for c in CASES) + "\n"
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(CASES)
+    parsed = {}
+    for c, line in zip(CASES, out):
+        if line.startswith("err="):
+            code, why = line.split(" why=", 1)
+            parsed[c.id] = dict(err=int(code[4:]), why=why)
+        else:
+            kv = dict(t.split("=", 1) for t in line.split())
+            parsed[c.id] = {k: v if k in ("decoder", "merge") else int(v) for k, v in kv.items()}
+    return parsed
+
+
+@pytest.mark.parametrize("shape,want", CASES)
+def test_decode_plan(plans, request, shape, want):
+    got = plans[request.node.callspec.id]
+    if "err" in want:
+        assert got["err"] == want["err"] and want["why"] in got["why"]
+        return
+    assert "err" not in got, got
+    want = dict(want)
+    grid = want.pop("grid", None)
+    if grid is not None:                                  # the fused launch: decoder workgroups and bands of every image
+        assert shape["B"] * (got["ndec"] + got["nbands"]) == grid
+    assert {k: got[k] for k in want} == want
+    assert got["lds_d"] == shape["lds_decoder"] and got["lds_f"] == max(got["lds_d"], got["lds_m"])
+    if got["decoder"] != "image":
+        assert got["lds_ss"] == got["stage_cap"] == got["chunk_cap"] == got["image_threads"] == 0
+    if got["decoder"] != "split":
+        assert got["split_batch"] == 0

@@ -407,6 +407,35 @@ def test_decoder_and_merge_in_one_launch_equal_the_throughput_path(B, H, W):
     assert int(st_l[0]) != 0 and torch.equal(st_l, st_t)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W,decoder,launches", [
+    (1, 256, 256, "latency", 1),            # decoder and merge as one launch
+    (1, 256, 256, "throughput", 2),         # the self-synchronising decoder, then the merge
+    (1400, 64, 64, "latency", 3),           # 3 x 1400 tickets are more than one request: two split-stream launches, then the merge
+])
+def test_decompress_issues_the_launches_its_plan_names(B, H, W, decoder, launches):
+    """the path cgic_decompress_streams takes (cgic_decode_plan.h), seen through the recorder of a one-group launch group: the
+    number of launches per call, and the same indices, masks, rows and statuses as the ungrouped call"""
+    from control_gic_amd import _lib
+    from control_gic_amd.quantize import vq_forward_route
+    cg, dev, rng, vq, codec = _setup(B + H)
+    x = torch.from_numpy(rng.random((B, 3, H, W), dtype=np.float32)).to(dev)
+    z = torch.from_numpy(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32)).to(dev)
+    e8, e16 = cg.entropy_maps(x)
+    _, _, ind, mask, _, mode = vq_forward_route(z, vq.embedding.weight, 0.25, True, e16, e8, 0.1, 0.8, per_image=True)
+    comp = codec.compress(ind, mask, mode)
+    ref = codec.decompress(comp, decoder=decoder)
+    grp = _lib.launch_group(1, None, dev)
+    with grp as g:
+        g.select(0)
+        got = codec.decompress(comp, decoder=decoder)
+    assert grp.launches == launches
+    torch.cuda.synchronize()
+    assert torch.equal(ref[0], got[0]) and torch.equal(ref[2], got[2]) and torch.equal(ref[3], got[3])
+    assert all(torch.equal(p, q) for p, q in zip(ref[1], got[1]))
+    assert int(got[3].abs().max()) == 0
+
+
 def test_tile_entry_points_check_their_arguments():
     """argument checks of cgic_cut_tiles / cgic_entropy_maps_tiles come before any launch (host logic only)"""
     import ctypes
