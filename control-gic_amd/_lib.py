@@ -421,3 +421,12 @@ def require_device(*tensors):
             raise RuntimeError(
                 "control_gic_amd ops run on an MI355X (HIP) device only; got a CPU tensor. "
                 "There is deliberately no CPU fallback -- the CPU oracle lives in oracle/ and is test-only.")
+
+
+def require_int32_masks(*masks):
+    """The kernels read a mask's words as int32: a float mask (the reference's own `mask.float()`) would have its bit
+    pattern taken for an integer (1.0f = 1065353216) and scale the latent by it silently."""
+    import torch
+    for m in masks:
+        if m.dtype != torch.int32:
+            raise TypeError("masks must be int32 like the router's (RouterTriple.py:92)")

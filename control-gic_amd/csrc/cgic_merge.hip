@@ -225,11 +225,11 @@ extern "C" int cgic_grain_merge_f32(const float *h_coarse, const float *h_medium
                                     int C, int64_t h, int64_t w, float *out, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_grain_merge_f32");
-    CGIC_REQUIRE(h_coarse && h_medium && h_fine && mask_c && mask_m && mask_f && out, CGIC_ERR_INVALID, "grain_merge: NULL tensor");
     CGIC_REQUIRE(B >= 0 && C > 0 && h > 0 && w > 0 && h % 4 == 0 && w % 4 == 0, CGIC_ERR_INVALID,
                  "grain_merge: fine grid %lldx%lld must be positive multiples of 4", (long long)h, (long long)w);
     const int64_t total = B * C * h * (w >> 2);
-    if (total == 0) return CGIC_OK;
+    if (total == 0) return CGIC_OK;                   // (an empty batch: its tensors have no storage, NULL is what arrives)
+    CGIC_REQUIRE(h_coarse && h_medium && h_fine && mask_c && mask_m && mask_f && out, CGIC_ERR_INVALID, "grain_merge: NULL tensor");
     int nblk = (int)((total + 255) / 256);
     if (nblk > 8192) nblk = 8192;
     hipLaunchKernelGGL(grain_merge_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, h_coarse, h_medium, h_fine,
@@ -247,12 +247,12 @@ static int stream_grid(int64_t total)
 extern "C" int cgic_avgpool_f32(const float *x, int64_t planes, int64_t H, int64_t W, int k, float *out, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_avgpool_f32");
-    CGIC_REQUIRE(x && out, CGIC_ERR_INVALID, "avgpool: NULL tensor");
     CGIC_REQUIRE(k == 2 || k == 4, CGIC_ERR_UNSUPPORTED, "avgpool: window %d; the decoder uses 4 and 2 (decoder.py:304-305)", k);
     CGIC_REQUIRE(planes >= 0 && H > 0 && W > 0 && H % k == 0 && W % k == 0, CGIC_ERR_INVALID,
                  "avgpool: %lldx%lld is not a multiple of the window", (long long)H, (long long)W);
     const int64_t total = planes * (H / k) * (W / k);
     if (total == 0) return CGIC_OK;
+    CGIC_REQUIRE(x && out, CGIC_ERR_INVALID, "avgpool: NULL tensor");
     hipLaunchKernelGGL(avgpool_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, planes, H, W, k, out);
     return launch_check("avgpool_kernel");
 }
@@ -261,18 +261,16 @@ extern "C" int cgic_decoder_blend_medium_f32(const float *h, const float *h_medi
                                              int64_t B, int C, int64_t hh, int64_t ww, float *out, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_decoder_blend_medium_f32");
-    CGIC_REQUIRE(h && h_medium && mask_c && mask_m && out, CGIC_ERR_INVALID, "decoder_blend_medium: NULL tensor");
     CGIC_REQUIRE(B >= 0 && C > 0 && hh > 0 && ww > 0 && hh % 2 == 0 && ww % 2 == 0, CGIC_ERR_INVALID,
                  "decoder_blend_medium: medium grid %lldx%lld (need even height and width)", (long long)hh, (long long)ww);
+    const int64_t total = B * C * hh * (ww % 4 != 0 ? ww >> 1 : ww >> 2);     // one thread = 2 or 4 consecutive x
+    if (total == 0) return CGIC_OK;
+    CGIC_REQUIRE(h && h_medium && mask_c && mask_m && out, CGIC_ERR_INVALID, "decoder_blend_medium: NULL tensor");
     if (ww % 4 != 0) {
-        const int64_t total2 = B * C * hh * (ww >> 1);
-        if (total2 == 0) return CGIC_OK;
-        hipLaunchKernelGGL(decoder_blend_medium2_kernel, dim3(stream_grid(total2)), dim3(256), 0, (hipStream_t)stream, h, h_medium,
+        hipLaunchKernelGGL(decoder_blend_medium2_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, h, h_medium,
                            mask_c, mask_m, B, C, hh, ww, out);
         return launch_check("decoder_blend_medium2_kernel");
     }
-    const int64_t total = B * C * hh * (ww >> 2);
-    if (total == 0) return CGIC_OK;
     hipLaunchKernelGGL(decoder_blend_kernel<false>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, h, h_medium, mask_c,
                        mask_m, (const int32_t *)nullptr, B, C, hh, ww, out);
     return launch_check("decoder_blend_kernel<medium>");
@@ -283,11 +281,11 @@ extern "C" int cgic_decoder_blend_fine_f32(const float *h, const float *h_fine, 
                                            cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_decoder_blend_fine_f32");
-    CGIC_REQUIRE(h && h_fine && mask_c && mask_m && mask_f && out, CGIC_ERR_INVALID, "decoder_blend_fine: NULL tensor");
     CGIC_REQUIRE(B >= 0 && C > 0 && hh > 0 && ww > 0 && hh % 4 == 0 && ww % 4 == 0, CGIC_ERR_INVALID,
                  "decoder_blend_fine: fine grid %lldx%lld must be positive multiples of 4", (long long)hh, (long long)ww);
     const int64_t total = B * C * hh * (ww >> 2);
     if (total == 0) return CGIC_OK;
+    CGIC_REQUIRE(h && h_fine && mask_c && mask_m && mask_f && out, CGIC_ERR_INVALID, "decoder_blend_fine: NULL tensor");
     hipLaunchKernelGGL(decoder_blend_kernel<true>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, h, h_fine, mask_c,
                        mask_m, mask_f, B, C, hh, ww, out);
     return launch_check("decoder_blend_kernel<fine>");

@@ -133,9 +133,10 @@ extern "C" int cgic_vq_backward_f32(const float *z, int64_t B, int64_t hw, const
                                     float *g_z, float *g_codebook, void *workspace, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_vq_backward_f32");
-    CGIC_REQUIRE(z && codebook && indices, CGIC_ERR_INVALID, "vq_backward: z, codebook and indices must not be NULL");
-    CGIC_REQUIRE(e_dim == 4 && K > 0 && K <= 2048, CGIC_ERR_UNSUPPORTED, "vq_backward: needs a [K<=2048, 4] codebook (K=%d, e_dim=%d)", K, e_dim);
     CGIC_REQUIRE(B >= 0 && hw >= 0, CGIC_ERR_INVALID, "vq_backward: negative shape");
+    // (an empty batch has no latent and no indices: a tensor library hands over NULL for both)
+    CGIC_REQUIRE(codebook && ((z && indices) || B * hw == 0), CGIC_ERR_INVALID, "vq_backward: z, codebook and indices must not be NULL");
+    CGIC_REQUIRE(e_dim == 4 && K > 0 && K <= 2048, CGIC_ERR_UNSUPPORTED, "vq_backward: needs a [K<=2048, 4] codebook (K=%d, e_dim=%d)", K, e_dim);
     CGIC_REQUIRE(!g_codebook || workspace, CGIC_ERR_INVALID, "vq_backward: the codebook gradient needs the workspace");
     const int64_t N = B * hw;
     hipStream_t s = (hipStream_t)stream;

@@ -41,6 +41,7 @@ def decoder_blend_medium(h, h_medium, mask, out=None):
     _lib.require_device(h, h_medium, mask[0], mask[1])
     h, hm = h.contiguous().float(), h_medium.contiguous().float()
     mc, mm = mask[0].contiguous(), mask[1].contiguous()
+    _lib.require_int32_masks(mc, mm)
     B, C, hh, ww = h.shape
     if tuple(hm.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 2) * (ww // 2) or mm.numel() != B * hh * ww:
         raise ValueError("decoder_blend_medium: h, h_medium on the medium grid; mask[0] at half of it, mask[1] on it")
@@ -58,6 +59,7 @@ def decoder_blend_fine(h, h_fine, mask, out=None):
     _lib.require_device(h, h_fine, *mask)
     h, hf = h.contiguous().float(), h_fine.contiguous().float()
     mc, mm, mf = (m.contiguous() for m in mask)
+    _lib.require_int32_masks(mc, mm, mf)
     B, C, hh, ww = h.shape
     if tuple(hf.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 4) * (ww // 4) or mm.numel() != B * (hh // 2) * (ww // 2) \
             or mf.numel() != B * hh * ww:

@@ -391,9 +391,12 @@ def grain_merge(h_coarse: torch.Tensor, h_medium: torch.Tensor, h_fine: torch.Te
     _lib.require_device(h_coarse, h_medium, h_fine, mask_c, mask_m, mask_f)
     hc, hm, hf = (t.contiguous().float() for t in (h_coarse, h_medium, h_fine))
     mc, mm, mf = (m.contiguous() for m in (mask_c, mask_m, mask_f))
+    _lib.require_int32_masks(mc, mm, mf)
     B, C, h, w = hf.shape
     if tuple(hc.shape) != (B, C, h // 4, w // 4) or tuple(hm.shape) != (B, C, h // 2, w // 2):
         raise ValueError("h_coarse / h_medium must be the fine map's shape divided by 4 / 2")
+    if mc.numel() != B * (h // 4) * (w // 4) or mm.numel() != B * (h // 2) * (w // 2) or mf.numel() != B * h * w:
+        raise ValueError("grain_merge: masks at 1/4, 1/2, 1/1 of the fine grid, one per image")
     out = torch.empty_like(hf)
     with torch.cuda.device(hf.device):
         _lib.call("cgic_grain_merge_f32", _lib.ptr(hc), _lib.ptr(hm), _lib.ptr(hf), _lib.ptr(mc), _lib.ptr(mm),
@@ -430,7 +433,8 @@ grain_merge.register_autograd(_grain_merge_bwd, setup_context=_grain_merge_setup
 
 @torch.library.custom_op("cgic::avg_pool", mutates_args=(), device_types=_DEV)
 def avg_pool(x: torch.Tensor, k: int) -> torch.Tensor:
-    """torch.nn.AvgPool2d(k, k, 0) for k in (2, 4) (decoder.py:304-305,366-367): row-major window sum / k^2, bit-identical to the CPU kernel"""
+    """torch.nn.AvgPool2d(k, k, 0) for k in (2, 4) (decoder.py:304-305,366-367): row-major window sum / k^2, bit-identical to the CPU kernel;
+    H and W must be multiples of k (the decoder's are; cgic_avgpool_f32 refuses anything else)"""
     _lib.require_device(x)
     x = x.contiguous().float()
     B, C, H, W = x.shape
@@ -448,16 +452,11 @@ def _(x, k):
 
 def _avg_pool_setup(ctx, inputs, output):
     ctx.k = inputs[1]
-    ctx.hw = tuple(inputs[0].shape[-2:])
 
 
 def _avg_pool_bwd(ctx, g):
-    k = ctx.k
-    gx = (g * (1.0 / (k * k))).repeat_interleave(k, dim=-2).repeat_interleave(k, dim=-1)
-    H, W = ctx.hw
-    if gx.shape[-2] != H or gx.shape[-1] != W:                           # rows / columns the pool dropped get no gradient
-        gx = torch.nn.functional.pad(gx, (0, W - gx.shape[-1], 0, H - gx.shape[-2]))
-    return gx, None
+    k = ctx.k                                                            # (H and W are multiples of k: the forward refuses others)
+    return (g * (1.0 / (k * k))).repeat_interleave(k, dim=-2).repeat_interleave(k, dim=-1), None
 
 
 avg_pool.register_autograd(_avg_pool_bwd, setup_context=_avg_pool_setup)
@@ -469,6 +468,7 @@ def decoder_blend_medium(h: torch.Tensor, h_medium: torch.Tensor, mask_c: torch.
     _lib.require_device(h, h_medium, mask_c, mask_m)
     h, hm = h.contiguous().float(), h_medium.contiguous().float()
     mc, mm = mask_c.contiguous(), mask_m.contiguous()
+    _lib.require_int32_masks(mc, mm)
     B, C, hh, ww = h.shape
     if tuple(hm.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 2) * (ww // 2) or mm.numel() != B * hh * ww:
         raise ValueError("decoder_blend_medium: h, h_medium on the medium grid; mask_c at half of it, mask_m on it")
@@ -503,6 +503,7 @@ def decoder_blend_fine(h: torch.Tensor, h_fine: torch.Tensor, mask_c: torch.Tens
     _lib.require_device(h, h_fine, mask_c, mask_m, mask_f)
     h, hf = h.contiguous().float(), h_fine.contiguous().float()
     mc, mm, mf = (m.contiguous() for m in (mask_c, mask_m, mask_f))
+    _lib.require_int32_masks(mc, mm, mf)
     B, C, hh, ww = h.shape
     if tuple(hf.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 4) * (ww // 4) or mm.numel() != B * (hh // 2) * (ww // 2) \
             or mf.numel() != B * hh * ww:

@@ -74,12 +74,27 @@ class _VQFunction(torch.autograd.Function):
 def vq_backward(z, weight, idx, g_zq, g_loss, beta, legacy, want_gz=True, want_gw=True):
     """(g_z [B,C,h,w] or None, g_codebook [K,C] or None) -- cgic_vq_backward_f32"""
     _lib.require_device(z, weight, idx, g_zq, g_loss)
+    if z.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise TypeError(f"vq_backward: fp32 z and codebook like the forward's; got {z.dtype}/{weight.dtype}")
+    if idx.dtype != torch.int64:
+        raise TypeError(f"vq_backward: int64 indices like the forward's; got {idx.dtype}")
     B, C, h, w = z.shape
+    if tuple(weight.shape[1:]) != (4,) or C != 4:
+        raise ValueError(f"vq_backward: z [B, 4, h, w] and a [K, 4] codebook; got {tuple(z.shape)} / {tuple(weight.shape)}")
+    if idx.numel() != B * h * w:
+        raise ValueError(f"vq_backward: {idx.numel()} indices for {B * h * w} vectors")
+    for name, g in (("g_zq", g_zq), ("g_loss", g_loss)):
+        if g is not None and g.dtype != torch.float32:
+            raise TypeError(f"vq_backward: fp32 {name} like the forward's outputs; got {g.dtype}")
+    if g_zq is not None and tuple(g_zq.shape) != tuple(z.shape):
+        raise ValueError(f"vq_backward: g_zq {tuple(g_zq.shape)} is not z's shape {tuple(z.shape)}")
+    if g_loss is not None and g_loss.numel() != 1:
+        raise ValueError(f"vq_backward: g_loss is one number; got {tuple(g_loss.shape)}")
     z = z.contiguous()
     wt = weight.detach().contiguous()
     dev = z.device
-    g_zq = None if g_zq is None else g_zq.contiguous().float()
-    g_loss = None if g_loss is None else g_loss.reshape(1).contiguous().float()
+    g_zq = None if g_zq is None else g_zq.contiguous()
+    g_loss = None if g_loss is None else g_loss.reshape(1).contiguous()
     gz = torch.empty_like(z) if want_gz else None
     gw = torch.empty_like(wt) if want_gw else None
     N = B * h * w

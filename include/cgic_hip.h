@@ -225,8 +225,14 @@ int cgic_vq_forward_valu_f32(const float *z, int64_t B, int64_t hw, const float 
  *   g_z    device [B, 4, hw] fp32 or NULL   = g_zq + g_loss * (-2/n * w_z) * (e[idx] - z)      (bit-identical to that expression)
  *   g_codebook device [K, 4] fp32 or NULL   = g_loss * (2/n * w_e) * sum_{idx[n] = k} (e[idx] - z_n); n = B*hw*4,
  *          (w_z, w_e) = (1, beta) if legacy else (beta, 1).  Deterministic (fixed-point LDS accumulation per workgroup,
- *          workgroup tables added in a fixed order), unlike torch.index_add_'s fp32 atomics; accurate to ~1e-9 relative
- *          of the largest |e - z| per term.
+ *          workgroup tables added in a fixed order), unlike torch.index_add_'s fp32 atomics.  Workgroup j of
+ *          min(256, ceil(N/2048)) takes the vectors [j*per, (j+1)*per), per = ceil(N/workgroups), N = B*hw, and rounds every
+ *          difference to a multiple of 2^(e_Mj - 30), e_Mj the exponent of its range's largest |e - z|: a term is
+ *          off by at most 2^(e_Mj - 31), the sums are exact, one fp32 rounding at the end.  (A range whose largest
+ *          difference is subnormal, below 2^-126, contributes zero.)
+ *   g_z is the expression above in IEEE arithmetic (NaN exactly where it is NaN; g_loss = inf: inf * 0 is NaN).  An Inf or
+ *          NaN difference makes the codebook gradient of its whole range of vectors meaningless (no contract yet).
+ *   B*hw == 0: g_codebook is zeroed, nothing else is touched (z, indices may be NULL).
  *   workspace device, cgic_vq_backward_workspace_bytes(B*hw, K) bytes, or NULL iff g_codebook == NULL */
 size_t cgic_vq_backward_workspace_bytes(int64_t n_vectors, int K);
 int cgic_vq_backward_f32(const float *z, int64_t B, int64_t hw, const float *codebook, int K, int e_dim,
