@@ -20,6 +20,7 @@ from . import rate
 from .rate import RateTable, rate_table, grain_indices, gather_grain_indices, choose, default_candidates, compress_to_bpp
 from .rate import RateCurve, rate_curve, ratio_for_rank, router_ranks
 from .rate import BppRoute, budget_bytes, route_to_bpp
+from .highres import to_frames, paste_tiles
 from .rate import TiledRateCurve, rate_curve_tiled, tiled_settings, compress_tiled_to_bpp
 
 __all__ = ["VectorQuantize2", "VectorQuantizer", "TripleGrainFixedEntropyRouter", "Entropy", "entropy_maps", "entropy_maps_u8", "entropy_maps_tiles",
@@ -27,4 +28,4 @@ __all__ = ["VectorQuantize2", "VectorQuantizer", "TripleGrainFixedEntropyRouter"
            "HotPathPipeline", "LaneStream", "GraphLanes", "capture_graph", "decoder_mode", "install", "compress_batch", "grain_merge", "avg_pool", "decoder_blend_medium", "decoder_blend_fine", "rate", "RateTable", "rate_table", "grain_indices", "gather_grain_indices", "choose",
            "default_candidates", "compress_to_bpp", "RateCurve", "rate_curve", "ratio_for_rank", "router_ranks",
            "BppRoute", "budget_bytes", "route_to_bpp",
-           "TiledRateCurve", "rate_curve_tiled", "tiled_settings", "compress_tiled_to_bpp", "highres", "container", "CgicError", "LIB_PATH"]
+           "TiledRateCurve", "rate_curve_tiled", "tiled_settings", "compress_tiled_to_bpp", "to_frames", "paste_tiles", "highres", "container", "CgicError", "LIB_PATH"]

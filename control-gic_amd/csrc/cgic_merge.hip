@@ -216,6 +216,116 @@ __global__ __launch_bounds__(256) void cut_tiles_kernel(CutArgs a)
     }
 }
 
+// ---- cgic_paste_tiles: blend + normalise + clamp + unpad (+ uint8 frames) of the tiling driver as ONE pass ------------------
+// inference_high_resolution.py:231-255 accumulates `tile * weights` and the weights into two padded float32 images, divides,
+// clamps and slices the pad off; write_images (:103) makes the uint8 frame.  The tiles do not overlap, so per value the loop is
+// the closed form of paste_value below (include/cgic_hip.h): the same roundings in the same order, bit-identical to the CPU loop.
+// One workgroup column per tile (blockIdx.y: the descriptor is wave-uniform by construction and stays on the scalar unit),
+// blockIdx.z = image; one thread = 4 consecutive pixels of one tile row across the three planes: three 16-byte loads, the weight
+// product once per pixel for three channels, 16-byte fp32 stores / dword uint8 stores where the unpad shift leaves the output
+// address aligned, element-wise otherwise.  No workgroup waits on another, no atomics.  The file is compiled without
+// contraction: (double)p * w is a product followed by one conversion.
+constexpr int kPasteMaxTiles = 96;
+struct PasteTile {           // 40 bytes: 96 of them and the header stay below 4 KB of kernel arguments
+    const float *src;        // element (image 0, this tile, channel 0, row 0)
+    const double *wx, *wy;   // [tw], [th] or both NULL
+    unsigned int stride4;    // image_stride / 4
+    int y0, x0;              // the tile's origin in UNPADDED output coordinates (negative inside the pad)
+    unsigned short th, tw;
+};
+struct PasteArgs {
+    float *out_f32;          // [N,3,H,W] or NULL
+    unsigned char *out_u8;   // [N,H,W,3] or NULL
+    int H, W;
+    PasteTile t[kPasteMaxTiles];
+};
+static_assert(sizeof(PasteTile) == 40 && sizeof(PasteArgs) <= 4096, "paste_tiles: the descriptors travel as kernel arguments");
+
+__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }       // NaN stays NaN
+
+__device__ __forceinline__ float paste_value(float p, double w)
+{
+    const float acc = (float)((double)p * w);      // rec += tile * wts: float32 += float64 product onto 0
+    const float con = (float)w;                    // contrib += wts
+    return clamp01(__fdiv_rn(acc, con));
+}
+
+__device__ __forceinline__ unsigned int frame_byte(float v)       // (255 * x).astype(uint8) on a clamped value; NaN -> 0
+{
+    return v == v ? (unsigned int)(255.0f * v) : 0u;
+}
+
+__global__ __launch_bounds__(256) void paste_tiles_kernel(PasteArgs a)
+{
+    const PasteTile &t = a.t[blockIdx.y];
+    const int64_t n = blockIdx.z;
+    const int H = a.H, W = a.W;
+    const unsigned int th = t.th, tw = t.tw, q = tw >> 2, items = th * q;
+    const size_t plane = (size_t)th * tw;
+    const float *src = t.src + n * ((int64_t)t.stride4 << 2);
+    const bool weighted = t.wx != nullptr;
+    for (unsigned int item = blockIdx.x * 256u + threadIdx.x; item < items; item += gridDim.x * 256u) {
+        const unsigned int r = item / q, c4 = (item - r * q) * 4;
+        const int oy = t.y0 + (int)r, ox = t.x0 + (int)c4;
+        if (oy < 0 || oy >= H || ox + 3 < 0 || ox >= W) continue;         // the unit lies in the pad: dropped unread
+        float v[3][4];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float4 p = *reinterpret_cast<const float4 *>(src + ch * plane + (size_t)r * tw + c4);
+            v[ch][0] = p.x; v[ch][1] = p.y; v[ch][2] = p.z; v[ch][3] = p.w;
+        }
+        if (weighted) {
+            const double wyv = t.wy[r];
+            const double2 wa = *reinterpret_cast<const double2 *>(t.wx + c4), wb = *reinterpret_cast<const double2 *>(t.wx + c4 + 2);
+            const double w[4] = {wyv * wa.x, wyv * wa.y, wyv * wb.x, wyv * wb.y};
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[ch][j] = paste_value(v[ch][j], w[j]);
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[ch][j] = clamp01(v[ch][j]);
+        }
+        const bool whole = ox >= 0 && ox + 3 < W;
+        if (a.out_f32) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                float *row = a.out_f32 + ((n * 3 + ch) * (int64_t)H + oy) * W;
+                if (whole && (((uintptr_t)(row + ox)) & 15u) == 0) {
+                    *reinterpret_cast<float4 *>(row + ox) = make_float4(v[ch][0], v[ch][1], v[ch][2], v[ch][3]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (ox + j >= 0 && ox + j < W) row[ox + j] = v[ch][j];
+                }
+            }
+        }
+        if (a.out_u8) {
+            unsigned char *row = a.out_u8 + (n * (int64_t)H + oy) * W * 3;
+            unsigned int b[4][3];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) b[j][ch] = frame_byte(v[ch][j]);
+            if (whole && (((uintptr_t)(row + (int64_t)ox * 3)) & 3u) == 0) {
+                unsigned int *d = reinterpret_cast<unsigned int *>(row + (int64_t)ox * 3);
+                d[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
+                d[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
+                d[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (ox + j >= 0 && ox + j < W) {
+                        unsigned char *d = row + (int64_t)(ox + j) * 3;
+                        d[0] = (unsigned char)b[j][0]; d[1] = (unsigned char)b[j][1]; d[2] = (unsigned char)b[j][2];
+                    }
+            }
+        }
+    }
+}
+
 }  // namespace cgic
 
 using namespace cgic;
@@ -327,4 +437,72 @@ extern "C" int cgic_cut_tiles(const void *x, int is_u8, int64_t N, int64_t H, in
     else
         hipLaunchKernelGGL(cut_tiles_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return launch_check("cut_tiles_kernel");
+}
+
+extern "C" int cgic_tile_weights_host(int n, int axis, double *out)
+{
+    CGIC_REQUIRE(out, CGIC_ERR_INVALID, "tile_weights_host: NULL output");
+    CGIC_REQUIRE(n >= 1, CGIC_ERR_INVALID, "tile_weights_host: extent %d", n);
+    CGIC_REQUIRE(axis == 0 || axis == 1, CGIC_ERR_INVALID, "tile_weights_host: axis %d (0 = x, 1 = y)", axis);
+    // _gaussian_weights (:127-143) term by term in the order Python evaluates it; libm's exp, no contraction (Makefile)
+    const double var = 0.01;
+    const double mid = axis == 0 ? (double)(n - 1) / 2 : (double)n / 2;
+    const double nn = (double)((int64_t)n * n);
+    const double norm = sqrt(2 * 3.141592653589793 * var);
+    for (int x = 0; x < n; ++x) {
+        const double d = (double)x - mid;
+        out[x] = exp(-d * d / nn / (2 * var)) / norm;
+    }
+    return CGIC_OK;
+}
+
+extern "C" int cgic_paste_tiles(int64_t N, int64_t H, int64_t W, int ntiles, const cgic_paste_tile *tiles, float *out_f32,
+                                unsigned char *out_u8, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_paste_tiles");
+    CGIC_REQUIRE(tiles, CGIC_ERR_INVALID, "paste_tiles: NULL argument");
+    CGIC_REQUIRE(out_f32 || out_u8, CGIC_ERR_INVALID, "paste_tiles: no output (out_f32 and out_u8 are both NULL)");
+    CGIC_REQUIRE(((uintptr_t)out_f32 & 3u) == 0, CGIC_ERR_INVALID, "paste_tiles: out_f32 not aligned");
+    CGIC_REQUIRE(N >= 0 && H > 0 && W > 0 && H < (1 << 30) && W < (1 << 30), CGIC_ERR_INVALID, "paste_tiles: bad image shape");
+    CGIC_REQUIRE(ntiles >= 1 && ntiles <= kPasteMaxTiles, CGIC_ERR_UNSUPPORTED, "paste_tiles: %d tiles (1..%d)", ntiles, kPasteMaxTiles);
+    CGIC_REQUIRE(N <= 65535, CGIC_ERR_UNSUPPORTED, "paste_tiles: more than 65535 images");
+    PasteArgs a;
+    a.out_f32 = out_f32; a.out_u8 = out_u8; a.H = (int)H; a.W = (int)W;
+    int64_t clip[kPasteMaxTiles][4];                  // the tile clipped to the image: y0, y1, x0, x1 (empty when y0 >= y1 or x0 >= x1)
+    unsigned int most = 0;
+    for (int k = 0; k < ntiles; ++k) {
+        const cgic_paste_tile &t = tiles[k];
+        CGIC_REQUIRE(t.src && t.th > 0 && t.tw > 0 && t.tw % 4 == 0, CGIC_ERR_INVALID,
+                     "paste_tiles: tile %d: %dx%d (width must be a positive multiple of 4)", k, t.th, t.tw);
+        CGIC_REQUIRE(t.th <= 65535 && t.tw <= 65535, CGIC_ERR_UNSUPPORTED, "paste_tiles: tile %d: %dx%d (at most 65535 a side)", k, t.th, t.tw);
+        CGIC_REQUIRE(((uintptr_t)t.src & 15u) == 0 && t.image_stride >= 0 && t.image_stride % 4 == 0, CGIC_ERR_INVALID,
+                     "paste_tiles: tile %d: source not 16-byte aligned or image stride not a multiple of 4", k);
+        CGIC_REQUIRE(t.image_stride < ((int64_t)1 << 34), CGIC_ERR_UNSUPPORTED, "paste_tiles: tile %d: image stride beyond 2^34", k);
+        CGIC_REQUIRE((t.wx != nullptr) == (t.wy != nullptr), CGIC_ERR_INVALID, "paste_tiles: tile %d: wx and wy must both be set or both be NULL", k);
+        CGIC_REQUIRE(((uintptr_t)t.wx & 15u) == 0 && ((uintptr_t)t.wy & 7u) == 0, CGIC_ERR_INVALID,
+                     "paste_tiles: tile %d: weights not aligned (wx 16 bytes, wy 8)", k);
+        CGIC_REQUIRE(t.y0 > -(1 << 30) && t.x0 > -(1 << 30) && t.y0 < (1 << 30) && t.x0 < (1 << 30), CGIC_ERR_INVALID, "paste_tiles: tile %d origin", k);
+        clip[k][0] = t.y0 > 0 ? t.y0 : 0; clip[k][1] = (int64_t)t.y0 + t.th < H ? (int64_t)t.y0 + t.th : H;
+        clip[k][2] = t.x0 > 0 ? t.x0 : 0; clip[k][3] = (int64_t)t.x0 + t.tw < W ? (int64_t)t.x0 + t.tw : W;
+        PasteTile &d = a.t[k];
+        d.src = t.src; d.wx = t.wx; d.wy = t.wy; d.stride4 = (unsigned int)(t.image_stride / 4);
+        d.y0 = t.y0; d.x0 = t.x0; d.th = (unsigned short)t.th; d.tw = (unsigned short)t.tw;
+        const unsigned int items = (unsigned int)t.th * (unsigned int)(t.tw / 4);
+        if (items > most) most = items;
+    }
+    // one tile per pixel: the closed form (and a race-free launch) needs the clipped tiles pairwise disjoint
+    for (int k = 0; k < ntiles; ++k) {
+        if (clip[k][0] >= clip[k][1] || clip[k][2] >= clip[k][3]) continue;
+        for (int j = 0; j < k; ++j) {
+            if (clip[j][0] >= clip[j][1] || clip[j][2] >= clip[j][3]) continue;
+            const bool apart = clip[k][1] <= clip[j][0] || clip[j][1] <= clip[k][0] || clip[k][3] <= clip[j][2] || clip[j][3] <= clip[k][2];
+            CGIC_REQUIRE(apart, CGIC_ERR_UNSUPPORTED, "paste_tiles: tiles %d and %d overlap (the reference's grid never does)", j, k);
+        }
+    }
+    for (int k = ntiles; k < kPasteMaxTiles; ++k) a.t[k] = a.t[ntiles - 1];
+    if (N == 0) return CGIC_OK;
+    unsigned int nblk = (most + 255) / 256;            // of the largest tile; smaller tiles' surplus workgroups leave at once
+    if (nblk > 4096) nblk = 4096;                      // grid-stride beyond
+    hipLaunchKernelGGL(paste_tiles_kernel, dim3(nblk, (unsigned)ntiles, (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_check("paste_tiles_kernel");
 }

@@ -62,6 +62,128 @@ def gaussian_weights(tile_width, tile_height, device=None):
     return wts.to(device).expand(1, 3, tile_height, tile_width)
 
 
+_factors = {}            # (device, n, axis) -> float64 [n]: the one-dimensional factors of gaussian_weights, made by the library
+
+
+def tile_weight_factors(n, axis, device=None):
+    """float64 [n]: the one-dimensional factors of gaussian_weights from the library (cgic_tile_weights_host) -- axis 0 = x
+    (midpoint (n-1)/2), axis 1 = y (midpoint n/2): gaussian_weights(tw, th)[0, 0] == outer(factors(th, 1), factors(tw, 0)), bit for
+    bit.  device None / "cpu": a host tensor; a HIP device: uploaded once and cached per (device, n, axis).  The first upload is a
+    host-to-device copy and must happen OUTSIDE a graph capture (TiledCall makes its factors when it is built; otherwise call this,
+    or paste once eagerly, before capturing)"""
+    import ctypes
+    dev = torch.device("cpu" if device is None else device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (dev, int(n), int(axis))
+    t = _factors.get(key)
+    if t is None:
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"tile_weight_factors({n}, {axis}): the factors of this tile extent are not on {dev} yet and a stream is being "
+                               "captured -- their first upload is a host-to-device copy and must happen outside a graph capture (paste once "
+                               "eagerly, or call tile_weight_factors for every tile extent, before capturing)")
+        host = (ctypes.c_double * int(n))() if n >= 1 else None
+        _lib.call("cgic_tile_weights_host", int(n), int(axis), host)
+        t = torch.tensor(list(host), dtype=torch.float64).to(dev)
+        _factors[key] = t
+    return t
+
+
+def _shape_groups(tiles):
+    """the shape groups [((th, tw), tile indices)] of a tile grid, largest first (the order of cut_groups / compress_tiled_batch)"""
+    by_shape = {}
+    for i, (_, _, th, tw) in enumerate(tiles):
+        by_shape.setdefault((th, tw), []).append(i)
+    return sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+
+
+def _check_cover(H, W, top, left, tiles):
+    """every pixel of the unpadded image belongs to exactly one tile (the closed form of cgic_paste_tiles holds for such grids only)"""
+    clipped = []
+    for (y, x, th, tw) in tiles:
+        y0, y1, x0, x1 = max(y - top, 0), min(y - top + th, H), max(x - left, 0), min(x - left + tw, W)
+        if y0 < y1 and x0 < x1:
+            clipped.append((y0, y1, x0, x1))
+    for k, (y0, y1, x0, x1) in enumerate(clipped):
+        for (v0, v1, u0, u1) in clipped[:k]:
+            if not (y1 <= v0 or v1 <= y0 or x1 <= u0 or u1 <= x0):
+                raise ValueError("paste_tiles: tiles overlap (the reference's grid never does: inference_high_resolution.py:112-125)")
+    if sum((y1 - y0) * (x1 - x0) for y0, y1, x0, x1 in clipped) != H * W:
+        raise ValueError(f"paste_tiles: the tile grid does not cover the {H}x{W} image (a pixel without a tile would be left unwritten)")
+
+
+def _paste(pixels, H, W, top, left, tiles, groups, N, weighted, frames, out):
+    if torch.is_tensor(pixels):
+        pixels = [pixels]
+    if len(pixels) != len(groups):
+        raise ValueError(f"paste_tiles: {len(pixels)} tile batches for {len(groups)} shape groups")
+    for ((th, tw), idxs), b in zip(groups, pixels):
+        if tuple(b.shape) != (N * len(idxs), 3, th, tw) or b.dtype != torch.float32 or not b.is_contiguous():
+            raise ValueError(f"paste_tiles: the batch of the {th}x{tw} tiles must be contiguous fp32 [{N * len(idxs)},3,{th},{tw}] (image-major), "
+                             f"got {b.dtype} {tuple(b.shape)}")
+        if tw % 4:
+            raise ValueError(f"paste_tiles: tile width {tw} is not a multiple of 4")
+    _lib.require_device(*pixels)
+    dev = pixels[0].device
+    if any(b.device != dev for b in pixels):
+        raise ValueError("paste_tiles: the tile batches live on different devices")
+    want, dt = ((N, H, W, 3), torch.uint8) if frames else ((N, 3, H, W), torch.float32)
+    if out is None:
+        out = torch.empty(want, dtype=dt, device=dev)
+    elif tuple(out.shape) != want or out.dtype != dt or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"paste_tiles: out must be contiguous {dt} {list(want)} on {dev}")
+    desc = []
+    for ((th, tw), idxs), b in zip(groups, pixels):
+        wx = tile_weight_factors(tw, 0, dev).data_ptr() if weighted else None
+        wy = tile_weight_factors(th, 1, dev).data_ptr() if weighted else None
+        T, per = len(idxs), 3 * th * tw
+        for k, i in enumerate(idxs):
+            desc.append(_lib.PasteTile(b.data_ptr() + k * per * 4, T * per, wx, wy, tiles[i][0] - top, tiles[i][1] - left, th, tw))
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream(dev)
+        for at in range(0, len(desc), 96):                       # (cgic_paste_tiles takes 96 tiles a launch)
+            part = desc[at:at + 96]
+            _lib.call("cgic_paste_tiles", N, H, W, len(part), (_lib.PasteTile * len(part))(*part),
+                      None if frames else out.data_ptr(), out.data_ptr() if frames else None, stream)
+    return out
+
+
+def paste_tiles(pixels, hw, tiles=None, groups=None, N=1, weighted=True, frames=False, out=None, tile=TILE):
+    """the way out of the tiling driver -- blend, normalise, clamp, unpad (inference_high_resolution.py:231-255) and with frames=True
+    the uint8 conversion of write_images (:103) -- as ONE launch for all tiles of all N images (cgic_paste_tiles), bit-identical to
+    the reference's loop on the CPU.
+    pixels: per shape group one fp32 batch [N*T,3,th,tw], image-major (the layout of cut_groups / compress_tiled_batch: what a decoder
+    called once per group returns); hw = (H, W) of the unpadded image.  tiles (row-major (y, x, th, tw) in padded coordinates) and
+    groups ([((th, tw), tile indices)]) default to what cut_groups derives from hw and `tile`; given, the grid must cover the image.
+    weighted=False: no blend weights, the result is clamp(p, 0, 1) (what the loop would give if its weights cancelled exactly).
+    -> [N,3,H,W] fp32, or uint8 frames [N,H,W,3].  With `out` (that shape, contiguous) nothing is allocated and nothing synchronises:
+    capturable, once the weight factors of the tile extents are on the device (tile_weight_factors).  More than 96 tiles are several launches."""
+    H, W = int(hw[0]), int(hw[1])
+    (left, right, top, bottom), _ = compute_padding(H, W)
+    if tiles is None:
+        tiles = tile_grid(H + top + bottom, W + left + right, tile)
+    else:
+        _check_cover(H, W, top, left, tiles)
+    if groups is None:
+        groups = _shape_groups(tiles)
+    elif sorted(i for _, idxs in groups for i in idxs) != list(range(len(tiles))) or \
+            any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
+        raise ValueError("paste_tiles: groups must name every tile once, under its own shape")
+    return _paste(pixels, H, W, top, left, tiles, groups, int(N), weighted, frames, out)
+
+
+def to_frames(x, out=None):
+    """the untiled way out: x [N,3,H,W] fp32 -> uint8 frames [N,H,W,3] = (255 * x.clamp(0, 1).permute(0, 2, 3, 1)).astype(uint8), the
+    clamp of inference.py:163 followed by write_images (inference_high_resolution.py:103), as a one-tile unweighted cgic_paste_tiles
+    (NaN -> 0).  W must be a multiple of 4 (the reference's inputs are cropped to multiples of 16)"""
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise ValueError(f"to_frames takes fp32 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    if W % 4:
+        raise ValueError(f"to_frames: width {W} is not a multiple of 4")
+    return _paste([x.contiguous()], H, W, 0, 0, [(0, 0, H, W)], [((H, W), [0])], N, False, True, out)
+
+
 class TiledImage:
     """result of compress_tiled: per shape-group CompressedBatch + where each tile sits"""
 
@@ -399,6 +521,15 @@ class TiledCall:
         self._bins = _lib.linspace_bins()
         self._decode = bool(decode)
         self.decoded = None
+        for (th, tw), _ in self.groups:               # the blend factors of paste(): uploaded here, outside any capture
+            tile_weight_factors(tw, 0, dev), tile_weight_factors(th, 1, dev)
+
+    def paste(self, pixels, out=None, frames=False):
+        """the way out for this call's geometry: pixels = per shape group (self.groups order) the decoded tiles fp32 [N*T,3,th,tw]
+        -> [N,3,H,W] fp32, or uint8 frames [N,H,W,3] (paste_tiles: one launch, the reference's blend + clamp + unpad).  Capturable:
+        the weight factors were uploaded when this object was built; with `out` nothing is allocated"""
+        left, _, top, _ = self.pad
+        return _paste(pixels, self.H, self.W, top, left, self.tiles, self.groups, self.N, True, frames, out)
 
     def refresh_codebook(self):
         """after changing embedding.weight: rewrite the codebook image in place (HotCall / HotPathPipeline have the same method; __call__
@@ -452,12 +583,15 @@ class TiledCall:
         return out
 
 
-def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chain=False, decoder=None):
+def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chain=False, decoder=None, decode=None, frames=False):
     """inverse of compress_tiled_batch for TiledImages of one geometry (from it, or from N compress_tiled calls on images
     of one size, or rebuilt from containers): ONE decompress per shape group over all the images
-    -> list (per image) of per-tile (ind, masks, z_q); check=False: (that, [N * tiles] status tensor)"""
+    -> list (per image) of per-tile (ind, masks, z_q); check=False: (that, [N * tiles] status tensor).
+    decode(z_q [N*T,4,h,w], masks) -> pixels [N*T,3,th,tw]: called ONCE per shape group on the whole batch (not once per tile), then all
+    tiles of all images are pasted in one launch (paste_tiles: the reference's blend + clamp + unpad, :248-255) -> (per_image, rec) with
+    rec [N,3,H,W] fp32, or with frames=True the uint8 frames [N,H,W,3] write_images would save; check=False: (per_image, rec, status)"""
     if not tiled_list:
-        return []
+        return [] if decode is None else ([], None)
     first = tiled_list[0]
     for t in tiled_list[1:]:
         if t.tiles != first.tiles or [g[0] for g in t.groups] != [g[0] for g in first.groups] or \
@@ -507,11 +641,15 @@ def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chai
                 per_image[n][i] = (ind[j:j + 1], [m[j:j + 1] for m in masks], zq[j:j + 1])
     fork.join(outs)
     all_status = status_all if status_all is not None else torch.cat(statuses)
-    if not check:
-        return per_image, all_status
-    if int(all_status.abs().max()) != 0:
+    if check and int(all_status.abs().max()) != 0:
         raise RuntimeError("corrupt tile stream")
-    return per_image
+    if decode is None:
+        return per_image if check else (per_image, all_status)
+    groups = [(tuple(first.tiles[idxs[0]][2:]), idxs) for idxs, _, _ in first.groups]
+    pixels = [decode(zq, masks).contiguous() for _, masks, zq, _ in outs]          # ONE decoder call per shape group
+    left, _, top, _ = first.pad
+    rec = _paste(pixels, first.image_hw[0], first.image_hw[1], top, left, first.tiles, groups, N, True, frames, None)
+    return (per_image, rec) if check else (per_image, rec, all_status)
 
 
 def decompress_tiled(tiled, codec, decode=None, concurrent=False, check=True, chain=False, decoder=None):

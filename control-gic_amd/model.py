@@ -204,6 +204,9 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
     model.compress_batch = types.MethodType(compress_batch, model)
     model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)
     model.compress_tiled_to_bpp = types.MethodType(_rate.compress_tiled_to_bpp, model)
+    from . import highres as _highres
+    model.to_frames = _highres.to_frames                 # the way out: inference.py:163 + write_images (:103) as one launch
+    model.paste_tiles = _highres.paste_tiles             # ... and the tiled one (inference_high_resolution.py:231-255)
     model._cgic_codec = None
     model._cgic_codec_key = None
     return model

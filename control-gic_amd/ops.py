@@ -12,6 +12,7 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     nbytes = torch.ops.cgic.rate_curve(ind_c, ind_m, ind_f, e16, e8, 0.1, table)                          # [B,n8+1,5] bytes per medium rank
     mc, mm, mf, ind, choice = torch.ops.cgic.route_to_bpp(ind_c, ind_m, ind_f, e16, e8, 0.1, budget, table)  # the rank picked on the device
     ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
+    rec    = torch.ops.cgic.paste_tiles([tiles_of_group0, ...], H, W, N, 768, True, False)        # decoded tiles -> [N,3,H,W] (frames: uint8 [N,H,W,3])
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).
@@ -163,6 +164,21 @@ def gather_grain_indices(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.
 @gather_grain_indices.register_fake
 def _(ind_c, ind_m, ind_f, mask_c, mask_m, mask_f):
     return ind_f.new_empty((mask_f.shape[0], mask_f.shape[-2], mask_f.shape[-1]), dtype=torch.int64)
+
+
+@torch.library.custom_op("cgic::paste_tiles", mutates_args=(), device_types=_DEV)
+def paste_tiles(pixels: List[torch.Tensor], H: int, W: int, N: int, tile: int, weighted: bool, frames: bool) -> torch.Tensor:
+    """the way out of the tiling driver (inference_high_resolution.py:231-255, write_images :103) in one launch: pixels = per shape
+    group of the HxW image's `tile` grid (cut_groups order) fp32 [N*T,3,th,tw] -> [N,3,H,W] fp32, or uint8 frames [N,H,W,3]"""
+    from .highres import paste_tiles as _paste_tiles
+    return _paste_tiles([p.contiguous() for p in pixels], (H, W), N=N, weighted=weighted, frames=frames, tile=tile)
+
+
+@paste_tiles.register_fake
+def _(pixels, H, W, N, tile, weighted, frames):
+    if frames:
+        return pixels[0].new_empty((N, H, W, 3), dtype=torch.uint8)
+    return pixels[0].new_empty((N, 3, H, W), dtype=torch.float32)
 
 
 # ------------------------------------------------------------------------------------------------------------------

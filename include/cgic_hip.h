@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 12
+#define CGIC_ABI_VERSION 13
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -495,6 +495,47 @@ typedef struct cgic_tile {
 } cgic_tile;
 int cgic_cut_tiles(const void *x, int is_u8, int64_t N, int64_t H, int64_t W, int ntiles, const cgic_tile *tiles,
                    cgic_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Tiling driver, the way out (ABI 13): blend + normalise + clamp + unpad of inference_high_resolution.py:231-255 -- and the uint8
+ * conversion of write_images (:95-110, inference.py:163-164) -- as ONE launch for all tiles of all N images.  The script
+ * accumulates `decoded_tile * gaussian_weights` into a float32 image and the weights into a second one, divides, clamps and
+ * slices the pad off.  Its tiles never overlap, so every padded pixel belongs to exactly one tile and the loop is, per value p,
+ *     w   = wy[r] * wx[c]                 (float64 product, rounded once)
+ *     acc = (float)((double)p * w)        (float32 += float32 * float64 onto 0: computed in double, rounded once to float)
+ *     con = (float)w
+ *     out = clamp(acc / con, 0, 1)        (IEEE float32 divide)
+ *     u8  = (uint8) trunc(255.0f * out)   (float32 product, truncation)
+ * which is what the kernel evaluates: bit-identical to the loop on the CPU (the weights do NOT cancel: acc / con differs from p
+ * in about one value of five).  con is neither zero nor subnormal for tile extents 16 .. 768.
+ *
+ * cgic_tile_weights_host: host only, no device work.  The reference's one-dimensional factors (_gaussian_weights, :127-143)
+ *   of a tile extent n into out[n]: axis 0 = x (midpoint (n - 1) / 2), axis 1 = y (midpoint n / 2; the asymmetry is the
+ *   reference's), exp(-(x - mid) * (x - mid) / (n * n) / (2 * var)) / sqrt(2 * pi * var), var = 0.01, evaluated in the order
+ *   of the Python expression with libm's exp: bit-equal to the Python list in the same process.
+ *
+ * cgic_paste_tiles
+ *   tiles    host [ntiles] (1 .. 96): src = device address of the tile of image 0, fp32 [3,th,tw], 16-byte aligned;
+ *            image_stride = elements from there to the same tile of the next image (a multiple of 4, below 2^34);
+ *            wx [tw], wy [th] = device float64 factors (8-byte aligned), or BOTH NULL: no weighting, out = clamp(p, 0, 1);
+ *            (y0, x0) = the tile's origin in UNPADDED coordinates (negative inside the pad); th, tw in 1 .. 65535, tw % 4 == 0
+ *   out_f32  device [N,3,H,W] or NULL;  out_u8  device [N,H,W,3] or NULL; at least one of them
+ * Every pixel of a tile inside [0,H) x [0,W) is written; tile pixels inside the pad are dropped (the unpad of :255).  Pixels
+ * of the outputs that NO tile covers are left untouched.  The tiles, clipped to the image, must be pairwise disjoint
+ * (CGIC_ERR_UNSUPPORTED otherwise: the reference's grid never overlaps, and the closed form holds for one tile per pixel).
+ * NaN stays NaN in the fp32 output and becomes 0 in the uint8 output (numpy leaves a NaN -> uint8 cast unspecified; this is
+ * a definition, not the reference's); +inf -> 1 / 255, -inf -> 0.  N <= 65535.  All checks precede the launch; not available
+ * inside a launch group.
+ * ------------------------------------------------------------------------- */
+int cgic_tile_weights_host(int n, int axis, double *out);
+typedef struct cgic_paste_tile {
+    const float *src;
+    int64_t image_stride;
+    const double *wx, *wy;
+    int y0, x0, th, tw;
+} cgic_paste_tile;
+int cgic_paste_tiles(int64_t N, int64_t H, int64_t W, int ntiles, const cgic_paste_tile *tiles, float *out_f32,
+                     unsigned char *out_u8, cgic_stream_t stream);
 /* cgic_cut_tiles for the tiles of ONE shape + cgic_entropy_maps_f32 / _u8 on them, in one pass: a lane of the map kernel reads its pixels
  * from the source window (zeros inside the pad) and the tile batch is written as a by-product -- 12 B read + 12 B written per pixel
  * instead of 12 + 12 for the cut and 12 again for the maps.  Recorded like the other entropy calls inside a launch group.
