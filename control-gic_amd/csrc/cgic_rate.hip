@@ -185,7 +185,7 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
     int32_t *stk_m = stk_c + C * sc;
     int32_t *stk_f = stk_m + C * sm;
 
-    // ---- every candidate is checked before anything is enqueued (router_prepare's checks; for the launch chain of segments
+    // ---- every candidate is checked before anything is enqueued (router_plan_args' checks; for the launch chain of segments
     // beyond the LDS also router_big's: the scratch, the pixels, the final launch's arguments)
     const bool have_px = refine && refine->x;
     cgic_pixels px_plain;                    // the pixels without the scratch: the one-launch form takes no refinement queues
@@ -199,8 +199,7 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
         const int mode = cgic_router_mode(coarse[c], medium[c]);
         int32_t *mc = stk_c + c * sc, *mm = stk_m + c * sm, *mf = stk_f + c * sf;
         RouterArgs a;
-        int64_t nseg = 0;
-        size_t l = 0;
+        RouterPlan rp;
         int rc;
         if (have_px && mode <= 3 && !router_refine_in_lds(B, h16, w16, per_image)) {
             const size_t sneed = router_big_scratch_bytes(B, h16, w16, per_image);
@@ -213,15 +212,16 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
             rc = refine_source(refine, h16, w16, &rs);
             if (rc) return rc;
             const float *e16x = reinterpret_cast<const float *>(refine->scratch), *e8x = e16x + B * n16;
-            rc = router_prepare(e16x, e8x, B, h16, w16, coarse[c], medium[c], per_image, mc, mm, mf, nullptr, &a, &nseg, &l,
-                                96 * 1024, nullptr, (hipStream_t)stream, false);
+            rc = router_plan_args(e16x, e8x, B, h16, w16, coarse[c], medium[c], per_image, mc, mm, mf, nullptr, 96 * 1024, nullptr, false, &rp, &a);
             if (rc) return rc;
             chain = true;
             continue;
         }
-        rc = router_prepare(e16, e8, B, h16, w16, coarse[c], medium[c], per_image, mc, mm, mf, nullptr, &a, &nseg, &l,
-                            96 * 1024, have_px ? &px_plain : nullptr, (hipStream_t)stream, false);
+        rc = router_plan_args(e16, e8, B, h16, w16, coarse[c], medium[c], per_image, mc, mm, mf, nullptr, 96 * 1024,
+                              have_px ? &px_plain : nullptr, false, &rp, &a);
         if (rc) return rc;
+        const int64_t nseg = rp.wgs;
+        const size_t l = rp.lds;
         if (c == 0 || (!ra.base.rf.x && a.rf.x)) ra.base = a;      // (the base carries the pixels if any candidate refines)
         CGIC_REQUIRE(nwg == 0 || nwg == nseg, CGIC_ERR_INVALID, "rate_table: candidates disagree on the router's grid");
         nwg = nseg;

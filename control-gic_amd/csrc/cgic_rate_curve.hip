@@ -531,7 +531,7 @@ __global__ __launch_bounds__(kApplyThreads) void rate_apply_kernel(RateApplyArgs
 
 using namespace cgic;
 
-// the rank arithmetic of the router (router_prepare in cgic_router.hip restated: Python's round() is round-half-even on the float64
+// the rank arithmetic of the router (router_plan in cgic_encode_plan.h restated: Python's round() is round-half-even on the float64
 // product, RouterTriple.py:23,30,42,54,65; ranks a mode does not use are 0)
 extern "C" int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64_t n16, int64_t *k_coarse, int64_t *k_medium)
 {

@@ -42,86 +42,74 @@ int refine_source(const cgic_pixels *refine, int64_t h16, int64_t w16, RefineSrc
     return CGIC_OK;
 }
 
-int router_prepare(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio,
-                   double m_ratio, int per_image, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, float *gate,
-                   RouterArgs *out, int64_t *nseg_out, size_t *lds_out, size_t lds_budget, const cgic_pixels *refine, hipStream_t stream, bool queues)
+int router_plan_args(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio, double m_ratio,
+                     int per_image, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, float *gate, size_t lds_budget,
+                     const cgic_pixels *refine, bool queues, RouterPlan *plan, RouterArgs *out)
 {
     CGIC_REQUIRE(e16 && e8 && mask_c && mask_m && mask_f, CGIC_ERR_INVALID, "router: NULL tensor");
     CGIC_REQUIRE(B > 0 && h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "router: bad shape");
-    const int mode = cgic_router_mode(c_ratio, m_ratio);
-    const int64_t per = per_image ? 1 : B;
-    const int64_t nseg = per_image ? B : 1;
-    const int64_t N16 = per * h16 * w16, N8 = 4 * N16;
-    CGIC_REQUIRE(N8 < (int64_t)1 << 31, CGIC_ERR_UNSUPPORTED, "router: segment too large");
-    // Python round() == round-half-even on the float64 product (:23,30,42,54,65)
-    long k_c = 0, k_m = 0;
-    if (mode == 0 || mode == 2 || mode == 3) k_c = (long)nearbyint((double)N16 * c_ratio);
-    if (mode == 0) k_m = (long)nearbyint((double)(4 * N16) * c_ratio + (double)N8 * m_ratio);
-    if (mode == 1) k_m = (long)nearbyint((double)N8 * m_ratio);
-    CGIC_REQUIRE(k_c >= 0 && k_c <= N16 && k_m >= 0 && k_m <= N8, CGIC_ERR_INVALID,
+    RouterShape s;
+    s.B = B; s.h16 = h16; s.w16 = w16; s.c_ratio = c_ratio; s.m_ratio = m_ratio; s.per_image = per_image != 0;
+    s.refine = refine && refine->x;
+    s.has_scratch = s.refine && refine->scratch;
+    s.scratch_bytes = s.has_scratch ? refine->scratch_bytes : 0;
+    s.queues = queues; s.lds_budget = lds_budget; s.lds_shared = kRouterSharedBytes; s.lds_refine = sizeof(RefineShared);
+    RouterPlan &p = *plan;
+    RouterWhy why;
+    const int rc = router_plan(s, &p, &why);
+    CGIC_REQUIRE(why != ROUTER_SEGMENT_TOO_LARGE, rc, "router: segment too large");
+    CGIC_REQUIRE(why != ROUTER_K_RANGE, rc,
                  "router: k out of range (k_coarse=%ld of %lld, k_medium=%ld of %lld); the reference raises IndexError",
-                 k_c, (long long)N16, k_m, (long long)N8);
+                 (long)p.k_c, (long long)p.N16, (long)p.k_m, (long long)p.N8);
     RouterArgs a;
     a.e16 = e16; a.e8 = e8; a.mask_c = mask_c; a.mask_m = mask_m; a.mask_f = mask_f; a.gate = gate;
-    a.per = per; a.h16 = h16; a.w16 = w16; a.mode = mode;
-    a.rank_c = (unsigned int)(k_c != 0 ? k_c - 1 : 0);      // sorted[k-1 if k != 0 else k]
-    a.rank_m = (unsigned int)(k_m != 0 ? k_m - 1 : 0);
-    {
-        // magic multipliers of the index divisions (cgic_router_dev.h: fdiv): exact while (largest dividend) x (divisor) < 2^32
-        const int64_t n8 = 4 * h16 * w16, n4 = 16 * h16 * w16, w8 = 2 * w16, w4 = 4 * w16;
-        auto magic = [](int64_t nmax, int64_t d) -> unsigned int {
-            return (d > 1 && nmax * d < ((int64_t)1 << 32)) ? (unsigned int)((((uint64_t)1 << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u;
-        };
-        a.mg_n8 = magic(N8, n8); a.mg_w8 = magic(n8, w8);
-        a.mg_n4 = magic(4 * N8, n4); a.mg_w4 = magic(n4, w4);
-    }
+    a.per = p.per; a.h16 = h16; a.w16 = w16; a.mode = p.mode;
+    a.rank_c = p.rank_c; a.rank_m = p.rank_m;
+    a.mg_n8 = p.mg_n8; a.mg_w8 = p.mg_w8; a.mg_n4 = p.mg_n4; a.mg_w4 = p.mg_w4;
     a.rf.x = nullptr;
     a.rq.hdr = nullptr; a.rq.board = nullptr; a.rq.scratch = nullptr; a.rq.nq = 0; a.rq.pad = 0;
-    if (refine && refine->x && (mode <= 3)) {          // (modes 4-6 compare nothing)
-        int rc = refine_source(refine, h16, w16, &a.rf);
-        if (rc) return rc;
+    if (p.refined) {
+        const int rc_src = refine_source(refine, h16, w16, &a.rf);
+        if (rc_src) return rc_src;
     }
-    // (with refinement every segment must fit the FUSED launch's budget, so that the stand-alone and the fused launch accept
-    // the same shapes)
-    const size_t lds = router_lds_bytes(N16, N8, &a.stage, a.rf.x ? (lds_budget < kRouterFusedLds ? lds_budget : kRouterFusedLds) : lds_budget,
-                                        a.rf.x != nullptr);
-    CGIC_REQUIRE(a.stage >= 0, CGIC_ERR_UNSUPPORTED,
+    CGIC_REQUIRE(why != ROUTER_LDS_FIT, rc,
                  "router: a segment of %lld + %lld patches does not fit the workgroup's LDS: its refinement is a chain of launches "
                  "(cgic_router_refine_in_lds == 0), which has no recorded form inside a launch group",
-                 (long long)N16, (long long)N8);
-    CGIC_REQUIRE(!a.rf.x || N8 <= 64 * (int64_t)kRefBitWords, CGIC_ERR_UNSUPPORTED, "router: refinement of a segment of %lld patches", (long long)N8);
-    // large per-image segments: several workgroups per image share the mask writing (every one repeats the selects, which
-    // costs nothing while most CUs are idle): up to 8, while the launch stays within ~a quarter of the chip
-    // (The row bands of a tile that split a threshold band WAIT for each other (refine_select's exchange()): every band of every launch
-    // in flight has to be resident.  nseg x bands <= 64 workgroups per launch = a quarter of the chip's CUs, two such workgroups fit a
-    // CU: up to FOUR launches in flight -- the pipeline's four hardware queues -- are resident together whatever else runs; more
-    // concurrent launches than that are outside the contract of cgic_pixels.scratch, see include/cgic_hip.h.)
-    a.bands = 1;
-    if (per_image && h16 * w16 >= 32 * 32) {
-        int64_t nb = 64 / nseg;
-        if (nb > 8) nb = 8;
-        if (nb > h16) nb = h16;
-        a.bands = nb >= 2 ? (int)nb : 1;
-    }
-    CGIC_REQUIRE(lds <= 150 * 1024, CGIC_ERR_UNSUPPORTED, "router: segment of %lld coarse patches exceeds LDS", (long long)N16);
-    // the launch's refinement queues: one header per (segment, select) + the board, in library-owned slots (a pool of their own); payload in the caller's scratch
-    // (the fused launch, queues == false, uses headers + scratch only for the row bands' exchange: segments with bands > 1)
-    if ((queues || a.bands > 1) && a.rf.x && refine->scratch && 2 * nseg <= 4096) {
-        const size_t need = (size_t)nseg * refine_scratch_bytes_per_segment(N16, N8);
-        CGIC_REQUIRE(refine->scratch_bytes >= need, CGIC_ERR_INVALID, "router: refinement scratch of %zu bytes, %zu needed (cgic_router_refine_scratch_bytes)",
-                     refine->scratch_bytes, need);
-        CGIC_REQUIRE(((uintptr_t)refine->scratch & 15u) == 0, CGIC_ERR_INVALID, "router: the refinement scratch must be 16-byte aligned");
-        int rc = acquire_tickets(stream, (int)(2 * nseg), &a.rq.hdr, 1);
-        if (rc) return rc;
-        rc = acquire_tickets(stream, 1, &a.rq.board, 0);
-        if (rc) return rc;
-        a.rq.scratch = reinterpret_cast<unsigned char *>(refine->scratch);
-        a.rq.nq = (unsigned int)(2 * nseg);
-    }
-    *out = a; *nseg_out = nseg * a.bands; *lds_out = lds;       // workgroups of the launch
+                 (long long)p.N16, (long long)p.N8);
+    CGIC_REQUIRE(why != ROUTER_REFINE_PATCHES, rc, "router: refinement of a segment of %lld patches", (long long)p.N8);
+    CGIC_REQUIRE(why != ROUTER_LDS_MAX, rc, "router: segment of %lld coarse patches exceeds LDS", (long long)p.N16);
+    CGIC_REQUIRE(why != ROUTER_SCRATCH_SMALL, rc, "router: refinement scratch of %zu bytes, %zu needed (cgic_router_refine_scratch_bytes)",
+                 s.scratch_bytes, p.scratch_need);
+    CGIC_REQUIRE(!p.nq || ((uintptr_t)refine->scratch & 15u) == 0, CGIC_ERR_INVALID, "router: the refinement scratch must be 16-byte aligned");
+    a.stage = p.stage; a.bands = p.bands;
+    *out = a;
     return CGIC_OK;
 }
 
+// the launch's refinement queues: one header per (segment, select) + the board, in library-owned slots (a pool of their own); the
+// payload lies in the caller's scratch
+int router_tickets(const RouterPlan &plan, const cgic_pixels *refine, hipStream_t stream, RouterArgs *a)
+{
+    if (!plan.nq) return CGIC_OK;
+    int rc = acquire_tickets(stream, (int)plan.nq, &a->rq.hdr, 1);
+    if (rc) return rc;
+    rc = acquire_tickets(stream, 1, &a->rq.board, 0);
+    if (rc) return rc;
+    a->rq.scratch = reinterpret_cast<unsigned char *>(refine->scratch);
+    a->rq.nq = plan.nq;
+    return CGIC_OK;
+}
+
+
+// the stand-alone launch of a planned router: its tickets, the LDS attribute where the launch needs it, the launch
+static int router_launch(const RouterPlan &p, const cgic_pixels *refine, hipStream_t stream, RouterArgs *a)
+{
+    int rc = router_tickets(p, refine, stream, a);
+    if (rc) return rc;
+    if (p.lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)router_kernel, p.lds); if (rc) return rc; }
+    hipLaunchKernelGGL(router_kernel, dim3((unsigned)p.wgs), dim3(kRouterThreads), p.lds, stream, *a);
+    return launch_check("router_kernel");
+}
 
 // ---- threshold-band refinement of segments that do not fit a workgroup's LDS ---------------------------------------------------
 // The reference routes over the FLATTENED batch (RouterTriple.py:21,40,52,63: encode() of B images is one segment of B x 256 +
@@ -253,10 +241,7 @@ size_t router_big_scratch_bytes(int64_t B, int64_t h16, int64_t w16, int per_ima
 
 bool router_refine_in_lds(int64_t B, int64_t h16, int64_t w16, int per_image)
 {
-    const int64_t N16 = (per_image ? 1 : B) * h16 * w16;
-    int st = 0;
-    router_lds_bytes(N16, 4 * N16, &st, kRouterFusedLds, true);
-    return st == 1 && 4 * N16 <= 64 * (int64_t)kRefBitWords;
+    return router_refine_fits((per_image ? 1 : B) * h16 * w16, kRouterSharedBytes, sizeof(RefineShared));
 }
 
 int router_big(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio, double m_ratio, int per_image,
@@ -274,9 +259,8 @@ int router_big(const float *e16, const float *e8, int64_t B, int64_t h16, int64_
     float *e16x = reinterpret_cast<float *>(refine->scratch), *e8x = e16x + T16, *thr = e8x + T8;
     // the final launch's arguments (ranks, mode, index magic) -- made first: it validates the shapes and ratios
     RouterArgs fa;
-    int64_t fseg;
-    size_t flds;
-    int rc = router_prepare(e16x, e8x, B, h16, w16, c_ratio, m_ratio, per_image, mask_c, mask_m, mask_f, gate, &fa, &fseg, &flds, 96 * 1024, nullptr, stream, false);
+    RouterPlan fp;
+    int rc = router_plan_args(e16x, e8x, B, h16, w16, c_ratio, m_ratio, per_image, mask_c, mask_m, mask_f, gate, 96 * 1024, nullptr, false, &fp, &fa);
     if (rc) return rc;
     BigArgs a;
     a.e16 = e16; a.e8 = e8; a.e16x = e16x; a.e8x = e8x; a.thr = thr;
@@ -306,9 +290,7 @@ int router_big(const float *e16, const float *e8, int64_t B, int64_t h16, int64_
     } else {
         CGIC_HIP_TRY(hipMemcpyAsync(e8x, e8, sizeof(float) * (size_t)T8, hipMemcpyDeviceToDevice, stream));
     }
-    if (flds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)router_kernel, flds); if (rc) return rc; }
-    hipLaunchKernelGGL(router_kernel, dim3((unsigned)fseg), dim3(kRouterThreads), flds, stream, fa);
-    return launch_check("router_kernel");
+    return router_launch(fp, nullptr, stream, &fa);
 }
 
 }  // namespace cgic
@@ -317,12 +299,7 @@ using namespace cgic;
 
 extern "C" int cgic_router_mode(double c, double m)
 {
-    // RouterTriple.py:13: fine = 1 - coarse - medium in float64; :19,36,72
-    volatile double f = 1.0 - c - m;
-    int nz = (f == 0) + (m == 0) + (c == 0);
-    if (nz == 0) return 0;
-    if (nz == 1) return c == 0 ? 1 : (m == 0 ? 2 : 3);
-    return c != 0 ? 4 : (m != 0 ? 5 : 6);
+    return router_mode(c, m);
 }
 
 extern "C" int cgic_router_refine_supported(int64_t B, int64_t h16, int64_t w16, int per_image)
@@ -343,9 +320,7 @@ extern "C" size_t cgic_router_refine_scratch_bytes(int64_t B, int64_t h16, int64
 {
     if (!cgic_router_refine_supported(B, h16, w16, per_image)) return 0;
     if (!router_refine_in_lds(B, h16, w16, per_image)) return router_big_scratch_bytes(B, h16, w16, per_image);      // REQUIRED there
-    const int64_t nseg = per_image ? B : 1, N16 = (per_image ? 1 : B) * h16 * w16;
-    if (2 * nseg > 4096) return 0;
-    return (size_t)nseg * refine_scratch_bytes_per_segment(N16, 4 * N16);
+    return router_queue_scratch_bytes(per_image ? B : 1, (per_image ? 1 : B) * h16 * w16);
 }
 
 extern "C" int cgic_router_f32(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16,
@@ -361,13 +336,7 @@ extern "C" int cgic_router_f32(const float *e16, const float *e8, int64_t B, int
     if (refine && refine->x && cgic_router_mode(c_ratio, m_ratio) <= 3 && !router_refine_in_lds(B, h16, w16, per_image))
         return router_big(e16, e8, B, h16, w16, c_ratio, m_ratio, per_image, mask_c, mask_m, mask_f, gate, refine, (hipStream_t)stream);
     RouterArgs a;
-    int64_t nseg;
-    size_t lds;
-    int rc = router_prepare(e16, e8, B, h16, w16, c_ratio, m_ratio, per_image, mask_c, mask_m, mask_f, gate, &a, &nseg, &lds,
-                            96 * 1024, refine, (hipStream_t)stream, true);
-    if (rc) return rc;
-    if (lds > 64 * 1024)
-        { int rc_ = ensure_dynamic_lds((const void *)router_kernel, (size_t)lds); if (rc_) return rc_; }
-    hipLaunchKernelGGL(router_kernel, dim3((unsigned)nseg), dim3(kRouterThreads), lds, (hipStream_t)stream, a);
-    return launch_check("router_kernel");
+    RouterPlan p;
+    const int rc = router_plan_args(e16, e8, B, h16, w16, c_ratio, m_ratio, per_image, mask_c, mask_m, mask_f, gate, 96 * 1024, refine, true, &p, &a);
+    return rc ? rc : router_launch(p, refine, (hipStream_t)stream, &a);
 }

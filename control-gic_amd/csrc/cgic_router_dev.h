@@ -2,6 +2,7 @@
 // stand-alone launch (cgic_router.hip) and the horizontally fused VQ+router launch (cgic_vq.hip).
 #pragma once
 #include "cgic_common.h"
+#include "cgic_encode_plan.h"
 #include "cgic_entropy_dev.h"
 
 #include <math.h>
@@ -196,7 +197,7 @@ struct RouterArgs {
                            // only its band of rows of the masks (one CU per 768x768 tile spent 10 us writing 200 KB of masks)
     RefineSrc rf;          // rf.x != nullptr (stage 1 only): threshold-band refinement from the pixels, see refine_select
     RefineQ rq;            // rq.nq != 0: large bands are evaluated by every idle wave of the launch (refine_help_wave)
-    unsigned int mg_n8, mg_w8, mg_n4, mg_w4;      // ceil(2^32 / d) for d = n8, w8, n4, w4, or 0: divide (router_prepare)
+    unsigned int mg_n8, mg_w8, mg_n4, mg_w4;      // ceil(2^32 / d) for d = n8, w8, n4, w4, or 0: divide (router_plan)
 };
 
 // ---- threshold-band refinement -------------------------------------------------------------------------------------------
@@ -233,7 +234,6 @@ constexpr int kRefFlatSlots = 128;         // distinct grays of constant patches
 constexpr unsigned int kRefEmpty = 0xFFFFFFFFu;      // (a NaN pattern: never the gray of a constant patch)
 constexpr int kFusedQRounds = 8;          // rounds of its waves' work above which an image with a workgroup of its own starts over with the launch's queues (refine_select, BAIL)
 constexpr int kFusedHelpWaves = 2;        // waves of a fused-launch router that did not refine itself and help while the board says busy (router_body)
-constexpr int kRefBitWords = 176;          // 64-bit words of the band's member bitmap: 11264 elements, more than any segment whose maps fit kRouterFusedLds
 
 // ---- evaluating a band's patches with the whole chip -------------------------------------------------------------------------
 // A band of a few patches is evaluated where it was found (four waves per 16x16 patch, side by side).  A long one -- smooth or flat
@@ -263,7 +263,6 @@ constexpr int kRefBitWords = 176;          // 64-bit words of the band's member 
 //     that hold a band open: helpers look for work only while it is non-zero.
 enum { QH_CLAIM = 0 /* + 1: the 64-bit queue word */, QH_SEQ = 2, QH_ARRIVE = 3, QH_FIN = 4, QH_LEFT = 5, QH_THR = 6, QH_NFINAL = 7 };
 enum { QB_BUSY = 0 };
-__host__ __device__ inline size_t refine_scratch_bytes_per_segment(int64_t N16, int64_t N8) { return 24 * (size_t)(N16 + N8); }
 
 __device__ __forceinline__ unsigned int ld_sc1(const unsigned int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld_sc1(const float *p) { return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
@@ -1509,36 +1508,17 @@ __device__ __forceinline__ int router_team(const RouterArgs &a, int64_t blk, uns
 }
 
 
-// stage 1: e16 and e8 live in LDS (e8 is masked in place for the medium select); stage 2: only e8 (e16 is read from global
-// memory by the coarse select's four passes); 0: nothing staged.  `budget`: the fused VQ + router launch keeps a router
-// workgroup under half a CU's LDS so that it can share the CU with a VQ workgroup.  `refine`: room for RefineShared behind
-// the maps (stage 1 only; *stage = -1 if that does not fit the budget).
-__host__ __device__ inline size_t router_lds_bytes(int64_t N16, int64_t N8, int *stage, size_t budget = 96 * 1024, bool refine = false)
-{
-    size_t lds = kRouterSharedBytes + 8 * (size_t)((N16 + 63) / 64);
-    int st = 0;
-    if (refine) {
-        const size_t need = lds + 4 * (size_t)(N16 + N8) + 16 + sizeof(RefineShared);
-        if (need <= budget) { st = 1; lds = need; } else st = -1;
-    } else if (lds + 4 * (size_t)(N16 + N8) <= budget) { st = 1; lds += 4 * (size_t)(N16 + N8); }
-    else if (lds + 4 * (size_t)N8 <= budget) { st = 2; lds += 4 * (size_t)N8; }
-    if (stage) *stage = st;
-    return lds;
-}
+// The host side of a router launch, shared by the stand-alone and the VQ-fused launch: check the arguments, plan the launch
+// (router_plan, cgic_encode_plan.h) and fill the RouterArgs from the plan and the pointers -- nothing is requested or enqueued;
+// then, when the whole call is planned, request the tickets of the plan's refinement queues.
+int router_plan_args(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio, double m_ratio,
+                     int per_image, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, float *gate, size_t lds_budget,
+                     const cgic_pixels *refine, bool queues, RouterPlan *plan, RouterArgs *out);
+int router_tickets(const RouterPlan &plan, const cgic_pixels *refine, hipStream_t stream, RouterArgs *a);
 
-// host-side argument preparation shared by the stand-alone and the VQ-fused launch
-int router_prepare(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio,
-                   double m_ratio, int per_image, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, float *gate,
-                   RouterArgs *out, int64_t *nseg, size_t *lds, size_t lds_budget = 96 * 1024, const cgic_pixels *refine = nullptr,
-                   hipStream_t stream = nullptr, bool queues = false);
-
-// segments whose maps do not fit the LDS budget below: refinement as a chain of launches over patched copies (cgic_router.hip)
+// segments whose maps do not fit kRouterFusedLds: refinement as a chain of launches over patched copies (cgic_router.hip)
 bool router_refine_in_lds(int64_t B, int64_t h16, int64_t w16, int per_image);
 int router_big(const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double c_ratio, double m_ratio, int per_image,
                int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, float *gate, const cgic_pixels *refine, hipStream_t stream);
-
-// LDS budget of a router workgroup in the fused VQ + router launch (two allocations per 160 KB CU); refinement is offered
-// for segments that fit THIS budget, in the stand-alone launch too, so that one answer holds for both
-constexpr size_t kRouterFusedLds = (size_t)78 * 1024;
 
 }  // namespace cgic

@@ -24,14 +24,13 @@
 #include <map>
 #include <mutex>
 #include <vector>
+#include <tuple>
+#include <type_traits>
 #include <utility>
 
 namespace cgic {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kVqThreads = 256;   // 4 waves
-constexpr int kVqMaxK = 8192;
 
 __device__ __forceinline__ float sumsq4(float a, float b, float c, float d)
 {
@@ -486,9 +485,7 @@ __global__ __launch_bounds__(kVqThreads, ZT <= 4 ? 4 : 2) void vq_router_kernel(
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kVqfMaxK = 1024;
 constexpr int kVqfBulk = 12;                   // more flagged vectors than this in a 64-vector group: rerun it exactly on the MFMA
-constexpr int kVqfGroup = 64;                  // vectors per group: two tiles of 32 (one lane per vector in the decide step)
 
 __device__ __forceinline__ unsigned int h16(float x)
 {
@@ -1148,12 +1145,6 @@ __device__ __forceinline__ void vq_filter_body(const VqArgs &a, unsigned char *s
     CGIC_BLK_END();
 }
 
-constexpr int kVqfThreads = 512;      // one workgroup per CU, 2 waves per SIMD.  Alone at B=64 x 64x64 latents 512 / 768 / 1024 threads are within 1 us of each other; with several batches in flight (bench.py --lanes 4) 512 leaves a third of the register file to the other batches' kernels: 86.9 vs 83.4 (768) vs 82.9 (1024) GPixel/s
-// 128 registers per lane (4-10 spilled, 20-44 bytes of scratch) instead of 144-150: two 512-thread workgroups then fit a CU's
-// register file, so a ROUTER workgroup of the fused launch (same launch => same allocation) shares its CU with a VQ workgroup
-// instead of holding the CU to itself for ~12 us: fused launch 26.3 -> 24.1 us at B=64 (the VQ kernel alone: 23.3 -> 23.8 on the
-// same GPU), no uneven split of the VQ shares needed any more.
-constexpr int kVqfVgprCap = 128;
 // (amdgpu_num_vgpr counts VGPR + AGPR on gfx950: the attribute carries half the cap)
 #define CGIC_VQF_BOUNDS __launch_bounds__(kVqfThreads, kVqfThreads / 256 > 1 ? kVqfThreads / 256 : 1) __attribute__((amdgpu_num_vgpr(kVqfVgprCap / 2)))
 
@@ -1389,160 +1380,6 @@ static int conv_check(const cgic_conv1x1 *qc)
     return CGIC_OK;
 }
 
-struct VqWs {
-    unsigned int *ticket;   // library-owned, self-resetting
-    double *partial;        // caller's workspace: double partial[nblk]
-};
-
-static int vq_ws(void *workspace, hipStream_t s, VqWs *out)
-{
-    out->partial = (double *)workspace;
-    out->ticket = nullptr;
-    if (!workspace) return CGIC_OK;
-    return acquire_tickets(s, 1, &out->ticket);
-}
-
-template <int ZT>
-static int launch_mfma(const float *z, int64_t hw, int64_t N, const float *cb, int K, int64_t *idx,
-                       float *zq, VqWs ws, float beta, int legacy, float *loss, hipStream_t s,
-                       const RouterArgs *router, int64_t router_blocks, size_t router_lds)
-{
-    const int64_t per_block = 4 * 16 * ZT;
-    VqArgs a;
-    a.z = z; a.hw = hw; a.N = N; a.cb = cb; a.K = K; a.idx_out = idx; a.zq_out = zq;
-    a.sq_partial = loss ? ws.partial : nullptr; a.ticket = ws.ticket; a.beta = beta; a.legacy = legacy; a.loss = loss;
-    a.nblk = (unsigned int)((N + per_block - 1) / per_block);
-    a.n_early = a.g_early = a.g_late = 0; a.tail_mode = 0; a.conv_w = a.conv_b = nullptr; a.conv_bias_first = 0; a.prep = nullptr; a.stats = nullptr; a.probe_scores = a.probe_aux = nullptr;
-    size_t lds = sizeof(float) * (size_t)K * 5;
-    if (!router) {
-        int rc = ensure_dynamic_lds((const void *)vq_mfma_kernel<ZT>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(vq_mfma_kernel<ZT>, dim3(a.nblk), dim3(kVqThreads), lds, s, a);
-        return launch_check("vq_mfma_kernel");
-    }
-    if (router_lds > lds) lds = router_lds;
-    int rc = ensure_dynamic_lds((const void *)vq_router_kernel<ZT>, lds);
-    if (rc) return rc;
-    // (no grouped form: inside a launch group this position is launched group by group)
-    const RouterArgs r = *router;
-    const dim3 grid(a.nblk + (unsigned int)router_blocks);
-    return launch_or_record(KID_NONE, grid, dim3(kVqThreads), lds, a, s, [=] {
-        hipLaunchKernelGGL(vq_router_kernel<ZT>, grid, dim3(kVqThreads), lds, s, a, r);
-        return launch_check("vq_router_kernel"); });
-}
-
-static bool prepared_is_perm(const void *prepared);      // (below, next to cgic_vq_prepare_f32)
-
-template <bool ALIGNED, bool CONV>
-static int launch_filter(const float *z, int64_t hw, int64_t N, const float *cb, int K, int64_t *idx, float *zq,
-                         VqWs ws, float beta, int legacy, float *loss, hipStream_t s, const RouterArgs *router,
-                         int64_t router_blocks, size_t router_lds, const cgic_conv1x1 *qc, const void *prepared)
-{
-    int cus = 0;
-    int rc = device_cu_count(&cus);
-    if (rc) return rc;
-    const int64_t ngroups = (N + kVqfGroup - 1) / kVqfGroup;
-    // one resident workgroup per CU; its waves take groups from a counter.  Fewer groups than CUs x waves: spread them
-    // over the CUs first (a small batch then costs one staging + one group per CU, whatever the waves per workgroup)
-    if (dev_knob("CGIC_VQ_WGS_PER_CU") > 1) cus *= dev_knob("CGIC_VQ_WGS_PER_CU");      // dev: several resident workgroups per CU
-    if (group_recording()) {          // one shape group of a grouped launch: its share of the chip
-        cus = (int)((double)cus * group_cu_share() + 0.5);
-        cus = cus < 1 ? 1 : cus;
-    }
-    int64_t nblk = ngroups < cus ? ngroups : cus;
-    VqArgs a;
-    a.z = z; a.hw = hw; a.N = N; a.cb = cb; a.K = K; a.idx_out = idx; a.zq_out = zq;
-    a.sq_partial = nullptr; a.ticket = ws.ticket; a.beta = beta; a.legacy = legacy; a.loss = loss;
-    if (loss) {
-        // the ticket and, behind it, one 8-byte partial per workgroup: library-owned, zero when handed out, zeroed again by the launch
-        // (finish_loss_wave); the caller's workspace is not touched by this path
-        unsigned int *t = nullptr;
-        rc = acquire_tickets(s, 1 + (int)((nblk + 7) / 8), &t);
-        if (rc) return rc;
-        a.ticket = t;
-        a.sq_partial = reinterpret_cast<double *>(t + kTicketStride);
-    }
-    a.nblk = (unsigned int)nblk;
-    a.tail_mode = loss ? 2u : 0u;                   // workgroup 0 collects (VqArgs::tail_mode)
-    a.conv_w = CONV ? qc->weight : nullptr; a.conv_b = CONV ? qc->bias : nullptr; a.conv_bias_first = CONV ? qc->bias_first : 0;
-    a.prep = prepared;
-    a.stats = g_vq_stats.load(std::memory_order_relaxed);
-    a.probe_scores = a.probe_aux = nullptr;
-    // groups per workgroup.  Router workgroups in front: the `late` VQ workgroups that must wait for a router's CU
-    // (~11 us at 256x256, ~`delta` groups of VQ work) own `g_late` groups, the others `g_early`, a multiple of 4
-    int64_t per = (ngroups + nblk - 1) / nblk, g_early = per, g_late = per, n_early = nblk;
-    const int64_t late = router ? nblk + router_blocks - cus : 0;
-    bool router_first = false;
-    // A router workgroup can share its CU with a VQ workgroup.  Behind the VQ workgroups in the grid (every VQ workgroup gets a
-    // CU at once and keeps its even share, the routers move in beside them) the router is free as long as it ends before the VQ
-    // does -- beside an issue-bound VQ workgroup it runs ~1.6x slower than alone: 64 images of 256x256 24.1 us fused against
-    // 23.5 for the VQ alone (in front with even shares: 27.1 -- the VQ workgroups pair up on the free CUs).  Few large tiles
-    // (8 of 768x768: router 21 us alone, VQ 26) keep the older scheme: routers in front, uneven VQ shares.
-    const double t_router = 10.9 + 0.000275 * (double)hw, t_vq = 3.0 + 1.25 * (double)per;
-    const bool coresident = kVqfVgprCap <= 128 && router && 1.6 * t_router <= t_vq;
-    if (!coresident && late > 0 && late < nblk && !dev_knob("CGIC_VQ_NOSPLIT")) {
-        // how long a router workgroup holds its CU, in groups of VQ work (~1.05 us each per workgroup): measured 12 us at
-        // 64x64 latents, 21 us at 192x192 (with its row bands)
-        const int64_t delta = (int64_t)((10.9 + 0.000275 * (double)hw) / 1.05 + 0.5);
-        const int force_ge = dev_knob("CGIC_VQ_GE");
-        for (int64_t ge = force_ge ? force_ge : (per / 4 + 1) * 4; ge <= per + 28; ge += 4) {
-            const int64_t rest = ngroups - (nblk - late) * ge;
-            const int64_t gl = rest > 0 ? (rest + late - 1) / late : 0;
-            // (gl == 0: the router outlasts the whole VQ -- the early workgroups simply take everything)
-            if (gl + delta <= ge || gl == 0) { g_early = ge; g_late = gl; n_early = nblk - late; router_first = true; break; }
-        }
-    }
-    a.n_early = (unsigned int)n_early; a.g_early = (unsigned int)g_early; a.g_late = (unsigned int)g_late;
-    size_t lds = vqf_lds_bytes(K);
-    // a prepared image packed by cluster takes the PERM kernels (their own instantiations; inside a launch group and with a fused
-    // quant_conv the plain kernels run: they do not trust the permuted image's tag and derive their own)
-    const bool perm = !CONV && !group_recording() && prepared_is_perm(prepared);
-    if (perm) lds += 4 * (size_t)K;
-    if (!router) {
-        if (perm) {
-            if constexpr (!CONV) {
-                rc = ensure_dynamic_lds((const void *)vq_filter_perm_kernel<ALIGNED>, lds);
-                if (rc) return rc;
-                hipLaunchKernelGGL((vq_filter_perm_kernel<ALIGNED>), dim3(a.nblk), dim3(kVqfThreads), lds, s, a);
-                return launch_check("vq_filter_perm_kernel");
-            }
-        }
-        rc = ensure_dynamic_lds((const void *)vq_filter_kernel<ALIGNED, CONV>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((vq_filter_kernel<ALIGNED, CONV>), dim3(a.nblk), dim3(kVqfThreads), lds, s, a);
-        return launch_check("vq_filter_kernel");
-    }
-    if (router_lds > lds) lds = router_lds;
-    if (perm) {
-        if constexpr (!CONV) {
-            rc = ensure_dynamic_lds((const void *)vq_filter_router_perm_kernel<ALIGNED>, lds);
-            if (rc) return rc;
-            const dim3 grid_p(a.nblk + (unsigned int)router_blocks);
-            const unsigned int behind = router_first ? 0u : 1u;
-            hipLaunchKernelGGL((vq_filter_router_perm_kernel<ALIGNED>), grid_p, dim3(kVqfThreads), lds, s, a, *router, (unsigned int)router_blocks, behind);
-            return launch_check("vq_filter_router_perm_kernel");
-        }
-    }
-    VqfrArgs p;
-    p.a = a; p.r = *router; p.nrouter = (unsigned int)router_blocks; p.router_behind = router_first ? 0u : 1u;
-    const dim3 grid(a.nblk + (unsigned int)router_blocks);
-    // row bands that share a threshold band's re-evaluation run the SPLIT instantiation (cgic_router_dev.h: router_body)
-    // ... and images with a workgroup of their own whose band is long start over with the launch's refinement queues (round 6)
-    const bool split = router->rq.nq != 0;
-    if (split) {
-        rc = ensure_dynamic_lds((const void *)vq_filter_router_kernel<ALIGNED, CONV, true>, lds);
-        if (rc) return rc;
-        return launch_or_record(CONV ? KID_NONE : ALIGNED ? KID_VQF_ROUTER_AL : KID_VQF_ROUTER_UN, grid, dim3(kVqfThreads), lds, p, s, [=] {
-            hipLaunchKernelGGL((vq_filter_router_kernel<ALIGNED, CONV, true>), grid, dim3(kVqfThreads), lds, s, p.a, p.r, p.nrouter, p.router_behind);
-            return launch_check("vq_filter_router_kernel(split)"); });
-    }
-    rc = ensure_dynamic_lds((const void *)vq_filter_router_kernel<ALIGNED, CONV>, lds);
-    if (rc) return rc;
-    return launch_or_record(CONV ? KID_NONE : ALIGNED ? KID_VQF_ROUTER_AL : KID_VQF_ROUTER_UN, grid, dim3(kVqfThreads), lds, p, s, [=] {
-        hipLaunchKernelGGL((vq_filter_router_kernel<ALIGNED, CONV>), grid, dim3(kVqfThreads), lds, s, p.a, p.r, p.nrouter, p.router_behind);
-        return launch_check("vq_filter_router_kernel"); });
-}
-
 template <bool ALIGNED>
 static int vqfr_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s)
 {
@@ -1560,30 +1397,182 @@ static int vqfr_grouped_launch(const GroupRec *const *recs, int n, hipStream_t s
 static GroupedRegistrar reg_vqfr_al(KID_VQF_ROUTER_AL, vqfr_grouped_launch<true>);
 static GroupedRegistrar reg_vqfr_un(KID_VQF_ROUTER_UN, vqfr_grouped_launch<false>);
 
-static int vq_dispatch(const float *z, int64_t hw, int64_t N, const float *codebook, int K, int64_t *indices, float *z_q,
-                       VqWs ws, float beta, int legacy, float *loss, hipStream_t s, const RouterArgs *router,
-                       int64_t router_blocks, size_t router_lds, const cgic_conv1x1 *qc, const void *prepared)
+static bool prepared_is_perm(const void *prepared);      // (below, next to cgic_vq_prepare_f32)
+
+// What a call of the VQ entry points hands to its launch (the checked arguments of the C ABI), and the shape its plan is made from
+struct VqCall {
+    const float *z;
+    int64_t hw, N;
+    const float *cb;
+    int K;
+    int64_t *idx;
+    float *zq;
+    float beta;
+    int legacy;
+    float *loss;
+    void *workspace;
+    const cgic_conv1x1 *qc;
+    const void *prepared;
+};
+
+// (knobs == false: the telemetry launch takes no dev knobs -- the whole chip, the filter path)
+static int vq_shape(const VqCall &c, const RouterPlan *router, bool knobs, VqShape *out)
 {
-    const int force_zt = dev_knob("CGIC_VQ_ZT");          // dev: tile count of the exact loop
-    if (!dev_knob("CGIC_VQ_EXACT") && K % 64 == 0 && K <= kVqfMaxK) {
-#define CGIC_VQF_LAUNCH(AL, CV) launch_filter<AL, CV>(z, hw, N, codebook, K, indices, z_q, ws, beta, legacy, loss, s, router, router_blocks, router_lds, qc, prepared)
-        if (hw % kVqfGroup == 0) return qc ? CGIC_VQF_LAUNCH(true, true) : CGIC_VQF_LAUNCH(true, false);
-        return qc ? CGIC_VQF_LAUNCH(false, true) : CGIC_VQF_LAUNCH(false, false);
-#undef CGIC_VQF_LAUNCH
+    VqShape s{};
+    s.N = c.N; s.hw = c.hw; s.K = c.K;
+    s.conv = c.qc != nullptr; s.loss = c.loss != nullptr;
+    const int rc = device_cu_count(&s.cus);
+    if (rc) return rc;
+    s.recording = group_recording();
+    s.cu_share = group_cu_share();
+    s.perm_image = prepared_is_perm(c.prepared);
+    if (router) { s.router_wgs = router->wgs; s.router_lds = router->lds; s.router_queues = router->nq != 0; }
+    s.lds_filter = vqf_lds_bytes(c.K);
+    s.kid_aligned = KID_VQF_ROUTER_AL; s.kid_unaligned = KID_VQF_ROUTER_UN;
+    if (knobs) {
+        s.knob_exact = dev_knob("CGIC_VQ_EXACT"); s.knob_zt = dev_knob("CGIC_VQ_ZT"); s.knob_wgs_per_cu = dev_knob("CGIC_VQ_WGS_PER_CU");
+        s.knob_nosplit = dev_knob("CGIC_VQ_NOSPLIT"); s.knob_ge = dev_knob("CGIC_VQ_GE");
     }
-    CGIC_REQUIRE(!qc, CGIC_ERR_UNSUPPORTED, "vq: the fused quant_conv needs K %% 64 == 0 and K <= %d (K=%d): apply the 1x1 convolution separately", kVqfMaxK, K);
-    // exact loop; per-wave tile: measured on MI355X (tools/probes/probe_vq.hip) ZT=4 at 4 waves/SIMD is the fastest
-    // for large N; smaller N shrinks the tile so that all 256 CUs get work
-#define CGIC_VQ_LAUNCH(ZT) launch_mfma<ZT>(z, hw, N, codebook, K, indices, z_q, ws, beta, legacy, loss, s, router, router_blocks, router_lds)
-    if (force_zt == 8) return CGIC_VQ_LAUNCH(8);
-    if (force_zt == 4) return CGIC_VQ_LAUNCH(4);
-    if (force_zt == 2) return CGIC_VQ_LAUNCH(2);
-    if (force_zt == 1) return CGIC_VQ_LAUNCH(1);
-    if (N >= (int64_t)1 << 22) return CGIC_VQ_LAUNCH(8);
-    if (N >= (int64_t)256 * 512) return CGIC_VQ_LAUNCH(4);
-    if (N >= (int64_t)128 * 512) return CGIC_VQ_LAUNCH(2);
-    return CGIC_VQ_LAUNCH(1);
-#undef CGIC_VQ_LAUNCH
+    *out = s;
+    return CGIC_OK;
+}
+
+// The tickets of a planned launch, requested when the whole call is planned.  The exact loop's last workgroup sums the caller's
+// workspace behind one ticket.  The filter path takes the ticket and, behind it, one 8-byte partial per workgroup: library-owned,
+// zero when handed out, zeroed again by the launch (finish_loss_wave); the caller's workspace is not touched by this path.
+struct VqWs {
+    unsigned int *ticket;   // library-owned, self-resetting
+    double *partial;        // double partial[nblk]
+};
+
+static int vq_ws(void *workspace, hipStream_t s, VqWs *out)
+{
+    out->partial = (double *)workspace;
+    out->ticket = nullptr;
+    if (!workspace) return CGIC_OK;
+    return acquire_tickets(s, 1, &out->ticket);
+}
+
+static int vq_tickets(const VqPlan &p, void *workspace, hipStream_t s, VqWs *out)
+{
+    int rc = vq_ws(workspace, s, out);
+    if (rc || !p.tickets) return rc;
+    rc = acquire_tickets(s, p.tickets, &out->ticket);
+    if (rc) return rc;
+    out->partial = reinterpret_cast<double *>(out->ticket + kTicketStride);
+    return CGIC_OK;
+}
+
+static VqArgs vq_args(const VqCall &c, const VqPlan &p, VqWs ws)
+{
+    const bool filter = p.path == VQ_FILTER;
+    VqArgs a;
+    a.z = c.z; a.hw = c.hw; a.N = c.N; a.cb = c.cb; a.K = c.K; a.idx_out = c.idx; a.zq_out = c.zq;
+    a.sq_partial = c.loss ? ws.partial : nullptr; a.ticket = ws.ticket; a.beta = c.beta; a.legacy = c.legacy; a.loss = c.loss;
+    a.nblk = (unsigned int)p.nblk;
+    a.n_early = (unsigned int)p.n_early; a.g_early = (unsigned int)p.g_early; a.g_late = (unsigned int)p.g_late;
+    a.tail_mode = p.tail_mode;
+    a.conv_w = filter && c.qc ? c.qc->weight : nullptr; a.conv_b = filter && c.qc ? c.qc->bias : nullptr;
+    a.conv_bias_first = filter && c.qc ? c.qc->bias_first : 0;
+    a.prep = filter ? c.prepared : nullptr;
+    a.stats = filter ? g_vq_stats.load(std::memory_order_relaxed) : nullptr;
+    a.probe_scores = a.probe_aux = nullptr;
+    return a;
+}
+
+// The kernel of a plan.  Every kernel of the VQ takes a prefix of VqfrArgs' members (VqArgs, RouterArgs, nrouter, router_behind)
+// as its arguments: vq_issue hands all four to hipLaunchKernel, and vq_kernel() is where the compiler checks that of a kernel.
+struct VqKernel {
+    const void *fn;
+    const char *name;
+};
+template <class... P, size_t... I>
+constexpr bool vq_kernel_params_ok(std::index_sequence<I...>)
+{
+    using All = std::tuple<VqArgs, RouterArgs, unsigned int, unsigned int>;
+    return (std::is_same_v<P, std::tuple_element_t<I, All>> && ...);
+}
+template <class... P>
+static VqKernel vq_kernel(void (*fn)(P...), const char *name)
+{
+    static_assert(sizeof...(P) >= 1 && sizeof...(P) <= 4 && vq_kernel_params_ok<P...>(std::index_sequence_for<P...>{}),
+                  "a VQ kernel takes a prefix of (VqArgs, RouterArgs, unsigned int, unsigned int)");
+    return {(const void *)fn, name};
+}
+// ONE switch over the variant per (ALIGNED, CONV), and the exact loop's two per ZT.  (The PERM kernels have no CONV form and the
+// plan names none: with a quant_conv those cases take the plain kernels.)
+template <bool ALIGNED, bool CONV>
+static VqKernel vq_filter_kernel_of(VqVariant v)
+{
+    switch (v) {
+    case VQ_PERM:
+        if constexpr (!CONV) return vq_kernel(vq_filter_perm_kernel<ALIGNED>, "vq_filter_perm_kernel");
+        else return vq_kernel(vq_filter_kernel<ALIGNED, CONV>, "vq_filter_kernel");
+    case VQ_PLAIN: return vq_kernel(vq_filter_kernel<ALIGNED, CONV>, "vq_filter_kernel");
+    case VQ_ROUTER_PERM:
+        if constexpr (!CONV) return vq_kernel(vq_filter_router_perm_kernel<ALIGNED>, "vq_filter_router_perm_kernel");
+        else break;
+    case VQ_ROUTER_SPLIT: return vq_kernel(vq_filter_router_kernel<ALIGNED, CONV, true>, "vq_filter_router_kernel(split)");
+    case VQ_ROUTER: break;
+    }
+    return vq_kernel(vq_filter_router_kernel<ALIGNED, CONV>, "vq_filter_router_kernel");
+}
+template <int ZT>
+static VqKernel vq_exact_kernel_of(VqVariant v)
+{
+    if (v == VQ_PLAIN) return vq_kernel(vq_mfma_kernel<ZT>, "vq_mfma_kernel");
+    return vq_kernel(vq_router_kernel<ZT>, "vq_router_kernel");
+}
+static VqKernel vq_kernel_of(const VqPlan &p, bool conv)
+{
+    if (p.path == VQ_FILTER) {
+        if (p.aligned) return conv ? vq_filter_kernel_of<true, true>(p.variant) : vq_filter_kernel_of<true, false>(p.variant);
+        return conv ? vq_filter_kernel_of<false, true>(p.variant) : vq_filter_kernel_of<false, false>(p.variant);
+    }
+    return p.zt == 8 ? vq_exact_kernel_of<8>(p.variant) : p.zt == 4 ? vq_exact_kernel_of<4>(p.variant)
+         : p.zt == 2 ? vq_exact_kernel_of<2>(p.variant) : vq_exact_kernel_of<1>(p.variant);
+}
+
+// One launch of the planned kernel: its LDS attribute, the launch -- made now or, inside a launch group, recorded -- and its check
+static int vq_issue(VqKernel k, const VqPlan &p, const VqfrArgs &v, hipStream_t s)
+{
+    const int rc = ensure_dynamic_lds(k.fn, p.lds);
+    if (rc) return rc;
+    const dim3 grid((unsigned int)p.grid), block((unsigned int)p.threads);
+    const size_t lds = p.lds;
+    return launch_or_record(p.kid, grid, block, lds, v, s, [=] {
+        void *args[] = {(void *)&v.a, (void *)&v.r, (void *)&v.nrouter, (void *)&v.router_behind};
+        const hipError_t e = hipLaunchKernel(k.fn, grid, block, args, lds, s);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("launch of %s failed: %s", k.name, hipGetErrorString(e));
+            return (int)CGIC_ERR_HIP;
+        }
+        return launch_check(k.name); });
+}
+
+// plan, tickets, launch: the VQ of a checked call, with the planned router's workgroups in the same launch if there is one
+static int vq_forward(const VqCall &c, const RouterPlan *router, const cgic_pixels *refine, RouterArgs *r, hipStream_t s)
+{
+    VqShape shape;
+    int rc = vq_shape(c, router, true, &shape);
+    if (rc) return rc;
+    VqPlan p;
+    const char *why = "";
+    rc = vq_plan(shape, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s (K=%d): apply the 1x1 convolution separately", why, c.K);
+    VqfrArgs v{};
+    if (router) {
+        rc = router_tickets(*router, refine, s, r);
+        if (rc) return rc;
+        v.r = *r;
+    }
+    VqWs ws;
+    rc = vq_tickets(p, c.loss ? c.workspace : nullptr, s, &ws);
+    if (rc) return rc;
+    v.a = vq_args(c, p, ws);
+    v.nrouter = (unsigned int)shape.router_wgs; v.router_behind = p.router_behind ? 1u : 0u;
+    return vq_issue(vq_kernel_of(p, shape.conv), p, v, s);
 }
 
 }  // namespace cgic
@@ -1606,29 +1595,20 @@ extern "C" int cgic_vq_filter_probe_f32(const float *z, int64_t B, int64_t hw, c
     CGIC_REQUIRE(indices && scores && aux, CGIC_ERR_INVALID, "vq_filter_probe: NULL output");
     const int64_t N = B * hw;
     if (N == 0) return CGIC_OK;
-    int cus = 0;
-    rc = device_cu_count(&cus);
+    const VqCall c{z, hw, N, codebook, K, indices, nullptr, 0.f, 1, nullptr, nullptr, nullptr, nullptr};
+    VqShape shape;
+    rc = vq_shape(c, nullptr, false, &shape);
     if (rc) return rc;
-    const int64_t ngroups = (N + kVqfGroup - 1) / kVqfGroup;
-    const int64_t nblk = ngroups < cus ? ngroups : cus, per = (ngroups + nblk - 1) / nblk;
-    VqArgs a;
-    a.z = z; a.hw = hw; a.N = N; a.cb = codebook; a.K = K; a.idx_out = indices; a.zq_out = nullptr;
-    a.sq_partial = nullptr; a.ticket = nullptr; a.beta = 0.f; a.legacy = 1; a.loss = nullptr;
-    a.nblk = (unsigned int)nblk; a.n_early = (unsigned int)nblk; a.g_early = a.g_late = (unsigned int)per;
-    a.tail_mode = 0; a.conv_w = a.conv_b = nullptr; a.conv_bias_first = 0; a.prep = nullptr; a.stats = nullptr;
-    a.probe_scores = scores; a.probe_aux = aux;
-    const size_t lds = vqf_lds_bytes(K);
-    hipStream_t s = (hipStream_t)stream;
-    if (hw % kVqfGroup == 0) {
-        rc = ensure_dynamic_lds((const void *)vq_filter_probe_kernel<true>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((vq_filter_probe_kernel<true>), dim3(a.nblk), dim3(kVqfThreads), lds, s, a);
-    } else {
-        rc = ensure_dynamic_lds((const void *)vq_filter_probe_kernel<false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((vq_filter_probe_kernel<false>), dim3(a.nblk), dim3(kVqfThreads), lds, s, a);
-    }
-    return launch_check("vq_filter_probe_kernel");
+    VqPlan p;
+    const char *why = "";
+    rc = vq_plan(shape, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "vq_filter_probe: %s", why);       // (never: this K has a filter path and there is no quant_conv)
+    VqfrArgs v{};
+    v.a = vq_args(c, p, VqWs{nullptr, nullptr});
+    v.a.stats = nullptr; v.a.probe_scores = scores; v.a.probe_aux = aux;
+    const VqKernel k = p.aligned ? vq_kernel(vq_filter_probe_kernel<true>, "vq_filter_probe_kernel")
+                                 : vq_kernel(vq_filter_probe_kernel<false>, "vq_filter_probe_kernel");
+    return vq_issue(k, p, v, (hipStream_t)stream);
 }
 
 extern "C" int cgic_vq_stats(unsigned int *device_counters)
@@ -1838,10 +1818,8 @@ extern "C" int cgic_vq_forward_f32(const float *z, int64_t B, int64_t hw, const 
     const int64_t N = B * hw;
     if (N == 0) return CGIC_OK;
     hipStream_t s = (hipStream_t)stream;
-    VqWs ws;
-    rc = vq_ws(loss ? workspace : nullptr, s, &ws);
-    if (rc) return rc;
-    rc = vq_dispatch(z, hw, N, codebook, K, indices, z_q, ws, beta, legacy, loss, s, nullptr, 0, 0, quant_conv, prepared);
+    const VqCall c{z, hw, N, codebook, K, indices, z_q, beta, legacy, loss, workspace, quant_conv, prepared};
+    rc = vq_forward(c, nullptr, nullptr, nullptr, s);
     if (rc == CGIC_OK && hist) rc = launch_hist(indices, N, K, hist, s);
     return rc;
 }
@@ -1863,32 +1841,25 @@ extern "C" int cgic_vq_forward_route_f32(const float *z, int64_t B, int64_t hw, 
     if (mode_out) *mode_out = cgic_router_mode(coarse_ratio, medium_ratio);
     const int64_t N = B * hw;
     if (N == 0) return CGIC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const VqCall c{z, hw, N, codebook, K, indices, z_q, beta, legacy, loss, workspace, quant_conv, prepared};
     if (refine && refine->x && cgic_router_mode(coarse_ratio, medium_ratio) <= 3 && !router_refine_in_lds(B, h16, w16, per_image)) {
         // a routing segment beyond the LDS (the reference's flattened-batch routing of encode(), an untiled large image): the VQ
         // launch by itself, then the router's chain of launches over patched copies of the maps (cgic_router.hip: router_big)
         CGIC_REQUIRE(!group_recording(), CGIC_ERR_UNSUPPORTED,
                      "vq_forward_route: the refinement of a segment that does not fit the LDS is a chain of launches: not inside a launch group");
-        hipStream_t s0 = (hipStream_t)stream;
-        VqWs ws0;
-        rc = vq_ws(loss ? workspace : nullptr, s0, &ws0);
+        rc = vq_forward(c, nullptr, nullptr, nullptr, s);
         if (rc) return rc;
-        rc = vq_dispatch(z, hw, N, codebook, K, indices, z_q, ws0, beta, legacy, loss, s0, nullptr, 0, 0, quant_conv, prepared);
-        if (rc) return rc;
-        return router_big(e16, e8, B, h16, w16, coarse_ratio, medium_ratio, per_image, mask_c, mask_m, mask_f, gate, refine, s0);
+        return router_big(e16, e8, B, h16, w16, coarse_ratio, medium_ratio, per_image, mask_c, mask_m, mask_f, gate, refine, s);
     }
     RouterArgs r;
-    int64_t nseg;
-    size_t rlds;
+    RouterPlan rp;
     // (78 KB: a router workgroup of the fused launch shares its CU with a VQ workgroup -- two allocations per 160 KB)
     // (with a scratch: the launch's refinement queues -- images with long threshold bands publish them, the routers that are done help)
-    rc = router_prepare(e16, e8, B, h16, w16, coarse_ratio, medium_ratio, per_image, mask_c, mask_m, mask_f, gate, &r, &nseg, &rlds,
-                        kRouterFusedLds, refine, (hipStream_t)stream, per_image != 0 && refine && refine->scratch);
+    rc = router_plan_args(e16, e8, B, h16, w16, coarse_ratio, medium_ratio, per_image, mask_c, mask_m, mask_f, gate, kRouterFusedLds,
+                          refine, per_image != 0 && refine && refine->scratch, &rp, &r);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    VqWs ws;
-    rc = vq_ws(loss ? workspace : nullptr, s, &ws);
-    if (rc) return rc;
-    return vq_dispatch(z, hw, N, codebook, K, indices, z_q, ws, beta, legacy, loss, s, &r, nseg, rlds, quant_conv, prepared);
+    return vq_forward(c, &rp, refine, &r, s);
 }
 
 extern "C" int cgic_vq_forward_valu_f32(const float *z, int64_t B, int64_t hw, const float *codebook, int K,

@@ -436,6 +436,39 @@ def test_decompress_issues_the_launches_its_plan_names(B, H, W, decoder, launche
     assert int(got[3].abs().max()) == 0
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W", [
+    (1, 16, 16),            # 16 vectors: fewer than a group of 64
+    (1, 80, 112),           # a 20x28 latent grid: 560 vectors per image, no multiple of 64 (the unaligned kernels)
+    (64, 256, 256),         # the routers share their CUs with the VQ workgroups: behind them in the grid, even VQ shares
+    (16, 512, 512),         # routers in front, uneven VQ shares: the late workgroups own fewer groups
+    (8, 768, 768),          # ... or none: the early ones cover every group (and the router has row bands)
+])
+def test_vq_forward_route_issues_the_launch_its_plan_names(B, H, W):
+    """every branch of vq_plan's split between VQ and router workgroups (cgic_encode_plan.h), seen through the recorder of a one-group
+    launch group: ONE launch per call, and indices, codebook rows, loss and masks bit-equal to the ungrouped call and to the
+    separate vq_forward + router calls"""
+    from control_gic_amd import _lib
+    from control_gic_amd.quantize import _vq_forward, vq_forward_route
+    cg, dev, rng, vq, _ = _setup(B + H + W)
+    w = vq.embedding.weight
+    z = torch.from_numpy(rng.standard_normal((B, 4, H // 4, W // 4), dtype=np.float32)).to(dev)
+    e16 = torch.from_numpy((rng.random((B, H // 16, W // 16)) * 2.6).astype(np.float32)).to(dev)
+    e8 = torch.from_numpy((rng.random((B, H // 8, W // 8)) * 2.6).astype(np.float32)).to(dev)
+    ref = vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True)
+    grp = _lib.launch_group(1, None, dev)
+    with grp as g:
+        g.select(0)
+        got = vq_forward_route(z, w, 0.25, True, e16, e8, 0.1, 0.8, per_image=True)
+    assert grp.launches == 1
+    zq, loss, idx = _vq_forward(z, w, 0.25, True, None)
+    mask, _, _, mode = cg.TripleGrainFixedEntropyRouter(0.1, 0.8, per_image=True)(e16, e8, want_gate=False)
+    torch.cuda.synchronize()
+    for out in (ref, got):
+        assert torch.equal(out[2], idx) and torch.equal(out[0], zq) and float(out[1]) == float(loss) and out[5] == mode
+        assert all(torch.equal(p, q) for p, q in zip(out[3], mask))
+
+
 def test_tile_entry_points_check_their_arguments():
     """argument checks of cgic_cut_tiles / cgic_entropy_maps_tiles come before any launch (host logic only)"""
     import ctypes
