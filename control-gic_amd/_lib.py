@@ -67,6 +67,12 @@ class PasteTile(C.Structure):
     _fields_ = [("src", _vp), ("image_stride", _i64), ("wx", _vp), ("wy", _vp), ("y0", _int), ("x0", _int), ("th", _int), ("tw", _int)]
 
 
+class PartitionTile(C.Structure):
+    """struct cgic_partition_tile (include/cgic_hip.h): one tile of cgic_partition_map -- the three masks OR the indices"""
+    _fields_ = [("mask_c", _vp), ("mask_m", _vp), ("mask_f", _vp), ("indices", _vp), ("image_stride_tiles", _i64),
+                ("y0", _int), ("x0", _int), ("th", _int), ("tw", _int), ("gh", _int), ("gw", _int)]
+
+
 class RateTile(C.Structure):
     """struct cgic_rate_tile (include/cgic_hip.h): one tile of cgic_rate_curve_tiles"""
     _fields_ = [("h16", _i32), ("w16", _i32), ("k_c", _i32), ("shape", _i32), ("image", _i32), ("reserved", _i32),
@@ -141,6 +147,7 @@ PROTOTYPES = {
     "cgic_cut_tiles": (_int, [_vp, _int, _i64, _i64, _i64, _int, C.POINTER(Tile), _vp]),
     "cgic_tile_weights_host": (_int, [_int, _int, C.POINTER(_f64)]),
     "cgic_paste_tiles": (_int, [_i64, _i64, _i64, _int, C.POINTER(PasteTile), _vp, _vp, _vp]),
+    "cgic_partition_map": (_int, [_vp, _int, _i64, _i64, _i64, _int, C.POINTER(PartitionTile), _vp, _vp, _vp]),
     "cgic_entropy_maps_tiles": (_int, [_vp, _int, _i64, _i64, _i64, _int, C.POINTER(_int), _i64, _i64, C.POINTER(_f32), _int, _f32, _vp, _vp, _vp,
                                        _vp, _vp]),
     "cgic_decoder_blend_medium_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _vp, _vp]),

@@ -70,6 +70,8 @@ class CompressedBatch:
     """streams of B images on the device: data [B, 5, slot] uint8, nbytes [B, 5] int32
     (-1 = not written in this mode, 0 = empty file)"""
 
+    partition_map = None          # compress_batch(save_img=True): fp32 [B,3,H,W], the input with its grain grid drawn in
+
     def __init__(self, data, nbytes, mode, h, w):
         self.data, self.nbytes, self.mode, self.h, self.w = data, nbytes, int(mode), int(h), int(w)
 

@@ -97,7 +97,7 @@ def _shape_groups(tiles):
     return sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
 
 
-def _check_cover(H, W, top, left, tiles):
+def _check_cover(H, W, top, left, tiles, what="paste_tiles", cover=True):
     """every pixel of the unpadded image belongs to exactly one tile (the closed form of cgic_paste_tiles holds for such grids only)"""
     clipped = []
     for (y, x, th, tw) in tiles:
@@ -107,9 +107,9 @@ def _check_cover(H, W, top, left, tiles):
     for k, (y0, y1, x0, x1) in enumerate(clipped):
         for (v0, v1, u0, u1) in clipped[:k]:
             if not (y1 <= v0 or v1 <= y0 or x1 <= u0 or u1 <= x0):
-                raise ValueError("paste_tiles: tiles overlap (the reference's grid never does: inference_high_resolution.py:112-125)")
-    if sum((y1 - y0) * (x1 - x0) for y0, y1, x0, x1 in clipped) != H * W:
-        raise ValueError(f"paste_tiles: the tile grid does not cover the {H}x{W} image (a pixel without a tile would be left unwritten)")
+                raise ValueError(f"{what}: tiles overlap (the reference's grid never does: inference_high_resolution.py:112-125)")
+    if cover and sum((y1 - y0) * (x1 - x0) for y0, y1, x0, x1 in clipped) != H * W:
+        raise ValueError(f"{what}: the tile grid does not cover the {H}x{W} image (a pixel without a tile would be left unwritten)")
 
 
 def _paste(pixels, H, W, top, left, tiles, groups, N, weighted, frames, out):
@@ -170,6 +170,101 @@ def paste_tiles(pixels, hw, tiles=None, groups=None, N=1, weighted=True, frames=
             any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
         raise ValueError("paste_tiles: groups must name every tile once, under its own shape")
     return _paste(pixels, H, W, top, left, tiles, groups, int(N), weighted, frames, out)
+
+
+def _partition(x, H, W, top, left, tiles, groups, masks, N, frames, out):
+    """cgic_partition_map for the tiles of N images: masks = per shape group (mask_c, mask_m, mask_f), each the image-major buffer of
+    the group's N * T tiles, read in place"""
+    from . import draw
+    if len(masks) != len(groups):
+        raise ValueError(f"partition_tiles: masks of {len(masks)} shape groups for {len(groups)}")
+    desc = []
+    for ((th, tw), idxs), m in zip(groups, masks):
+        T = len(idxs)
+        if th % 16 or tw % 16:
+            raise ValueError(f"partition_tiles: tile {th}x{tw}: the router's masks belong to tiles whose sides are multiples of 16")
+        m = list(m)
+        if len(m) != 3:
+            raise ValueError("partition_tiles: per shape group the router's three masks (coarse, medium, fine)")
+        _lib.require_device(*m)
+        _lib.require_int32_masks(*m)
+        for t, d in zip(m, (16, 8, 4)):
+            if t.numel() != N * T * (th // d) * (tw // d) or tuple(t.shape[-2:]) != (th // d, tw // d) or not t.is_contiguous() or t.device != x.device:
+                raise ValueError(f"partition_tiles: a mask of the {th}x{tw} tiles must be contiguous int32 [{N * T},1,{th // d},{tw // d}] (image-major) "
+                                 f"on {x.device}, got {tuple(t.shape)}")
+        for k, i in enumerate(idxs):
+            ptrs = [_lib.ptr(t) + k * (th // d) * (tw // d) * 4 for t, d in zip(m, (16, 8, 4))]
+            desc.append(_lib.PartitionTile(ptrs[0], ptrs[1], ptrs[2], None, T, tiles[i][0] - top, tiles[i][1] - left, th, tw, 0, 0))
+    return draw._launch(x, N, H, W, desc, frames, out, "partition_tiles")
+
+
+def _group_masks(tiled_list):
+    """per shape group the image-major mask buffers behind a list of TiledImages of one geometry: the shared buffers themselves where
+    the images are views of them one after the other (compress_tiled_batch, TiledCall), a concatenation otherwise"""
+    first = tiled_list[0]
+    for t in tiled_list[1:]:
+        if t.tiles != first.tiles or t.image_hw != first.image_hw or [g[0] for g in t.groups] != [g[0] for g in first.groups]:
+            raise ValueError("partition_tiles: the images differ in geometry")
+    out = []
+    for lane in range(len(first.groups)):
+        per = [t.groups[lane][2][1] for t in tiled_list]                  # per image: [mask_c, mask_m, mask_f] of its T tiles
+        trio = []
+        for j in range(3):
+            ms = [p[j] for p in per]
+            step = ms[0].numel() * ms[0].element_size()
+            store = ms[0].untyped_storage().data_ptr()
+            in_place = all(m.is_contiguous() and m.shape == ms[0].shape and m.untyped_storage().data_ptr() == store
+                           and m.data_ptr() == ms[0].data_ptr() + n * step for n, m in enumerate(ms))
+            if in_place:                                         # N consecutive views of one buffer: that buffer, as one view
+                base = ms[0]
+                trio.append(base.as_strided((len(ms) * base.shape[0],) + tuple(base.shape[1:]), base.stride(), base.storage_offset()))
+            else:
+                trio.append(torch.cat([m.contiguous() for m in ms]))
+        out.append(trio)
+    return out
+
+
+def partition_tiles(x, tiled, frames=False, out=None, tile=TILE, tiles=None, groups=None):
+    """the partition map of tiled images -- the picture inference_high_resolution.py's -w promises (:188-189) and never draws (it passes
+    False at :246) -- as ONE launch for all tiles of all N images (cgic_partition_map).  Defined as: per tile, the reference's
+    draw_triple_grain_256res (CGIC/modules/draw.py:78-119) on that tile of the PADDED image with that tile's grain indices, then the
+    unpad of :255; tiles never overlap, so that is well defined.
+    x: the unpadded images, fp32 [N,3,H,W] or uint8 frames [N,H,W,3].  tiled: a TiledImage (N = 1), the list of N from
+    compress_tiled_batch / TiledCall (their shared per-group mask buffers are read in place), or -- with the geometry from `tile`, or
+    from tiles= / groups= as paste_tiles takes them -- per shape group the router's three masks [N*T,1,..] (image-major).
+    -> fp32 [N,3,H,W] (line pixels -1), or with frames=True uint8 frames [N,H,W,3] (line pixels 1); x is not modified unless `out is x`.
+    With `out` nothing is allocated and nothing synchronises.  More than 84 tiles are several launches."""
+    from . import draw
+    _lib.require_device(x)
+    _, N, H, W = draw._image_shape(x, "partition_tiles")
+    if not x.is_contiguous():
+        if out is x:
+            raise ValueError("partition_tiles: an in-place draw needs a contiguous image")
+        x = x.contiguous()
+    (left, right, top, bottom), _ = compute_padding(H, W)
+    if isinstance(tiled, TiledImage):
+        tiled = [tiled]
+    if len(tiled) and isinstance(tiled[0], TiledImage):
+        first = tiled[0]
+        if tuple(first.image_hw) != (H, W) or len(tiled) != N:
+            raise ValueError(f"partition_tiles: {len(tiled)} tiled images of {tuple(first.image_hw)} for x {tuple(x.shape)}")
+        tiles = first.tiles
+        groups = [(tuple(first.tiles[idxs[0]][2:]), idxs) for idxs, _, _ in first.groups]
+        masks = _group_masks(tiled)
+    else:
+        masks = tiled
+        if tiles is None:
+            tiles = tile_grid(H + top + bottom, W + left + right, tile)
+        else:
+            # disjoint always (the library checks it per launch only, and more than 84 tiles are several launches); a hole is
+            # allowed where the caller's `out` already holds what the uncovered pixels keep
+            _check_cover(H, W, top, left, tiles, "partition_tiles", cover=out is None)
+        if groups is None:
+            groups = _shape_groups(tiles)
+        elif sorted(i for _, idxs in groups for i in idxs) != list(range(len(tiles))) or \
+                any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
+            raise ValueError("partition_tiles: groups must name every tile once, under its own shape")
+    return _partition(x, H, W, top, left, tiles, groups, masks, N, bool(frames), out)
 
 
 def to_frames(x, out=None):
@@ -530,6 +625,18 @@ class TiledCall:
         the weight factors were uploaded when this object was built; with `out` nothing is allocated"""
         left, _, top, _ = self.pad
         return _paste(pixels, self.H, self.W, top, left, self.tiles, self.groups, self.N, True, frames, out)
+
+    def partition(self, x, out=None, frames=False):
+        """the partition map of the images this call compressed last (partition_tiles for this call's geometry and its own mask
+        buffers, read in place): x = the unpadded images as __call__ takes them, fp32 [N,3,H,W] or uint8 frames [N,H,W,3]
+        -> fp32 [N,3,H,W], or uint8 frames [N,H,W,3].  One launch; capturable: with `out` nothing is allocated"""
+        from . import draw
+        _lib.require_device(x)
+        _, N, H, W = draw._image_shape(x, "TiledCall.partition")
+        if (N, H, W) != (self.N, self.H, self.W) or not x.is_contiguous() or x.device != self.dev:
+            raise ValueError("TiledCall.partition: x does not have the shape, device or layout this object was built for")
+        left, _, top, _ = self.pad
+        return _partition(x, H, W, top, left, self.tiles, self.groups, [t["mask"] for t in self._buf], N, bool(frames), out)
 
     def refresh_codebook(self):
         """after changing embedding.weight: rewrite the codebook image in place (HotCall / HotPathPipeline have the same method; __call__

@@ -11,6 +11,7 @@ import types
 import torch
 
 from . import _lib
+from . import draw as _draw
 from . import rate as _rate
 from .codec import GrainCodec
 from .entropy import Entropy
@@ -97,9 +98,11 @@ def _codec_for(model, h_indices=None):
     return c
 
 
-def compress_batch(model, input, h_indices=None, decode=True):
+def compress_batch(model, input, h_indices=None, decode=True, save_img=False):
     """batched CGIC.compress (model.py:206-401): -> (dec [B,3,H,W] or None, bpp list[B], CompressedBatch).
-    Every image is routed on its own thresholds (what B independent B=1 calls of the reference give)."""
+    Every image is routed on its own thresholds (what B independent B=1 calls of the reference give).
+    save_img: the returned CompressedBatch carries `.partition_map`, fp32 [B,3,H,W]: the input with the grain grid of the routing
+    that was used drawn in as -1 (draw.partition_map on the masks: one launch; model.py:213-214)."""
     assert len(input.shape) == 4                                         # model.py:207
     codec = _codec_for(model, h_indices)
     # "B independent B=1 calls": every image routed on its own thresholds, whatever the router's batch semantics
@@ -120,6 +123,8 @@ def compress_batch(model, input, h_indices=None, decode=True):
     comp = codec.compress(ind, grain_mask, mode)
     bpp = comp.bpp(input.shape[2] * input.shape[3])                      # model.py:223,233
     dec = _decode(model, codec, comp) if decode else None
+    if save_img:
+        comp.partition_map = _draw.partition_map(input.float(), grain_mask)
     return dec, bpp, comp
 
 
@@ -140,14 +145,17 @@ def _decode(model, codec, comp):
 def compress(self, input, path, h_indices=None, h_mask=None, save_img=False):
     """CGIC.compress with the reference's signature and return value (dec, bpp, partition_map); also
     leaves the reference's five .bin files for the image in `path` (model.py:226-249).  B must be 1 like
-    the reference; use compress_batch for more."""
-    if save_img:
-        raise NotImplementedError("partition-map drawing (CGIC/modules/draw.py) is outside the hot path")
+    the reference; use compress_batch for more.
+    save_img=True: partition_map = fp32 [1,3,H,W], the input with the grain grid drawn in as -1 (model.py:213-214), None otherwise.
+    Deliberate deviation: the map shows the routing that was USED -- draw.partition_map on the router's masks, bit-identical to the
+    reference's draw_triple_grain_256res on the masks' grain indices (draw.grain_map).  The stock encoder's own `grain_indices` is
+    a malformed [B,1,h] tensor (the permute at vqvae_blocks.py:357 puts the wrong axis under the argmax), whose picture is a few
+    meaningless lines; draw.draw_triple_grain_256res(input.clone(), grain_indices) reproduces that picture bit for bit."""
     if input.shape[0] != 1:
         raise IndexError("compress() takes one image like the reference (model.py:219); use compress_batch")
-    dec, bpp, comp = compress_batch(self, input, h_indices)
+    dec, bpp, comp = compress_batch(self, input, h_indices, save_img=bool(save_img))
     comp.write_legacy(path, 0)
-    return dec, bpp[0], None
+    return dec, bpp[0], comp.partition_map if save_img else None
 
 
 class AvgPool(torch.nn.Module):
@@ -207,6 +215,8 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
     from . import highres as _highres
     model.to_frames = _highres.to_frames                 # the way out: inference.py:163 + write_images (:103) as one launch
     model.paste_tiles = _highres.paste_tiles             # ... and the tiled one (inference_high_resolution.py:231-255)
+    model.partition_map = _draw.partition_map             # the grain grid of a batch (CGIC/modules/draw.py:78-119) as one launch
+    model.partition_tiles = _highres.partition_tiles      # ... and of tiled images (what inference_high_resolution.py -w promises)
     model._cgic_codec = None
     model._cgic_codec_key = None
     return model

@@ -13,6 +13,7 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     mc, mm, mf, ind, choice = torch.ops.cgic.route_to_bpp(ind_c, ind_m, ind_f, e16, e8, 0.1, budget, table)  # the rank picked on the device
     ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
     rec    = torch.ops.cgic.paste_tiles([tiles_of_group0, ...], H, W, N, 768, True, False)        # decoded tiles -> [N,3,H,W] (frames: uint8 [N,H,W,3])
+    pmap   = torch.ops.cgic.partition_map(x, mc, mm, mf, False)                                   # the grain grid drawn into the batch (draw.py:78-119)
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).
@@ -179,6 +180,25 @@ def _(pixels, H, W, N, tile, weighted, frames):
     if frames:
         return pixels[0].new_empty((N, H, W, 3), dtype=torch.uint8)
     return pixels[0].new_empty((N, 3, H, W), dtype=torch.float32)
+
+
+@torch.library.custom_op("cgic::partition_map", mutates_args=(), device_types=_DEV)
+def partition_map(x: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor, mask_f: torch.Tensor, frames: bool) -> torch.Tensor:
+    """the partition map of a batch (CGIC/modules/draw.py:78-119 on the masks' grain indices) in one launch: x fp32 [B,3,H,W] or uint8
+    frames [B,H,W,3] + the router's three int32 masks -> fp32 [B,3,H,W] (line pixels -1), or with frames the uint8 [B,H,W,3] (line pixels 1)"""
+    from .draw import partition_map as _partition_map
+    return _partition_map(x, (mask_c, mask_m, mask_f), frames=frames)
+
+
+@partition_map.register_fake
+def _(x, mask_c, mask_m, mask_f, frames):
+    if x.dtype == torch.uint8:
+        B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    else:
+        B, H, W = x.shape[0], x.shape[2], x.shape[3]
+    if frames:
+        return x.new_empty((B, H, W, 3), dtype=torch.uint8)
+    return x.new_empty((B, 3, H, W), dtype=torch.float32)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 13
+#define CGIC_ABI_VERSION 14
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -536,6 +536,53 @@ typedef struct cgic_paste_tile {
 } cgic_paste_tile;
 int cgic_paste_tiles(int64_t N, int64_t H, int64_t W, int ntiles, const cgic_paste_tile *tiles, float *out_f32,
                      unsigned char *out_u8, cgic_stream_t stream);
+/* ---------------------------------------------------------------------------
+ * Partition map (ABI 14): the picture of where the router spent coarse, medium and fine codes -- draw_triple_grain_256res
+ * (CGIC/modules/draw.py:78-119; called from model.py:213-214, log_images :421, inference.py -w :148-166 and promised by
+ * inference_high_resolution.py:188-189) -- for a batch or for all tiles of N tiled images as ONE launch.  The reference draws it
+ * with three nested Python loops and two strided slice assignments per cell (5376 cells per 256x256 image).  Per pixel the loops
+ * are a select.  With (gh, gw) the index grid of a tile of th x tw pixels, sh = th / gh, sw = tw / gw (integer divisions) and
+ * (y, x) the pixel's position inside the tile, the pixel of EVERY channel becomes a line pixel when any of these holds:
+ *     coarse (whatever the indices hold):  y < 4 sh (gh / 4)  and  x < 4 sw (gw / 4)  and  (y % (4 sh) == 0  or  x % (4 sw) == 0)
+ *     medium:  y < 2 sh (gh / 2)  and  x < 2 sw (gw / 2)  and  indices[2 (y / (2 sh)), 2 (x / (2 sw))] == 1   (the top-left cell of
+ *              the 2x2 block only)  and  (y % (2 sh) == 0  or  x % (2 sw) == 0)
+ *     fine:    y < sh gh  and  x < sw gw  and  indices[y / sh, x / sw] == 2  and  (y % sh == 0  or  x % sw == 0)
+ * and keeps the source value otherwise: bit-identical to the loops (tests/golden/partition.npz holds the reference's pictures).
+ *
+ *   src      device, the UNPADDED images: fp32 [N,3,H,W] (4-byte aligned), or with src_u8 the uint8 frames [N,H,W,3]
+ *   out_f32  device [N,3,H,W] or NULL;  out_u8  device [N,H,W,3] or NULL; at least one of them.  An output may BE src (the same
+ *            address and the same layout: an in-place draw, what the reference does); any other overlap of an output with src, or
+ *            of the two outputs, is refused
+ *   tiles    host [ntiles] (1 .. 84: what fits a 4 KB kernel-argument block next to the header; callers split larger sets):
+ *            every tile in ONE of two forms, the same for all tiles of a call
+ *              masks:    mask_c / mask_m / mask_f = device int32 (4-byte aligned), the router's masks of this tile of image 0:
+ *                        [th/16,tw/16], [th/8,tw/8], [th/4,tw/4]; th % 16 == tw % 16 == 0; the index grid is (th/4, tw/4) (gh, gw
+ *                        must be that or 0) and a cell's index is the FIRST maximum over (up4(mask_c), up2(mask_m), mask_f) with a
+ *                        nonzero element counting as 1 -- coarse -> 0, else medium -> 1, else fine -> 2, all zero -> 0: what the
+ *                        comment at vqvae_blocks.py:358 means and what argmax gives
+ *              indices:  indices = device int64 [gh,gw] (8-byte aligned) of this tile of image 0, the reference function's own
+ *                        argument, any values (only == 1 and == 2 matter); gh, gw >= 1 with th / gh >= 1 and tw / gw >= 1
+ *                        (CGIC_ERR_UNSUPPORTED otherwise); the three masks NULL
+ *            image_stride_tiles = tiles between this tile of image n and of image n + 1 (T of its shape group in an image-major
+ *            batch, 1 for a plain batch; 0 .. 2^31 - 1): each array advances by that many of its OWN tile sizes;
+ *            (y0, x0) = the tile's origin in UNPADDED image coordinates (negative inside the pad); th, tw in 1 .. 65535
+ * A line pixel is -1.0f in the fp32 output and 1 in the uint8 output: 1 is the wrap numpy performs on x86-64 for write_images'
+ * conversion (255 * -1.0f).astype(uint8) (inference_high_resolution.py:103; numpy leaves the cast of a negative float
+ * unspecified) -- a definition, as NaN -> 0 is for cgic_paste_tiles.  Any other pixel is the source value: fp32 -> fp32 and
+ * uint8 -> uint8 the value itself (trunc(255.0f * (b / 255.0f)) == b for all 256 bytes), fp32 -> uint8
+ * trunc(255.0f * clamp(p, 0, 1)) with NaN -> 0 (as cgic_paste_tiles), uint8 -> fp32 b / 255.0f (IEEE divide: T.ToTensor()).
+ * Tile pixels inside the pad are dropped; output pixels NO tile covers are left untouched.  The tiles, clipped to the image, must
+ * be pairwise disjoint (CGIC_ERR_UNSUPPORTED).  N <= 65535; H, W in 1 .. 65535.  All checks precede the launch; not available
+ * inside a launch group.
+ * ------------------------------------------------------------------------- */
+typedef struct cgic_partition_tile {
+    const int32_t *mask_c, *mask_m, *mask_f;
+    const int64_t *indices;
+    int64_t image_stride_tiles;
+    int y0, x0, th, tw, gh, gw;
+} cgic_partition_tile;
+int cgic_partition_map(const void *src, int src_u8, int64_t N, int64_t H, int64_t W, int ntiles, const cgic_partition_tile *tiles,
+                       float *out_f32, unsigned char *out_u8, cgic_stream_t stream);
 /* cgic_cut_tiles for the tiles of ONE shape + cgic_entropy_maps_f32 / _u8 on them, in one pass: a lane of the map kernel reads its pixels
  * from the source window (zeros inside the pad) and the tile batch is written as a by-product -- 12 B read + 12 B written per pixel
  * instead of 12 + 12 for the cut and 12 again for the maps.  Recorded like the other entropy calls inside a launch group.
