@@ -73,6 +73,17 @@ class PartitionTile(C.Structure):
                 ("y0", _int), ("x0", _int), ("th", _int), ("tw", _int), ("gh", _int), ("gw", _int)]
 
 
+class ContainerGroup(C.Structure):
+    """struct cgic_container_group (include/cgic_hip.h): the slot buffers of one group of cgic_container_pack / _unpack"""
+    _fields_ = [("data", _vp), ("nbytes", _vp), ("B", _i64), ("slot", _i64), ("mode", _int)]
+
+
+class ContainerEntry(C.Structure):
+    """struct cgic_container_entry (include/cgic_hip.h): one entry of the container, and where its streams live"""
+    _fields_ = [("image_id", C.c_uint32), ("y", C.c_uint32), ("x", C.c_uint32), ("height", C.c_uint32), ("width", C.c_uint32),
+                ("group", _i32), ("index", _i32)]
+
+
 class RateTile(C.Structure):
     """struct cgic_rate_tile (include/cgic_hip.h): one tile of cgic_rate_curve_tiles"""
     _fields_ = [("h16", _i32), ("w16", _i32), ("k_c", _i32), ("shape", _i32), ("image", _i32), ("reserved", _i32),
@@ -165,6 +176,10 @@ PROTOTYPES = {
                                      _i64, _vp, _vp, _vp, _vp]),
     "cgic_route_to_budget_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "cgic_route_to_budget": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgic_container_bound": (_sz, [C.POINTER(ContainerGroup), _int, _i64]),
+    "cgic_container_workspace_bytes": (_sz, [_i64]),
+    "cgic_container_pack": (_int, [C.POINTER(ContainerGroup), _int, C.POINTER(ContainerEntry), _i64, _vp, _i64, _vp, _vp, _vp]),
+    "cgic_container_unpack": (_int, [_vp, _vp, _i64, C.POINTER(ContainerGroup), _int, C.POINTER(ContainerEntry), _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -94,6 +94,11 @@ class CompressedBatch:
                  for s in range(_lib.NUM_STREAMS) if int(nb[b, s]) >= 0}
                 for b in range(self.batch)]
 
+    def pack(self, height, width, first_image_id=0):
+        """the container of this batch of whole images, built on the device: container.pack_device(self, ...) -> PackedContainer"""
+        from .container import pack_device
+        return pack_device(self, height, width, first_image_id)
+
     def total_bytes(self):
         """[B] int64 on the device: sum of stream sizes per image"""
         return self.nbytes.clamp(min=0).sum(dim=1, dtype=torch.int64)

@@ -300,6 +300,11 @@ class TiledImage:
         bits = sum(b * tw * th for b, (_, _, th, tw) in zip(self.tile_bpp(), self.tiles))
         return bits / self.image_hw[1] / self.image_hw[0]
 
+    def pack(self, image_id=0):
+        """the container of this image's tiles, built on the device: container.pack_device(self, ...) -> PackedContainer"""
+        from .container import pack_device
+        return pack_device(self, first_image_id=image_id)
+
     def streams(self):
         """per tile (row-major) {stream name: bytes}"""
         out = [None] * len(self.tiles)
@@ -692,7 +697,7 @@ class TiledCall:
 
 def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chain=False, decoder=None, decode=None, frames=False):
     """inverse of compress_tiled_batch for TiledImages of one geometry (from it, or from N compress_tiled calls on images
-    of one size, or rebuilt from containers): ONE decompress per shape group over all the images
+    of one size, or rebuilt from containers by container.load(...).tiled(hw)): ONE decompress per shape group over all the images
     -> list (per image) of per-tile (ind, masks, z_q); check=False: (that, [N * tiles] status tensor).
     decode(z_q [N*T,4,h,w], masks) -> pixels [N*T,3,th,tw]: called ONCE per shape group on the whole batch (not once per tile), then all
     tiles of all images are pasted in one launch (paste_tiles: the reference's blend + clamp + unpad, :248-255) -> (per_image, rec) with

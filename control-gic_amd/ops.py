@@ -14,6 +14,7 @@ ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (ther
     ind    = torch.ops.cgic.gather_grain_indices(ind_c, ind_m, ind_f, mc, mm, mf)                 # the merged latent's indices
     rec    = torch.ops.cgic.paste_tiles([tiles_of_group0, ...], H, W, N, 768, True, False)        # decoded tiles -> [N,3,H,W] (frames: uint8 [N,H,W,3])
     pmap   = torch.ops.cgic.partition_map(x, mc, mm, mf, False)                                   # the grain grid drawn into the batch (draw.py:78-119)
+    blob, total = torch.ops.cgic.container_pack(data, nbytes, mode, 256, 256, 0)                  # the batch as a container file, on the device
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).
@@ -245,6 +246,27 @@ def _(ind, mask_c, mask_m, mask_f, mode, table, hist):
     B, h, w = mask_f.shape[0], mask_f.shape[-2], mask_f.shape[-1]
     return (ind.new_empty((B, _lib.NUM_STREAMS, _slot_bytes(table, h, w)), dtype=torch.uint8),
             ind.new_empty((B, _lib.NUM_STREAMS), dtype=torch.int32))
+
+
+@torch.library.custom_op("cgic::container_pack", mutates_args=(), device_types=_DEV)
+def container_pack(data: torch.Tensor, nbytes: torch.Tensor, mode: int, height: int, width: int, first_image_id: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the container of one batch of whole images (container.pack_device on one group; cgic_container_pack): data uint8 [B,5,slot] and
+    nbytes int32 [B,5] as compress_streams returns them -> (blob uint8 [12 + 44 B + 5 B slot], total int64 [1]): blob[:total] ==
+    container.pack(entries_from_batch(...)); total < 0: a stream of the batch failed (cgic_container_pack)"""
+    from .codec import CompressedBatch
+    from .container import pack_device
+    _lib.require_device(data, nbytes)
+    if data.dim() != 3 or data.shape[1] != _lib.NUM_STREAMS or data.dtype != torch.uint8 or nbytes.dtype != torch.int32:
+        raise ValueError("container_pack: data uint8 [B,5,slot] and nbytes int32 [B,5]")
+    # (the grid of the latent is not part of the file: CompressedBatch only carries it for decompress)
+    p = pack_device(CompressedBatch(data.contiguous(), nbytes.contiguous(), mode, height // 4, width // 4), height, width, first_image_id)
+    return p.blob, p.total
+
+
+@container_pack.register_fake
+def _(data, nbytes, mode, height, width, first_image_id):
+    B, slot = data.shape[0], data.shape[2]
+    return data.new_empty((12 + 44 * B + _lib.NUM_STREAMS * B * slot,), dtype=torch.uint8), data.new_empty((1,), dtype=torch.int64)
 
 
 @torch.library.custom_op("cgic::rate_curve", mutates_args=(), device_types=_DEV)

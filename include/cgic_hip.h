@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 14
+#define CGIC_ABI_VERSION 15
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -815,6 +815,66 @@ int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, const int64_
                          const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio, const int32_t *ranks_dev, int64_t R,
                          const int64_t *budget_dev, int32_t *mask_c, int32_t *mask_m, int32_t *mask_f, int64_t *ind,
                          int64_t *choice_dev, void *workspace, cgic_stream_t stream);
+
+/* The container on the device (ABI 15): the blob of control_gic_amd/container.py -- version 1, flags 0:
+ *     "CGIC" | u16 version | u16 flags | u32 n_entries | n_entries x 44-byte entry header | payload
+ * with an entry header u32 image_id, y, x, height, width | u8 mode | 3 zero bytes | 5 x i32 stream length (-1 = not written), all
+ * little endian, and the payload the streams of entry 0 in stream order, entry 1 ... -- built from, and taken apart into, slot
+ * buffers as cgic_compress_streams writes and cgic_decompress_streams reads them, with no host loop and no synchronisation.
+ *
+ *   groups   host [G], G <= 64: per group  data   device [B, 5, slot] uint8, 16-byte aligned
+ *                                          nbytes device [B, 5] int32
+ *                                          B >= 0, slot a positive multiple of 16 below 2^31, mode 0 .. 6
+ *   entries  host [E], E <= 65535, in container order: the five header words of the entry, the group it lives in and its index
+ *            inside that group (0 <= index < B of the group; entries of different groups interleave freely, an image may appear
+ *            more than once)
+ * Both tables are consumed by the call (they travel in kernel-argument blocks: 64 entries a launch); nothing host-side has to
+ * outlive it, and a captured call replays with the tables it was recorded with.
+ *
+ * cgic_container_pack:
+ *   blob     device, `capacity` bytes, 16-byte aligned.  cgic_container_bound(groups, G, E) = 12 + 44 E + 5 E (largest slot) always
+ *            suffices
+ *   total    device int64 [1]: the bytes written -- blob[0 .. total) == container.pack of the same entries --, or a negative value:
+ *            the smallest nbytes word of the named streams if any is below -1 (what cgic_compress_streams leaves for a symbol
+ *            outside the table: CGIC_ERR_INVALID - 10; a length beyond its slot counts as CGIC_ERR_CAPACITY - 10), else
+ *            CGIC_ERR_CAPACITY - 10 if the blob does not fit `capacity`.  On a negative total the content of the blob is
+ *            unspecified, but no byte at or beyond `capacity` is touched; bytes at or beyond `total` are never written
+ *   workspace device, cgic_container_workspace_bytes(E) bytes, 16-byte aligned
+ * ceil(E / 64) + 2 launches ordered by the stream alone, no workgroup waits on another, no atomics on global memory: the stage
+ * launches (slot address and length word of every stream into the workspace, the entry headers into the blob), the scan (ONE
+ * workgroup: 5 E clamped lengths -> int64 offsets, the 12-byte header, total) and the copy (one thread per 16-byte word of the
+ * blob gathers every stream that overlaps it -- a word can hold many: the shortest non-empty file has 2 bytes, empty and absent
+ * streams make offsets coincide --: aligned 16-byte loads from the slots, a byte funnel shift, aligned 16-byte stores inside the
+ * payload and byte stores in its first and last word).
+ *
+ * cgic_container_unpack: the inverse
+ *   host_blob  host: the file, `bytes` long.  Checked in full before anything is enqueued: magic, version, n_entries == E, every
+ *            length >= -1, 12 + 44 E + the lengths == bytes, the mode byte of every entry == its group's mode, its streams the
+ *            set that mode writes (cgic_mode_streams), length + 8 <= slot of its group (CGIC_ERR_CAPACITY)
+ *   blob     device: the same bytes in ONE contiguous upload, 16-byte aligned, readable up to the next multiple of 16
+ *   groups, entries as above (of an entry only group and index are read); data / nbytes are the OUTPUTS: nbytes of all five streams
+ *            of every named image (-1 included); every stream copied to the start of its slot and zeros from its end to the end of
+ *            the 16-byte word that holds byte length + 7 (the slack the decoders' word fetches rely on); the rest of a slot, and
+ *            images no entry names, are left alone
+ * The same chain: stage (lengths re-read from the DEVICE copy, nbytes written), scan, and a scatter of one thread per 16-byte slot
+ * word (aligned loads from the blob, the funnel, an aligned store).
+ * Every host argument of both calls is checked before anything is enqueued.  Not inside a launch group. */
+typedef struct cgic_container_group {
+    void *data;
+    int32_t *nbytes;
+    int64_t B, slot;
+    int mode;
+} cgic_container_group;
+typedef struct cgic_container_entry {
+    uint32_t image_id, y, x, height, width;
+    int32_t group, index;
+} cgic_container_entry;
+size_t cgic_container_bound(const cgic_container_group *groups, int G, int64_t E);
+size_t cgic_container_workspace_bytes(int64_t E);
+int cgic_container_pack(const cgic_container_group *groups, int G, const cgic_container_entry *entries, int64_t E, uint8_t *blob,
+                        int64_t capacity, int64_t *total, void *workspace, cgic_stream_t stream);
+int cgic_container_unpack(const uint8_t *host_blob, const uint8_t *blob, int64_t bytes, const cgic_container_group *groups, int G,
+                          const cgic_container_entry *entries, int64_t E, void *workspace, cgic_stream_t stream);
 
 #ifdef __cplusplus
 }
