@@ -305,12 +305,12 @@ class LoadedContainer:
                 if first is None:
                     raise ValueError(f"LoadedContainer.tiled: image {v} has no tile at (0, 0)")
                 t = rect(first)[3] if any(r[1] > 0 for r in mine) else rect(first)[2] if any(r[0] > 0 for r in mine) else max(highres.TILE, ph, pw)
-            tiles = highres.tile_grid(ph, pw, int(t))
+            _, tiles, order = highres.tile_geometry(H, W, int(t))
             if len(mine) != len(by_image[v]) or sorted(mine) != sorted(tiles):
                 raise ValueError(f"LoadedContainer.tiled: the rectangles of image {v} are not the tile grid of a {H}x{W} image "
                                  f"(padded {ph}x{pw}, tile {t})")
             lanes = []
-            for (th, tw), idxs in highres._shape_groups(tiles):
+            for (th, tw), idxs in order:
                 at = [where[mine[tiles[i]]] for i in idxs]
                 if len({g for g, _ in at}) != 1:
                     raise ValueError(f"LoadedContainer.tiled: the {th}x{tw} tiles of image {v} were written in different modes")

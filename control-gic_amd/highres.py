@@ -8,6 +8,7 @@ sum(bpp_tile * tile_w * tile_h) / (W * H) of the UNPADDED image (:250,:256).
 Here tiles of equal shape are batched through the kernels together (router thresholds stay per tile =
 per image of the batch), the streams stay on the device, and the accounting is the reference's.
 """
+import ctypes
 import math
 
 import torch
@@ -71,7 +72,6 @@ def tile_weight_factors(n, axis, device=None):
     bit.  device None / "cpu": a host tensor; a HIP device: uploaded once and cached per (device, n, axis).  The first upload is a
     host-to-device copy and must happen OUTSIDE a graph capture (TiledCall makes its factors when it is built; otherwise call this,
     or paste once eagerly, before capturing)"""
-    import ctypes
     dev = torch.device("cpu" if device is None else device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -95,6 +95,45 @@ def _shape_groups(tiles):
     for i, (_, _, th, tw) in enumerate(tiles):
         by_shape.setdefault((th, tw), []).append(i)
     return sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+
+
+def tile_geometry(H, W, tile=TILE):
+    """the tiling of an unpadded HxW image -> (pad, tiles, groups): the centred pad (left, right, top, bottom) to multiples of 16, the
+    row-major tile grid of the padded image and its shape groups, largest first.  Bytes, pictures and bpp all follow this order"""
+    pad, _ = compute_padding(H, W)
+    left, right, top, bottom = pad
+    tiles = tile_grid(H + top + bottom, W + left + right, tile)
+    return pad, tiles, _shape_groups(tiles)
+
+
+def _check_groups(tiles, groups, what):
+    if sorted(i for _, idxs in groups for i in idxs) != list(range(len(tiles))) or \
+            any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
+        raise ValueError(f"{what}: groups must name every tile once, under its own shape")
+
+
+def _resolve_geometry(H, W, tile, tiles, groups, what, cover=True):
+    """(top, left, tiles, groups) of an unpadded HxW image: what tile_geometry derives from `tile`, or the caller's own tiles / groups,
+    checked"""
+    (left, _, top, _), grid, order = tile_geometry(H, W, tile)
+    if tiles is None:
+        tiles = grid
+    else:
+        _check_cover(H, W, top, left, tiles, what, cover)
+    if groups is None:
+        groups = order if tiles is grid else _shape_groups(tiles)
+    else:
+        _check_groups(tiles, groups, what)
+    return top, left, tiles, groups
+
+
+def _placed(tiles, groups, top, left):
+    """the tiles in launch order, shape group by shape group -> (group, position in the group, group size T, y0, x0, th, tw) with the
+    origin in UNPADDED coordinates (negative inside the pad): what a tile descriptor of the library is built from.  In an image-major
+    batch [N * T, ...] the tile sits `position` tiles behind image 0's first and T tiles before the next image's"""
+    for g, ((th, tw), idxs) in enumerate(groups):
+        for k, i in enumerate(idxs):
+            yield g, k, len(idxs), tiles[i][0] - top, tiles[i][1] - left, th, tw
 
 
 def _check_cover(H, W, top, left, tiles, what="paste_tiles", cover=True):
@@ -132,13 +171,10 @@ def _paste(pixels, H, W, top, left, tiles, groups, N, weighted, frames, out):
         out = torch.empty(want, dtype=dt, device=dev)
     elif tuple(out.shape) != want or out.dtype != dt or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"paste_tiles: out must be contiguous {dt} {list(want)} on {dev}")
-    desc = []
-    for ((th, tw), idxs), b in zip(groups, pixels):
-        wx = tile_weight_factors(tw, 0, dev).data_ptr() if weighted else None
-        wy = tile_weight_factors(th, 1, dev).data_ptr() if weighted else None
-        T, per = len(idxs), 3 * th * tw
-        for k, i in enumerate(idxs):
-            desc.append(_lib.PasteTile(b.data_ptr() + k * per * 4, T * per, wx, wy, tiles[i][0] - top, tiles[i][1] - left, th, tw))
+    wts = [(tile_weight_factors(tw, 0, dev).data_ptr(), tile_weight_factors(th, 1, dev).data_ptr()) if weighted else (None, None)
+           for (th, tw), _ in groups]
+    desc = [_lib.PasteTile(pixels[g].data_ptr() + k * 3 * th * tw * 4, T * 3 * th * tw, wts[g][0], wts[g][1], y0, x0, th, tw)
+            for g, k, T, y0, x0, th, tw in _placed(tiles, groups, top, left)]
     with torch.cuda.device(dev):
         stream = _lib.current_stream(dev)
         for at in range(0, len(desc), 96):                       # (cgic_paste_tiles takes 96 tiles a launch)
@@ -159,16 +195,7 @@ def paste_tiles(pixels, hw, tiles=None, groups=None, N=1, weighted=True, frames=
     -> [N,3,H,W] fp32, or uint8 frames [N,H,W,3].  With `out` (that shape, contiguous) nothing is allocated and nothing synchronises:
     capturable, once the weight factors of the tile extents are on the device (tile_weight_factors).  More than 96 tiles are several launches."""
     H, W = int(hw[0]), int(hw[1])
-    (left, right, top, bottom), _ = compute_padding(H, W)
-    if tiles is None:
-        tiles = tile_grid(H + top + bottom, W + left + right, tile)
-    else:
-        _check_cover(H, W, top, left, tiles)
-    if groups is None:
-        groups = _shape_groups(tiles)
-    elif sorted(i for _, idxs in groups for i in idxs) != list(range(len(tiles))) or \
-            any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
-        raise ValueError("paste_tiles: groups must name every tile once, under its own shape")
+    top, left, tiles, groups = _resolve_geometry(H, W, tile, tiles, groups, "paste_tiles")
     return _paste(pixels, H, W, top, left, tiles, groups, int(N), weighted, frames, out)
 
 
@@ -178,7 +205,7 @@ def _partition(x, H, W, top, left, tiles, groups, masks, N, frames, out):
     from . import draw
     if len(masks) != len(groups):
         raise ValueError(f"partition_tiles: masks of {len(masks)} shape groups for {len(groups)}")
-    desc = []
+    trios = []
     for ((th, tw), idxs), m in zip(groups, masks):
         T = len(idxs)
         if th % 16 or tw % 16:
@@ -192,9 +219,9 @@ def _partition(x, H, W, top, left, tiles, groups, masks, N, frames, out):
             if t.numel() != N * T * (th // d) * (tw // d) or tuple(t.shape[-2:]) != (th // d, tw // d) or not t.is_contiguous() or t.device != x.device:
                 raise ValueError(f"partition_tiles: a mask of the {th}x{tw} tiles must be contiguous int32 [{N * T},1,{th // d},{tw // d}] (image-major) "
                                  f"on {x.device}, got {tuple(t.shape)}")
-        for k, i in enumerate(idxs):
-            ptrs = [_lib.ptr(t) + k * (th // d) * (tw // d) * 4 for t, d in zip(m, (16, 8, 4))]
-            desc.append(_lib.PartitionTile(ptrs[0], ptrs[1], ptrs[2], None, T, tiles[i][0] - top, tiles[i][1] - left, th, tw, 0, 0))
+        trios.append(m)
+    desc = [_lib.PartitionTile(*[_lib.ptr(t) + k * (th // d) * (tw // d) * 4 for t, d in zip(trios[g], (16, 8, 4))], None, T, y0, x0, th, tw, 0, 0)
+            for g, k, T, y0, x0, th, tw in _placed(tiles, groups, top, left)]
     return draw._launch(x, N, H, W, desc, frames, out, "partition_tiles")
 
 
@@ -241,29 +268,19 @@ def partition_tiles(x, tiled, frames=False, out=None, tile=TILE, tiles=None, gro
         if out is x:
             raise ValueError("partition_tiles: an in-place draw needs a contiguous image")
         x = x.contiguous()
-    (left, right, top, bottom), _ = compute_padding(H, W)
     if isinstance(tiled, TiledImage):
         tiled = [tiled]
     if len(tiled) and isinstance(tiled[0], TiledImage):
         first = tiled[0]
         if tuple(first.image_hw) != (H, W) or len(tiled) != N:
             raise ValueError(f"partition_tiles: {len(tiled)} tiled images of {tuple(first.image_hw)} for x {tuple(x.shape)}")
-        tiles = first.tiles
-        groups = [(tuple(first.tiles[idxs[0]][2:]), idxs) for idxs, _, _ in first.groups]
-        masks = _group_masks(tiled)
+        (left, _, top, _), _ = compute_padding(H, W)
+        tiles, groups, masks = first.tiles, first.shape_groups(), _group_masks(tiled)
     else:
+        # the caller's tiles: disjoint always (the library checks it per launch only, and more than 84 tiles are several launches); a
+        # hole is allowed where the caller's `out` already holds what the uncovered pixels keep
+        top, left, tiles, groups = _resolve_geometry(H, W, tile, tiles, groups, "partition_tiles", cover=out is None)
         masks = tiled
-        if tiles is None:
-            tiles = tile_grid(H + top + bottom, W + left + right, tile)
-        else:
-            # disjoint always (the library checks it per launch only, and more than 84 tiles are several launches); a hole is
-            # allowed where the caller's `out` already holds what the uncovered pixels keep
-            _check_cover(H, W, top, left, tiles, "partition_tiles", cover=out is None)
-        if groups is None:
-            groups = _shape_groups(tiles)
-        elif sorted(i for _, idxs in groups for i in idxs) != list(range(len(tiles))) or \
-                any(tuple(tiles[i][2:]) != tuple(shape) for shape, idxs in groups for i in idxs):
-            raise ValueError("partition_tiles: groups must name every tile once, under its own shape")
     return _partition(x, H, W, top, left, tiles, groups, masks, N, bool(frames), out)
 
 
@@ -287,6 +304,10 @@ class TiledImage:
         self.pad = pad                    # (left, right, top, bottom)
         self.tiles = tiles                # [(y, x, th, tw)] row-major, padded coordinates
         self.groups = groups              # [(tile indices, CompressedBatch, encode outputs)]
+
+    def shape_groups(self):
+        """[((th, tw), tile indices)] in this image's group order: what paste_tiles / partition_tiles take as groups="""
+        return [(tuple(self.tiles[idxs[0]][2:]), idxs) for idxs, _, _ in self.groups]
 
     def tile_bpp(self):
         bpp = [None] * len(self.tiles)
@@ -378,19 +399,12 @@ def _cut_all(x, frames, N, H, W, top, left, tiles, order):
     """the tile batches of all shape groups from the unpadded image(s) in one launch -> [batch per group], batch
     [N, T, 3, th, tw] fp32 or [N, T, th, tw, 3] uint8 (inference_high_resolution.py:145-173 pad + :236-244 crop)"""
     _lib.require_device(x)
-    n = sum(len(idxs) for _, idxs in order)
-    desc = (_lib.Tile * n)()
-    batches, j = [], 0
-    for (th, tw), idxs in order:
-        T = len(idxs)
-        batch = torch.empty((N, T, th, tw, 3) if frames else (N, T, 3, th, tw), dtype=x.dtype, device=x.device)
-        per = 3 * th * tw
-        for k, i in enumerate(idxs):
-            desc[j] = _lib.Tile(batch.data_ptr() + k * per * batch.element_size(), T * per, tiles[i][0] - top, tiles[i][1] - left, th, tw)
-            j += 1
-        batches.append(batch)
+    batches = [torch.empty((N, len(idxs), th, tw, 3) if frames else (N, len(idxs), 3, th, tw), dtype=x.dtype, device=x.device)
+               for (th, tw), idxs in order]
+    desc = [_lib.Tile(batches[g].data_ptr() + k * 3 * th * tw * x.element_size(), T * 3 * th * tw, y0, x0, th, tw)
+            for g, k, T, y0, x0, th, tw in _placed(tiles, order, top, left)]
     with torch.cuda.device(x.device):
-        _lib.call("cgic_cut_tiles", _lib.ptr(x), int(frames), N, H, W, n, desc, _lib.current_stream(x.device))
+        _lib.call("cgic_cut_tiles", _lib.ptr(x), int(frames), N, H, W, len(desc), (_lib.Tile * len(desc))(*desc), _lib.current_stream(x.device))
     return batches
 
 
@@ -403,15 +417,10 @@ def _compress_groups(x, encode, codec, tile, concurrent, chain=False, fuse_maps=
         raise ValueError(f"expected [N,3,H,W] (or uint8 [N,H,W,3]), got {x.dtype} {tuple(x.shape)}")
     N = x.shape[0]
     H, W = (x.shape[1], x.shape[2]) if frames else (x.shape[2], x.shape[3])
-    pad, _ = compute_padding(H, W)
-    left, right, top, bottom = pad
-    tiles = tile_grid(H + top + bottom, W + left + right, tile)
-    by_shape = {}
-    for i, (_, _, th, tw) in enumerate(tiles):
-        by_shape.setdefault((th, tw), []).append(i)
-    groups = []
     # the largest group first: it is the long pole, and lane 0 (no fork latency) is its stream
-    order = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+    pad, tiles, order = tile_geometry(H, W, tile)
+    left, _, top, _ = pad
+    groups = []
     chain = chain and 1 < len(order) <= _lib.lib().cgic_group_max()
     fork = _Fork(x.device, concurrent and not chain)
     xv = x.permute(0, 3, 1, 2) if frames else x              # [N,3,H,W] view either way
@@ -505,9 +514,10 @@ def compress_tiled_batch(x, encode, codec, tile=TILE, concurrent=False, chain=Fa
     return assemble_tiled(hw, pad, tiles, groups, N)
 
 
-def assemble_tiled(hw, pad, tiles, groups, N):
+def assemble_tiled(hw, pad, tiles, groups, N, whole=True):
     """the N TiledImages of shape groups that hold the tiles of N images of one size image-major ([N * T, ...] per group:
-    (tile indices, CompressedBatch, (ind, masks, mode))), as views of the shared per-group buffers"""
+    (tile indices, CompressedBatch, (ind, masks, mode))), as views of the shared per-group buffers.  whole=False leaves out the mark that lets
+    decompress_tiled_batch read those buffers in place: for buffers that are only valid until their owner's next call (TiledCall)"""
     out = []
     for n in range(N):
         mine = []
@@ -518,7 +528,8 @@ def assemble_tiled(hw, pad, tiles, groups, N):
             mine.append((idxs, type(comp)(comp.data[sl], comp.nbytes[sl], comp.mode, comp.h, comp.w),
                          (ind.view(N * T, per)[sl].reshape(-1), [m[sl] for m in masks], mode)))
         t = TiledImage(hw, pad, tiles, mine)
-        t._whole = (groups, n, N)                 # decompress_tiled_batch of the whole list reads the shared buffers in place
+        if whole:
+            t._whole = (groups, n, N)             # decompress_tiled_batch of the whole list reads the shared buffers in place
         out.append(t)
     return out
 
@@ -530,13 +541,8 @@ def cut_groups(x, tile=TILE):
     if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
         raise ValueError(f"cut_groups takes fp32 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
     N, H, W = x.shape[0], x.shape[2], x.shape[3]
-    pad, _ = compute_padding(H, W)
-    left, right, top, bottom = pad
-    tiles = tile_grid(H + top + bottom, W + left + right, tile)
-    by_shape = {}
-    for i, (_, _, th, tw) in enumerate(tiles):
-        by_shape.setdefault((th, tw), []).append(i)
-    order = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+    pad, tiles, order = tile_geometry(H, W, tile)
+    left, _, top, _ = pad
     if len(tiles) <= 96:
         cut = _cut_all(x.contiguous(), False, N, H, W, top, left, tiles, order)
     else:
@@ -556,7 +562,6 @@ class TiledCall:
 
     def __init__(self, quantizer, coarse_ratio, medium_ratio, N, H, W, frequency=None, decode=True, frames=False, decoder=None, tile=TILE,
                  prepare=True):
-        import ctypes
         from .codec import GrainCodec, _decoder_flag
         from .quantize import prepare_codebook
         w = quantizer.embedding.weight
@@ -568,13 +573,8 @@ class TiledCall:
         self.prepared = prepare_codebook(w) if prepare else None
         self._prepared_version = w._version
         self.decoder = _decoder_flag(decoder)
-        self.pad, _ = compute_padding(H, W)
-        left, right, top, bottom = self.pad
-        self.tiles = tile_grid(H + top + bottom, W + left + right, tile)
-        by_shape = {}
-        for i, (_, _, th, tw) in enumerate(self.tiles):
-            by_shape.setdefault((th, tw), []).append(i)
-        self.groups = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+        self.pad, self.tiles, self.groups = tile_geometry(H, W, tile)
+        left, _, top, _ = self.pad
         l = _lib.lib()
         if len(self.groups) > l.cgic_group_max():
             raise ValueError(f"{len(self.groups)} tile shapes; cgic_compress_tiled takes at most {l.cgic_group_max()}")
@@ -652,7 +652,6 @@ class TiledCall:
             self._prepared_version = self.vq.embedding.weight._version
 
     def __call__(self, x, zs):
-        import ctypes
         from .codec import CompressedBatch
         N, H, W = self.N, self.H, self.W
         if tuple(x.shape) != ((N, H, W, 3) if self.frames else (N, 3, H, W)) or x.dtype != (torch.uint8 if self.frames else torch.float32) \
@@ -682,17 +681,21 @@ class TiledCall:
         self.decoded = [(t["dind"], t["dmask"], t["dz_q"], t["status"]) for t in self._buf] if self._decode else None
         if N == 1:
             return TiledImage((H, W), self.pad, self.tiles, groups)
-        out = []
-        for n in range(N):
-            mine = []
-            for idxs, comp, (ind, masks, mode_) in groups:
-                T = len(idxs)
-                sl = slice(n * T, (n + 1) * T)
-                per = ind.numel() // (N * T)
-                mine.append((idxs, CompressedBatch(comp.data[sl], comp.nbytes[sl], comp.mode, comp.h, comp.w),
-                             (ind.view(N * T, per)[sl].reshape(-1), [m[sl] for m in masks], mode_)))
-            out.append(TiledImage((H, W), self.pad, self.tiles, mine))
-        return out
+        return assemble_tiled((H, W), self.pad, self.tiles, groups, N, whole=False)
+
+
+def _decompress_chain(comps, codec, dev, decoder):
+    """chain=True of the two decompress drivers: the decoder and the merge of all shape groups (`comps`: one CompressedBatch each) as ONE
+    launch each (see compress_tiled), and one status buffer for all of them: no concatenation kernel afterwards
+    -> ([(ind, masks, z_q, status) per group], the status of all groups)"""
+    status_all = torch.empty(sum(c.batch for c in comps), dtype=torch.int32, device=dev)
+    outs, at = [], 0
+    with _lib.launch_group(len(comps), [c.batch * c.h * c.w for c in comps], dev) as g:
+        for k, comp in enumerate(comps):
+            g.select(k)
+            outs.append(codec.decompress(comp, status=status_all[at:at + comp.batch], decoder=decoder))
+            at += comp.batch
+    return outs, status_all
 
 
 def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chain=False, decoder=None, decode=None, frames=False):
@@ -736,14 +739,7 @@ def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chai
             outs.append(codec.decompress(comp, decoder=decoder))
     status_all = None
     if chain:
-        # the decoder and the merge of all shape groups as ONE launch each (see compress_tiled); one status buffer for all of them
-        status_all = torch.empty(sum(c.batch for c in pending), dtype=torch.int32, device=dev)
-        at = 0
-        with _lib.launch_group(len(pending), [c.batch * c.h * c.w for c in pending], dev) as g:
-            for k, comp in enumerate(pending):
-                g.select(k)
-                outs.append(codec.decompress(comp, status=status_all[at:at + comp.batch], decoder=decoder))
-                at += comp.batch
+        outs, status_all = _decompress_chain(pending, codec, dev, decoder)
     for (idxs, _, _), (ind, masks, zq, status) in zip(first.groups, outs):
         statuses.append(status)
         T = len(idxs)
@@ -757,10 +753,9 @@ def decompress_tiled_batch(tiled_list, codec, concurrent=False, check=True, chai
         raise RuntimeError("corrupt tile stream")
     if decode is None:
         return per_image if check else (per_image, all_status)
-    groups = [(tuple(first.tiles[idxs[0]][2:]), idxs) for idxs, _, _ in first.groups]
     pixels = [decode(zq, masks).contiguous() for _, masks, zq, _ in outs]          # ONE decoder call per shape group
     left, _, top, _ = first.pad
-    rec = _paste(pixels, first.image_hw[0], first.image_hw[1], top, left, first.tiles, groups, N, True, frames, None)
+    rec = _paste(pixels, first.image_hw[0], first.image_hw[1], top, left, first.tiles, first.shape_groups(), N, True, frames, None)
     return (per_image, rec) if check else (per_image, rec, all_status)
 
 
@@ -777,18 +772,7 @@ def decompress_tiled(tiled, codec, decode=None, concurrent=False, check=True, ch
     dev = tiled.groups[0][1].data.device if tiled.groups else None
     chain = chain and dev is not None and 1 < len(tiled.groups) <= _lib.lib().cgic_group_max()
     fork = _Fork(dev, concurrent and dev is not None and not chain)
-    outs = []
-    # chain: the decoder and the merge of all shape groups as ONE launch each (see compress_tiled)
-    status_all = None
-    if chain:
-        # (one status buffer for all groups: no concatenation kernel afterwards)
-        status_all = torch.empty(sum(c.batch for _, c, _ in tiled.groups), dtype=torch.int32, device=dev)
-        at = 0
-        with _lib.launch_group(len(tiled.groups), [c.batch * c.h * c.w for _, c, _ in tiled.groups], dev) as g:
-            for lane, (_, comp, _) in enumerate(tiled.groups):
-                g.select(lane)
-                outs.append(codec.decompress(comp, status=status_all[at:at + comp.batch], decoder=decoder))
-                at += comp.batch
+    outs, status_all = _decompress_chain([c for _, c, _ in tiled.groups], codec, dev, decoder) if chain else ([], None)
     for lane, (idxs, comp, _) in enumerate(tiled.groups):
         if not chain:
             with fork.on(lane):

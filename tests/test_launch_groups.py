@@ -263,10 +263,7 @@ def test_cut_tiles_equals_pad_then_crop(H, W, frames):
     (left, right, top, bottom), _ = highres.compute_padding(H, W)
     padded = torch.nn.functional.pad(xc, (left, right, top, bottom), mode="constant", value=0)
     tiles = highres.tile_grid(H + top + bottom, W + left + right)
-    by_shape = {}
-    for i, (_, _, th, tw) in enumerate(tiles):
-        by_shape.setdefault((th, tw), []).append(i)
-    order = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+    order = highres._shape_groups(tiles)
     batches = highres._cut_all(x, frames, N, H, W, top, left, tiles, order)
     torch.cuda.synchronize()
     for ((th, tw), idxs), batch in zip(order, batches):
@@ -344,10 +341,7 @@ def test_maps_of_tiles_in_one_pass_equal_cut_then_maps(H, W, frames):
         x[:, :, : H // 3, : W // 2] = 0.25
     (left, right, top, bottom), _ = highres.compute_padding(H, W)
     tiles = highres.tile_grid(H + top + bottom, W + left + right)
-    by_shape = {}
-    for i, (_, _, th, tw) in enumerate(tiles):
-        by_shape.setdefault((th, tw), []).append(i)
-    order = sorted(by_shape.items(), key=lambda kv: -len(kv[1]) * kv[0][0] * kv[0][1])
+    order = highres._shape_groups(tiles)
     cut = highres._cut_all(x, frames, N, H, W, top, left, tiles, order)
     ref = []
     for ((th, tw), idxs), batch in zip(order, cut):
