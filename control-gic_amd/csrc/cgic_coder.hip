@@ -28,6 +28,7 @@
 // checked against it through the oracle + tests/golden/{coders,compress_cfg1}.npz.
 // (round 3: this file is the ENCODE side; the decoders live in cgic_decode.hip / cgic_decode_ss.hip)
 #include "cgic_coder_dev.h"
+#include "cgic_coder_plan.h"
 
 namespace cgic {
 
@@ -36,11 +37,8 @@ __device__ long long g_phase_clk[32];
 __device__ long long g_blk_t[2 * 4096];
 #endif
 
-// 1024 -> 512 in round 3: with four batches in flight 36.3 -> 35.5 us per step (smaller workgroups find a CU sooner); alone +0.5 us
-constexpr int kEncThreads = 512;         // x kEncItems = 4096 positions per scan round: one round per 256x256 stream
-constexpr int kEncItems = 4;            // consecutive positions per thread per scan round
-constexpr int kLdsPos = 8192;           // streams up to this many positions keep phase-A results in LDS
-constexpr int kLdsPosSmall = 4096;              // ... and the small instantiation of the compress kernel (grids up to 64x64)
+// (kEncThreads, kLdsPos, kLdsPosSmall, kEncPartPos, kEncMaxParts: cgic_coder_plan.h, with the host path's decisions)
+constexpr int kEncItems = 4;            // consecutive positions per thread per scan round: x kEncThreads = 4096 per round
 
 // -------------------------------------------------------------------------------------------
 // encode
@@ -160,8 +158,6 @@ __device__ int pack_huffman_stream(const TableDev &t, unsigned long long carry, 
 // ranges).  A part compacts and sizes its own range, tells the others (symbols, bits, its first 32 code bits), learns where
 // its bits start from the parts before it, and packs the output words whose FIRST payload bit is its own; the tail of its last
 // word comes from the heads of the parts behind it.  No atomics on the output, no pre-zeroed buffer.
-constexpr int kEncPartPos = 4096;         // positions per part of a split stream: measured 8192 -> 14.1 us, 4096 -> 12.2 us, 3072 -> 12.2 us (8 tiles of 768x768)
-constexpr int kEncMaxParts = 7;           // descriptors of a stream fit two ticket slots: 4 words per part + the reader count
 constexpr int kEncDoneWord = 4 * kEncMaxParts;
 struct EncExchange {
     unsigned int *tick;      // 2 ticket slots (zero when the launch starts): [4g..4g+3] = {symbols, bits, head, 1 ok | 2 error}
@@ -520,8 +516,9 @@ __device__ __forceinline__ void compress_streams_body(const CompressArgs &a, con
             const int64_t gh = h >> sh, gw = w >> sh, npos = gh * gw;
             const int32_t *mask = (s == 0 ? a.mc : s == 1 ? a.mm : a.mf) + b * npos;
             const int64_t *ind = a.ind + b * h * w;
-            // this workgroup's positions: all of them, or the part-th of nparts ranges (whole groups of four)
-            const int64_t per = nparts > 1 ? (((npos + nparts - 1) / nparts) + 3) & ~(int64_t)3 : npos;
+            // this workgroup's positions: all of them, or the part-th of nparts ranges (whole groups of four: the function by which
+            // the host sizes the staging, cgic_coder_plan.h)
+            const int64_t per = nparts > 1 ? enc_part_positions(npos, nparts) : npos;
             const int64_t pos0 = (int64_t)part * per < npos ? (int64_t)part * per : npos;
             const int64_t mypos = pos0 + per < npos ? per : npos - pos0;
             EncStorage st, st_glob;
@@ -662,30 +659,27 @@ extern "C" int cgic_mode_streams(int mode)
 extern "C" size_t cgic_stream_capacity(const cgic_table *t, int64_t n)
 {
     if (!t || n < 0) return 0;
-    const uint64_t bits = (uint64_t)cgic_table_max_len(t) * (uint64_t)n;
-    return align16((size_t)(bits / 8 + 2) + 8);    // header + pad byte + word-store/fetch slack
+    return stream_capacity(cgic_table_max_len(t), n);
 }
 
 extern "C" size_t cgic_stream_workspace_bytes(int64_t n)
 {
-    return n > kLdsPos ? align16((size_t)n * 4) + align16((size_t)n * 2) : 0;
+    return stream_workspace_bytes(n);
 }
 
 extern "C" size_t cgic_compress_slot_bytes(const cgic_table *t, int64_t h, int64_t w)
 {
     if (!t || h <= 0 || w <= 0) return 0;
-    const size_t a = cgic_stream_capacity(t, h * w);
-    const size_t m = align16((size_t)((h / 2) * (w / 2) / 8 + 2) + 8);
-    return a > m ? a : m;
+    return compress_slot_bytes(cgic_table_max_len(t), h, w);
 }
-
-static size_t ws_stride(int64_t h, int64_t w) { return ((size_t)(h * w) + 7) & ~(size_t)7; }
 
 extern "C" size_t cgic_compress_workspace_bytes(int64_t B, int64_t h, int64_t w)
 {
-    if (B <= 0 || h * w <= kLdsPos) return 0;
-    return (size_t)B * 3 * ws_stride(h, w) * (sizeof(uint32_t) + sizeof(uint16_t));
+    return compress_ws(B, h, w).bytes;
 }
+
+// check the arguments, plan (cgic_coder_plan.h), then issue: a call that is refused has taken no ticket, set no attribute and
+// enqueued nothing
 extern "C" int cgic_compress_streams(const cgic_table *t, const int64_t *ind, const int32_t *mask_c,
                                      const int32_t *mask_m, const int32_t *mask_f, int64_t B, int64_t h,
                                      int64_t w, int mode, uint8_t *out, int64_t slot, int32_t *nbytes,
@@ -694,67 +688,43 @@ extern "C" int cgic_compress_streams(const cgic_table *t, const int64_t *ind, co
     int rc = check_grid(B, h, w, mode);
     if (rc) return rc;
     CGIC_REQUIRE(t && ind && mask_c && mask_m && mask_f && out && nbytes, CGIC_ERR_INVALID, "compress_streams: NULL argument");
-    CGIC_REQUIRE(slot % 16 == 0 && (size_t)slot >= cgic_compress_slot_bytes(t, h, w), CGIC_ERR_CAPACITY,
-                 "compress_streams: slot=%lld, need a multiple of 16 >= %zu", (long long)slot, cgic_compress_slot_bytes(t, h, w));
-    CGIC_REQUIRE(cgic_table_num_symbols(t) <= 65536, CGIC_ERR_UNSUPPORTED, "table too large");
-    CGIC_REQUIRE((uint64_t)cgic_table_max_len(t) * (uint64_t)(h * w) < 0xFFFFFF00ull, CGIC_ERR_UNSUPPORTED,
-                 "compress_streams: a stream could exceed 2^32 bits");
-    CGIC_REQUIRE(workspace || cgic_compress_workspace_bytes(B, h, w) == 0, CGIC_ERR_INVALID,
-                 "compress_streams: workspace required for %lldx%lld grids", (long long)h, (long long)w);
-    if (B == 0) return CGIC_OK;
+    CompressShape shape;
+    shape.B = B; shape.h = h; shape.w = w; shape.slot = slot;
+    shape.max_len = cgic_table_max_len(t); shape.nsym = cgic_table_num_symbols(t);
+    shape.has_hist = hist != nullptr; shape.has_workspace = workspace != nullptr;
+    CompressPlan p;
+    const char *why = "";
+    rc = compress_plan(shape, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+    if (p.jobs == 0) return CGIC_OK;
     CompressArgs a;
     rc = table_device_view(t, &a.tab);
     if (rc) return rc;
     a.ind = ind; a.mc = mask_c; a.mm = mask_m; a.mf = mask_f; a.h = h; a.w = w;
     a.stream_mask = kModeStreams[mode];
     a.out = out; a.slot = slot; a.nbytes = nbytes;
-    CGIC_REQUIRE(!hist || cgic_table_num_symbols(t) <= kLdsPos, CGIC_ERR_UNSUPPORTED, "compress_streams: hist needs n <= %d", kLdsPos);
     a.hist = (unsigned long long *)hist;
-    a.ws_stride = (int64_t)ws_stride(h, w);
+    a.ws_stride = (int64_t)p.ws.stride;
     a.ws_end = (uint32_t *)workspace;
-    a.ws_sym = workspace ? (uint16_t *)((char *)workspace + (size_t)B * 3 * ws_stride(h, w) * sizeof(uint32_t)) : nullptr;
-    // Streams beyond kLdsPos positions are split over workgroups of at most ~kLdsPos positions each (a 768x768 tile: fine
-    // 36 864 positions -> 5 parts, medium 9216 -> 2) when the launch is small enough for the ticket pool; every part stages
-    // 2 bytes per position of its range in dynamic LDS (static: 57.5 KB).
-    a.parts[0] = a.parts[1] = a.parts[2] = 1;
+    a.ws_sym = workspace ? (uint16_t *)((char *)workspace + p.ws.sym_offset) : nullptr;
+    a.parts[0] = p.parts[0]; a.parts[1] = p.parts[1]; a.parts[2] = p.parts[2];
+    a.stage_positions = p.stage_positions;
+    a.combine = p.combine;
     a.tick = nullptr;
-    int64_t longest = 0;                  // positions the longest workgroup stages
-    const bool split = B * 6 <= kTicketRequestMax;
-    for (int g = 0; g < 3; ++g) {
-        const int64_t npos = (h >> (2 - g)) * (w >> (2 - g));
-        int64_t P = split && npos > kLdsPos ? (npos + kEncPartPos - 1) / kEncPartPos : 1;
-        P = P > kEncMaxParts ? kEncMaxParts : P;
-        a.parts[g] = (int)P;
-        const int64_t per = P > 1 ? (((npos + P - 1) / P) + 3) & ~(int64_t)3 : npos;
-        if (npos > kLdsPos && per > longest) longest = per;
-    }
-    size_t dyn = 0;
-    a.stage_positions = 0;
-    if (longest > 0 && (size_t)longest * 2 <= 96 * 1024) {
-        dyn = (((size_t)longest + 3) / 4 * 4 * 2 + 64 + 15) & ~(size_t)15;       // whole 4-entry groups (+ slack)
-        a.stage_positions = longest;
-        { int rc_ = ensure_dynamic_lds((const void *)compress_streams_kernel<kLdsPos>, dyn); if (rc_) return rc_; }
-    } else if (longest > 0) {
-        a.parts[0] = a.parts[1] = a.parts[2] = 1;                 // no staging room: the round-by-round form, unsplit
-    }
-    if (a.parts[0] + a.parts[1] + a.parts[2] > 3) {
-        rc = acquire_tickets((hipStream_t)stream, (int)(B * 6), &a.tick);
+    const auto kernel = p.small ? compress_streams_kernel<kLdsPosSmall> : compress_streams_kernel<kLdsPos>;
+    if (p.dyn_lds) {
+        rc = ensure_dynamic_lds((const void *)kernel, p.dyn_lds);
         if (rc) return rc;
     }
-    // every index stream fits the static LDS arrays and nothing is split: the short jobs of an image share one workgroup
-    a.combine = (!a.tick && h * w <= kLdsPos) ? 1 : 0;
-    const unsigned jobs = a.combine ? 3u + (hist ? 1u : 0u) : (unsigned)(a.parts[0] + a.parts[1] + a.parts[2]) + 2u + (hist ? 1u : 0u);
-    if (a.combine && h * w <= kLdsPosSmall && (!hist || cgic_table_num_symbols(t) <= kLdsPosSmall)) {
-        const dim3 grid_s((unsigned)B, jobs);
-        hipStream_t s_ = (hipStream_t)stream;
-        return launch_or_record(KID_NONE, grid_s, dim3(kEncThreads), 0, a, s_, [=] {
-            hipLaunchKernelGGL(compress_streams_kernel<kLdsPosSmall>, grid_s, dim3(kEncThreads), 0, s_, a);
-            return launch_check("compress_streams_kernel"); });
+    if (p.tickets) {
+        rc = acquire_tickets((hipStream_t)stream, p.tickets, &a.tick);
+        if (rc) return rc;
     }
-    const dim3 grid = a.tick ? dim3(jobs, (unsigned)B) : dim3((unsigned)B, jobs);
+    const dim3 grid = p.parts_fastest ? dim3(p.jobs, (unsigned)B) : dim3((unsigned)B, p.jobs);
+    const size_t dyn = p.dyn_lds;
     hipStream_t s = (hipStream_t)stream;
-    return launch_or_record(KID_COMPRESS, grid, dim3(kEncThreads), dyn, a, s, [=] {
-        hipLaunchKernelGGL(compress_streams_kernel<kLdsPos>, grid, dim3(kEncThreads), dyn, s, a);
+    return launch_or_record(p.recorded ? KID_COMPRESS : KID_NONE, grid, dim3(kEncThreads), dyn, a, s, [=] {
+        hipLaunchKernelGGL(kernel, grid, dim3(kEncThreads), dyn, s, a);
         return launch_check("compress_streams_kernel"); });
 }
 
@@ -777,7 +747,7 @@ extern "C" int cgic_encode_stream(const cgic_table *t, const void *syms, int ele
     if (rc) return rc;
     a.syms = syms; a.elem_bytes = elem_bytes; a.n = n; a.out = out; a.cap = cap; a.nbytes = nbytes;
     a.ws_end = (uint32_t *)workspace;
-    a.ws_sym = workspace ? (uint16_t *)((char *)workspace + align16((size_t)n * 4)) : nullptr;
+    a.ws_sym = workspace ? (uint16_t *)((char *)workspace + stream_workspace_sym_offset(n)) : nullptr;
     hipLaunchKernelGGL(encode_stream_kernel, dim3(1), dim3(kEncThreads), 0, (hipStream_t)stream, a);
     return launch_check("encode_stream_kernel");
 }

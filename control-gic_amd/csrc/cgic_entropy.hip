@@ -32,9 +32,8 @@
 
 namespace cgic {
 
-constexpr int kEntThreads = 256;
-constexpr int kEntWaves = kEntThreads / kWave;
-constexpr int kEntTilesPpw = 4;      // patches a wave walks in the windowed (tiles) form
+// (kEntThreads, kEntWaves, kEntTilesPpw, kEntMaxTiles, kBins: cgic_entropy_plan.h, with the host side's checks and grids)
+static_assert(kEntWaves * kWave == kEntThreads, "kEntWaves counts wavefronts of kWave lanes");
 constexpr int kWin = 2;            // bins evaluated per pixel: the two that bracket it
 constexpr int kHistStride = 36;    // dwords per bin: 4 sub-patches x 8 replicas + 4 pad (conflict-free b128 rows)
 constexpr float kFixScale = 67108864.f;           // 2^26: a replica collects <= 8 pixels with values <= 1, four replicas < 2^31
@@ -106,7 +105,6 @@ __device__ __forceinline__ unsigned int cvt_round_u32(float v)
 // reads its 4 pixels from the SOURCE window (zeros where the tile reaches into the centred pad), the tile itself is written to
 // x_out as a by-product (the conv encoder's input and the router's refinement pixels).  33 MB read + 33 MB written for a
 // 2040x1356 image instead of (33 + 33) for the cut and 33 again for the maps.
-constexpr int kEntMaxTiles = 48;
 struct EntWindow {
     const void *src;          // fp32 [N,3,srcH,srcW] or uint8 [N,srcH,srcW,3]
     int srcH, srcW, T;
@@ -492,51 +490,46 @@ __global__ __launch_bounds__(256) void entropy_ref_kernel(const float *__restric
 
 using namespace cgic;
 
+// Every entry point below: check the arguments (cgic_entropy_plan.h, in the order the checks always had), plan, then issue.
+#define CGIC_ENT_CHECK(check, ...) do { EntropyWhy why_; const int rc_ = check(__VA_ARGS__, &why_); CGIC_REQUIRE(rc_ == CGIC_OK, rc_, "%s", why_.text); } while (0)
+
+// one launch of `kernel` now, or its record under `kid` for cgic_group_launch
+template <class A>
+static int entropy_issue(int kid, void (*kernel)(A), const char *name, const EntropyPlan &p, const A &a, hipStream_t s)
+{
+    const dim3 grid(p.gx, p.gy, p.gz);
+    return launch_or_record(kid, grid, dim3(kEntThreads), 0, a, s, [=] {
+        hipLaunchKernelGGL(kernel, grid, dim3(kEntThreads), 0, s, a);
+        return launch_check(name); });
+}
+
 static int entropy_maps_launch(const void *x, bool u8, int64_t B, int64_t H, int64_t W, const float *bins, int nbins, float sigma,
                                float *x_out, float *e8, float *e16, float *flat8, cgic_stream_t stream)
 {
     CGIC_REQUIRE(x && bins, CGIC_ERR_INVALID, "entropy: x and bins must not be NULL");
-    CGIC_REQUIRE(nbins == kBins, CGIC_ERR_UNSUPPORTED, "entropy: nbins=%d; the reference uses 32 (model.py:480)", nbins);
-    CGIC_REQUIRE(B >= 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, CGIC_ERR_INVALID,
-                 "entropy: H=%lld W=%lld must be positive multiples of 16", (long long)H, (long long)W);
-    CGIC_REQUIRE(B <= 65535 && H / 16 <= 65535, CGIC_ERR_UNSUPPORTED, "entropy: batch/height exceed the grid limits");
-    // The two-bin window drops kernel values <= exp(-0.5 ((2/31) / sigma)^2): 6.5e-9 at the bound below, 9e-10 at the
-    // reference's sigma
-    CGIC_REQUIRE(sigma > 0.f && sigma <= 0.0105f, CGIC_ERR_UNSUPPORTED,
-                 "entropy: sigma=%g; the 2-bin window assumes the reference's sigma=0.01 (model.py:481)", sigma);
-    for (int i = 1; i < kBins; ++i)
-        CGIC_REQUIRE(fabsf((bins[i] - bins[i - 1]) - 2.0f / 31.0f) < 1e-5f, CGIC_ERR_UNSUPPORTED,
-                     "entropy: bins are not linspace(-1, 1, 32)");
-    if (B == 0 || (!e8 && !e16 && !flat8 && !(u8 && x_out))) return CGIC_OK;
-
-    BinsArg ba;
-    memcpy(ba.v, bins, sizeof(ba.v));
-    hipStream_t s = (hipStream_t)stream;
+    CGIC_ENT_CHECK(entropy_nbins_check, nbins);
+    CGIC_ENT_CHECK(entropy_shape_check, B, H, W);
+    CGIC_ENT_CHECK(entropy_setup_check, sigma, bins, "2-bin");
     // a wave walks `ppw` patches of its row band: 4 for a 256-wide image (one workgroup per 16 rows)
     const int ppw = 4;
-    const int64_t per_wg = (int64_t)kEntWaves * ppw;
-    dim3 grid((unsigned)((W / 16 + per_wg - 1) / per_wg), (unsigned)(H / 16), (unsigned)B);
-    // exp(-0.5 (r/sigma)^2) = exp2(c r^2), c = -0.5 log2(e) / sigma^2 (float64 on the host, rounded once)
-    const float exp2_scale = (float)(-0.5 * 1.4426950408889634 / ((double)sigma * (double)sigma));
+    const EntropyPlan p = entropy_plan(H, W, B, ppw, sigma, e8 || e16 || flat8 || (u8 && x_out));
+    if (p.nothing) return CGIC_OK;
+
+    hipStream_t s = (hipStream_t)stream;
     EntArgs a;
-    a.x = x; a.H = H; a.W = W; a.exp2_scale = exp2_scale; a.ppw = ppw; a.e8 = e8; a.e16 = e16; a.x_out = u8 ? x_out : nullptr; a.flat8 = flat8;
-    a.bins = ba;
+    a.x = x; a.H = H; a.W = W; a.exp2_scale = p.exp2_scale; a.ppw = ppw; a.e8 = e8; a.e16 = e16; a.x_out = u8 ? x_out : nullptr; a.flat8 = flat8;
+    memcpy(a.bins.v, bins, sizeof(a.bins.v));
 #ifdef CGIC_DEV_KNOBS
     // dev: pad the workgroup's LDS so that fewer of them fit a CU (co-residency experiments)
     const int pad = dev_knob("CGIC_ENT_PAD");
     if (pad > 0 && !u8 && !group_recording()) {
         CGIC_HIP_TRY(hipFuncSetAttribute((const void *)entropy_maps_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, pad));
-        hipLaunchKernelGGL(entropy_maps_kernel<false>, grid, dim3(kEntThreads), (size_t)pad, s, a);
+        hipLaunchKernelGGL(entropy_maps_kernel<false>, dim3(p.gx, p.gy, p.gz), dim3(kEntThreads), (size_t)pad, s, a);
         return launch_check("entropy_maps_kernel");
     }
 #endif
-    if (u8)
-        return launch_or_record(KID_ENTROPY_U8, grid, dim3(kEntThreads), 0, a, s, [=] {
-            hipLaunchKernelGGL(entropy_maps_kernel<true>, grid, dim3(kEntThreads), 0, s, a);
-            return launch_check("entropy_maps_kernel"); });
-    return launch_or_record(KID_ENTROPY_F32, grid, dim3(kEntThreads), 0, a, s, [=] {
-        hipLaunchKernelGGL(entropy_maps_kernel<false>, grid, dim3(kEntThreads), 0, s, a);
-        return launch_check("entropy_maps_kernel"); });
+    return u8 ? entropy_issue(KID_ENTROPY_U8, entropy_maps_kernel<true>, "entropy_maps_kernel", p, a, s)
+              : entropy_issue(KID_ENTROPY_F32, entropy_maps_kernel<false>, "entropy_maps_kernel", p, a, s);
 }
 
 template <bool U8>
@@ -560,40 +553,26 @@ extern "C" int cgic_entropy_maps_tiles(const void *src, int is_u8, int64_t N, in
                                        float *e8, float *e16, float *flat8, cgic_stream_t stream)
 {
     CGIC_REQUIRE(src && bins && origins && x_out, CGIC_ERR_INVALID, "entropy_maps_tiles: src, bins, origins and x_out must not be NULL");
-    CGIC_REQUIRE(nbins == kBins, CGIC_ERR_UNSUPPORTED, "entropy: nbins=%d; the reference uses 32 (model.py:480)", nbins);
-    CGIC_REQUIRE(N >= 0 && H > 0 && W > 0 && H < (1 << 30) && W < (1 << 30), CGIC_ERR_INVALID, "entropy_maps_tiles: bad source shape");
-    CGIC_REQUIRE(T >= 1 && T <= kEntMaxTiles, CGIC_ERR_UNSUPPORTED, "entropy_maps_tiles: %d tiles per image in this group (1..%d): cut them with cgic_cut_tiles",
-                 T, kEntMaxTiles);
-    CGIC_REQUIRE(th > 0 && tw > 0 && th % 16 == 0 && tw % 16 == 0, CGIC_ERR_INVALID,
-                 "entropy_maps_tiles: tile %lldx%lld must be positive multiples of 16", (long long)th, (long long)tw);
-    CGIC_REQUIRE(N * T <= 65535 && th / 16 <= 65535, CGIC_ERR_UNSUPPORTED, "entropy: batch/height exceed the grid limits");
-    CGIC_REQUIRE(sigma > 0.f && sigma <= 0.0105f, CGIC_ERR_UNSUPPORTED,
-                 "entropy: sigma=%g; the 2-bin window assumes the reference's sigma=0.01 (model.py:481)", sigma);
-    for (int i = 1; i < kBins; ++i)
-        CGIC_REQUIRE(fabsf((bins[i] - bins[i - 1]) - 2.0f / 31.0f) < 1e-5f, CGIC_ERR_UNSUPPORTED, "entropy: bins are not linspace(-1, 1, 32)");
+    CGIC_ENT_CHECK(entropy_nbins_check, nbins);
+    CGIC_ENT_CHECK(entropy_shape_check, N, H, W, T, th, tw);
+    CGIC_ENT_CHECK(entropy_setup_check, sigma, bins, "2-bin");
     CGIC_REQUIRE((reinterpret_cast<uintptr_t>(x_out) & 15) == 0 && (!is_u8 || (reinterpret_cast<uintptr_t>(src) & 3) == 0), CGIC_ERR_INVALID,
                  "entropy_maps_tiles: x_out must be 16-byte aligned (uint8 frames 4-byte aligned)");
-    if (N == 0) return CGIC_OK;
+    const EntropyPlan p = entropy_plan(th, tw, N * T, kEntTilesPpw, sigma, true);
+    if (p.nothing) return CGIC_OK;
+    CGIC_ENT_CHECK(entropy_origins_check, T, origins);
     EntWinArgs a;
     memcpy(a.e.bins.v, bins, sizeof(a.e.bins.v));
     a.e.x = nullptr; a.e.H = th; a.e.W = tw; a.e.ppw = kEntTilesPpw; a.e.e8 = e8; a.e.e16 = e16; a.e.x_out = x_out; a.e.flat8 = flat8;
-    a.e.exp2_scale = (float)(-0.5 * 1.4426950408889634 / ((double)sigma * (double)sigma));
+    a.e.exp2_scale = p.exp2_scale;
     a.w.src = src; a.w.srcH = (int)H; a.w.srcW = (int)W; a.w.T = T;
-    for (int k = 0; k < kEntMaxTiles; ++k) {
+    for (int k = 0; k < kEntMaxTiles; ++k) {          // (unused entries repeat the last tile)
         const int kk = k < T ? k : T - 1;
         a.w.org[k][0] = origins[2 * kk]; a.w.org[k][1] = origins[2 * kk + 1];
-        CGIC_REQUIRE(abs(a.w.org[k][0]) < (1 << 29) && abs(a.w.org[k][1]) < (1 << 29), CGIC_ERR_INVALID, "entropy_maps_tiles: tile origin out of range");
     }
-    const int64_t per_wg = (int64_t)kEntWaves * a.e.ppw;
-    const dim3 grid((unsigned)((tw / 16 + per_wg - 1) / per_wg), (unsigned)(th / 16), (unsigned)(N * T));
     hipStream_t s = (hipStream_t)stream;
-    if (is_u8)
-        return launch_or_record(KID_ENTROPY_WIN_U8, grid, dim3(kEntThreads), 0, a, s, [=] {
-            hipLaunchKernelGGL(entropy_tiles_kernel<true>, grid, dim3(kEntThreads), 0, s, a);
-            return launch_check("entropy_tiles_kernel"); });
-    return launch_or_record(KID_ENTROPY_WIN_F32, grid, dim3(kEntThreads), 0, a, s, [=] {
-        hipLaunchKernelGGL(entropy_tiles_kernel<false>, grid, dim3(kEntThreads), 0, s, a);
-        return launch_check("entropy_tiles_kernel"); });
+    return is_u8 ? entropy_issue(KID_ENTROPY_WIN_U8, entropy_tiles_kernel<true>, "entropy_tiles_kernel", p, a, s)
+                 : entropy_issue(KID_ENTROPY_WIN_F32, entropy_tiles_kernel<false>, "entropy_tiles_kernel", p, a, s);
 }
 
 extern "C" int cgic_entropy_maps_f32(const float *x, int64_t B, int64_t H, int64_t W, const float *bins,
@@ -614,20 +593,13 @@ extern "C" int cgic_entropy_maps_ref_f32(const float *x, int64_t B, int64_t H, i
 {
     CGIC_NOT_IN_GROUP("cgic_entropy_maps_ref_f32");
     CGIC_REQUIRE(x && bins, CGIC_ERR_INVALID, "entropy: x and bins must not be NULL");
-    CGIC_REQUIRE(nbins == kBins, CGIC_ERR_UNSUPPORTED, "entropy: nbins=%d; the reference uses 32 (model.py:480)", nbins);
-    CGIC_REQUIRE(B >= 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, CGIC_ERR_INVALID,
-                 "entropy: H=%lld W=%lld must be positive multiples of 16", (long long)H, (long long)W);
-    CGIC_REQUIRE(B <= 65535 && H / 16 <= 65535, CGIC_ERR_UNSUPPORTED, "entropy: batch/height exceed the grid limits");
-    CGIC_REQUIRE(sigma > 0.f && sigma <= 0.0105f, CGIC_ERR_UNSUPPORTED,
-                 "entropy: sigma=%g; the five-bin window assumes the reference's sigma=0.01 (model.py:481)", sigma);
-    for (int i = 1; i < kBins; ++i)
-        CGIC_REQUIRE(fabsf((bins[i] - bins[i - 1]) - 2.0f / 31.0f) < 1e-5f, CGIC_ERR_UNSUPPORTED,
-                     "entropy: bins are not linspace(-1, 1, 32)");
+    CGIC_ENT_CHECK(entropy_nbins_check, nbins);
+    CGIC_ENT_CHECK(entropy_shape_check, B, H, W);
+    CGIC_ENT_CHECK(entropy_setup_check, sigma, bins, "five-bin");
     if (B == 0 || (!e8 && !e16)) return CGIC_OK;
     BinsArg ba;
     memcpy(ba.v, bins, sizeof(ba.v));
-    dim3 grid((unsigned)(W / 16), (unsigned)(H / 16), (unsigned)B);
+    dim3 grid((unsigned)(W / 16), (unsigned)(H / 16), (unsigned)B);           // a workgroup per 16x16 block
     hipLaunchKernelGGL(entropy_ref_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, H, W, sigma, e8, e16, ba);
     return launch_check("entropy_ref_kernel");
 }
-

@@ -14,12 +14,12 @@
 // arguments, which is what is left against the real class: 98.6-100 % of the values bit-identical, the rest <= 5e-7).
 #pragma once
 #include "cgic_common.h"
+#include "cgic_entropy_plan.h"      // kBins and the host side's checks and launch geometry
 
 #include <math.h>
 
 namespace cgic {
 
-constexpr int kBins = 32;
 constexpr int kRefWin = 5;         // bins that can be non-zero for one pixel in fp32 (exp underflows beyond 14.42 sigma)
 constexpr int kRefRow = kBins + 1; // LDS row stride of a chunk-sum row (+1: bank padding)
 

@@ -463,6 +463,79 @@ def test_vq_forward_route_issues_the_launch_its_plan_names(B, H, W):
         assert all(torch.equal(p, q) for p, q in zip(out[3], mask))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,h,w,hist", [
+    (2, 16, 16, True),          # the small instantiation, with the histogram job
+    (1, 64, 128, False),        # combined jobs, the 8192-position instantiation
+    (1, 64, 132, False),        # the smallest split: the fine stream in 3 parts, tickets, the parts-fastest grid
+    (683, 64, 132, False),      # beyond one ticket request: unsplit, the fine stream staged in 16960 bytes of dynamic LDS
+    (1, 588, 588, False),       # a part of 49392 positions exceeds the 96 KB stage: the parts are reset, round by round through the workspace
+])
+def test_compress_issues_the_launch_its_plan_names(orc, B, h, w, hist):
+    """the smallest latent shape of every branch of compress_plan (cgic_coder_plan.h), seen through the recorder of a one-group launch
+    group: ONE launch per call, and slots and sizes equal to the ungrouped call and to the CPU oracle's bytes"""
+    from control_gic_amd import _lib
+    cg, dev, rng, vq, _ = _setup(B + h + w)
+    freq = np.floor(1e6 / (1 + np.arange(1024)) ** 1.1).astype(np.int64)
+    vq.usage_counter.copy_(torch.from_numpy(freq.astype(np.float32)))
+    codec = cg.GrainCodec(vq.embedding_counter, vq.embedding.weight.detach())
+    htab = orc.HuffmanTable(freq)
+    e16 = (rng.random((B, h // 4, w // 4)) * 2.6).astype(np.float32)
+    e8 = (rng.random((B, h // 2, w // 2)) * 2.6).astype(np.float32)
+    ind = rng.integers(0, 1024, (B, h, w))
+    mks = orc.router(e16, e8, 0.1, 0.8, per_image=True, want_gate=False)
+    mode = mks[4]
+    mask = [torch.from_numpy(m).to(dev) for m in mks[:3]]
+    ind_d = torch.from_numpy(ind).to(dev)
+    hists = [torch.zeros(1024, dtype=torch.int64, device=dev) if hist else None for _ in range(2)]
+    ref = codec.compress(ind_d, mask, mode, hist=hists[0])
+    grp = _lib.launch_group(1, None, dev)
+    with grp as g:
+        g.select(0)
+        got = codec.compress(ind_d, mask, mode, hist=hists[1])
+    assert grp.launches == 1
+    torch.cuda.synchronize()
+    assert torch.equal(ref.nbytes, got.nbytes) and int(ref.nbytes.min()) >= 0
+    host_ref, host_got = ref.to_host(), got.to_host()
+    assert host_ref == host_got
+    for b in sorted({0, B // 2, B - 1}):
+        assert host_got[b] == orc.compress_image(ind[b], mks[0][b, 0], mks[1][b, 0], mks[2][b, 0], mode, htab), f"image {b}"
+    if hist:
+        want = torch.from_numpy(np.bincount(ind.ravel(), minlength=1024)).to(dev)
+        assert torch.equal(hists[0], want) and torch.equal(hists[1], want)
+
+
+@pytest.mark.gpu
+def test_entropy_maps_issue_the_launch_their_plan_names():
+    """a 272-wide image (two workgroups per row band: entropy_plan in cgic_entropy_plan.h) through cgic_entropy_maps_f32 and, as one
+    tile of its own size, through cgic_entropy_maps_tiles, each seen through the recorder of a one-group launch group: ONE launch per
+    call, and maps, flat8 and tiles bit-equal to the ungrouped calls"""
+    import control_gic_amd as cg
+    from control_gic_amd import _lib
+    from control_gic_amd.entropy import entropy_maps_tiles
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(272)
+    x = torch.from_numpy(rng.random((2, 3, 48, 272), dtype=np.float32)).to(dev)
+    x[:, :, :16, :136] = 0.25                                                # constant patches: flat8 has numbers, not only NaN
+    same = lambda a, b: torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0))
+    ref = cg.entropy_maps(x)
+    ref_t = entropy_maps_tiles(x, [(0, 0)], 48, 272)
+    grp = _lib.launch_group(1, None, dev)
+    with grp as g:
+        g.select(0)
+        got = cg.entropy_maps(x)
+    assert grp.launches == 1
+    grp = _lib.launch_group(1, None, dev)
+    with grp as g:
+        g.select(0)
+        got_t = entropy_maps_tiles(x, [(0, 0)], 48, 272)
+    assert grp.launches == 1
+    torch.cuda.synchronize()
+    assert torch.equal(ref_t[0], x) and torch.equal(got_t[0], x)
+    for e8, e16 in (got, ref_t[1:], got_t[1:]):
+        assert torch.equal(e8, ref[0]) and torch.equal(e16, ref[1]) and same(e8._cgic_flat8, ref[0]._cgic_flat8)
+
+
 def test_tile_entry_points_check_their_arguments():
     """argument checks of cgic_cut_tiles / cgic_entropy_maps_tiles come before any launch (host logic only)"""
     import ctypes
