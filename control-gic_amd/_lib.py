@@ -452,10 +452,19 @@ def require_device(*tensors):
                 "There is deliberately no CPU fallback -- the CPU oracle lives in oracle/ and is test-only.")
 
 
-def require_int32_masks(*masks):
+def require_int32_masks(*masks, msg="masks must be int32 like the router's (RouterTriple.py:92)"):
     """The kernels read a mask's words as int32: a float mask (the reference's own `mask.float()`) would have its bit
     pattern taken for an integer (1.0f = 1065353216) and scale the latent by it silently."""
     import torch
     for m in masks:
         if m.dtype != torch.int32:
-            raise TypeError("masks must be int32 like the router's (RouterTriple.py:92)")
+            raise TypeError(msg)
+
+
+def grain_masks(B, h, w, device=None, alloc=None):
+    """the three int32 mask tensors of B images on the fine grid h x w, in the router's layouts (RouterTriple.py:92):
+    [B,1,h/4,w/4], [B,1,h/2,w/2], [B,1,h,w].  alloc(shape, dtype): the caller's allocator instead of torch.empty on `device`"""
+    import torch
+    if alloc is None:
+        alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+    return [alloc((B, 1, h // 4, w // 4), torch.int32), alloc((B, 1, h // 2, w // 2), torch.int32), alloc((B, 1, h, w), torch.int32)]

@@ -23,14 +23,15 @@ def mode_streams(mode):
     return tuple(bool(m >> i & 1) for i in range(_lib.NUM_STREAMS))
 
 
-_DECODE_MODES = {"auto": 0, "latency": 1, "throughput": 2}
+#: the names of the prefix decoders and the `decoder` argument of cgic_decompress_streams each stands for
+DECODERS = {"auto": 0, "latency": 1, "throughput": 2}
 _tls = threading.local()
 
 
 def set_default_decoder(mode):
     """process-wide default of calls that name no decoder (cgic_set_decode_mode); returns the previous one"""
-    prev = _lib.call("cgic_set_decode_mode", _DECODE_MODES[mode])
-    return {v: k for k, v in _DECODE_MODES.items()}[prev]
+    prev = _lib.call("cgic_set_decode_mode", DECODERS[mode])
+    return {v: k for k, v in DECODERS.items()}[prev]
 
 
 class decoder_mode:
@@ -42,8 +43,8 @@ class decoder_mode:
     the calling THREAD's default, so two threads can decode in different modes at the same time."""
 
     def __init__(self, mode):
-        if mode not in _DECODE_MODES:
-            raise ValueError(f"decoder mode {mode!r}: expected one of {sorted(_DECODE_MODES)}")
+        if mode not in DECODERS:
+            raise ValueError(f"decoder mode {mode!r}: expected one of {sorted(DECODERS)}")
         self.mode = mode
         self.prev = None
 
@@ -61,9 +62,9 @@ def _decoder_flag(decoder):
     mode = decoder if decoder is not None else getattr(_tls, "mode", None)
     if mode is None:
         return 0
-    if mode not in _DECODE_MODES:
-        raise ValueError(f"decoder mode {mode!r}: expected one of {sorted(_DECODE_MODES)}")
-    return _DECODE_MODES[mode]
+    if mode not in DECODERS:
+        raise ValueError(f"decoder mode {mode!r}: expected one of {sorted(DECODERS)}")
+    return DECODERS[mode]
 
 
 class CompressedBatch:
@@ -146,6 +147,63 @@ class CompressedBatch:
         return cls.from_host([im], mode, h, w, slot, device)
 
 
+def slot_bytes(table, h, w):
+    """bytes of one stream slot of an h x w latent under the code table `table` (a cgic_table* handle)"""
+    return int(_lib.lib().cgic_compress_slot_bytes(table, int(h), int(w)))
+
+
+def compress_streams(table, ind, masks, mode, hist=None):
+    """cgic_compress_streams under the code table `table` (a cgic_table* handle): ind [B,h,w] (or flat [B*h*w]) int64;
+    masks = [mask_c, mask_m, mask_f] int32 -> CompressedBatch.  hist (int64 [n_e], optional) accumulates the usage histogram of
+    `ind` in the same launch.  GrainCodec.compress and torch.ops.cgic.compress_streams are this call."""
+    mc, mm, mf = (m.contiguous() for m in masks)
+    _lib.require_device(ind, mc, mm, mf)
+    B, h, w = mf.shape[0], mf.shape[-2], mf.shape[-1]
+    ind = ind.contiguous()
+    if ind.numel() != B * h * w or ind.dtype != torch.int64:
+        raise ValueError("ind must be int64 with B*h*w elements")
+    _lib.require_int32_masks(mc, mm, mf)
+    dev = ind.device
+    slot = slot_bytes(table, h, w)
+    data = torch.empty((B, _lib.NUM_STREAMS, slot), dtype=torch.uint8, device=dev)
+    nbytes = torch.empty((B, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
+    wsb = _lib.lib().cgic_compress_workspace_bytes(B, h, w)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    with _lib.on_device(dev):
+        _lib.call("cgic_compress_streams", table, _lib.ptr(ind), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), B, h, w, int(mode),
+                  _lib.ptr(data), slot, _lib.ptr(nbytes), _lib.ptr(hist), _lib.ptr(ws), _lib.current_stream(dev))
+    return CompressedBatch(data, nbytes, mode, h, w)
+
+
+def decompress_streams(table, comp, codebook, want_masks=True, want_zq=True, post_table=None, decoder=None, status=None):
+    """cgic_decompress_streams under the code table `table` (a cgic_table* handle): CompressedBatch -> (ind [B,h,w] int64,
+    [mask_c, mask_m, mask_f] int32 [B,1,.,.] or None, z_q [B,4,h,w] fp32 or None, status [B] int32 on the device (0 = ok)).
+    codebook: [K,4] for the gather of z_q; post_table: a second gather table (GrainCodec.post_conv_table) -> the third element is
+    the pair (z_q, the gather from post_table).  decoder, status: see GrainCodec.decompress, which is this call, as
+    torch.ops.cgic.decompress_streams is."""
+    B, h, w, dev = comp.batch, comp.h, comp.w, comp.data.device
+    ind = torch.empty((B, h, w), dtype=torch.int64, device=dev)
+    mc, mm, mf = masks = _lib.grain_masks(B, h, w, dev) if want_masks else (None, None, None)
+    zq = cbk = zq2 = None
+    if want_zq:
+        cbk = codebook.detach().contiguous()
+        zq = torch.empty((B, cbk.shape[1], h, w), dtype=torch.float32, device=dev)
+        if post_table is not None:
+            zq2 = torch.empty_like(zq)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous() or status.device != dev:
+        raise ValueError("status must be a contiguous int32 tensor with one element per image on the streams' device")
+    ws = torch.empty(_lib.lib().cgic_decompress_workspace_bytes(B, h, w), dtype=torch.uint8, device=dev)
+    flag = _decoder_flag(decoder)
+    with _lib.on_device(dev):
+        _lib.call("cgic_decompress_streams", table, _lib.ptr(comp.data), comp.data.shape[2], _lib.ptr(comp.nbytes), B, h, w, comp.mode,
+                  _lib.ptr(ind), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), _lib.ptr(cbk),
+                  cbk.shape[0] if cbk is not None else 0, cbk.shape[1] if cbk is not None else 0,
+                  _lib.ptr(zq), _lib.ptr(post_table), _lib.ptr(zq2), _lib.ptr(status), _lib.ptr(ws), flag, _lib.current_stream(dev))
+    return ind, masks if want_masks else None, (zq, zq2) if post_table is not None else zq, status
+
+
 class GrainCodec:
     """encode/decode the three index streams + two mask streams of a batch.
 
@@ -157,32 +215,12 @@ class GrainCodec:
         self.codebook = codebook
 
     def slot_bytes(self, h, w):
-        return int(_lib.lib().cgic_compress_slot_bytes(self.huffman.table.handle, h, w))
+        return slot_bytes(self.huffman.table.handle, h, w)
 
     def compress(self, ind, masks, mode, hist=None):
         """ind [B,h,w] (or flat [B*h*w]) int64; masks = [mask_c, mask_m, mask_f] int32 -> CompressedBatch.
         hist (int64 [n_e], optional) accumulates the usage histogram of `ind` in the same launch."""
-        mc, mm, mf = (m.contiguous() for m in masks)
-        _lib.require_device(ind, mc, mm, mf)
-        B, h, w = mf.shape[0], mf.shape[-2], mf.shape[-1]
-        ind = ind.contiguous()
-        if ind.numel() != B * h * w or ind.dtype != torch.int64:
-            raise ValueError("ind must be int64 with B*h*w elements")
-        for m in (mc, mm, mf):
-            if m.dtype != torch.int32:
-                raise TypeError("masks must be int32 like the router's (RouterTriple.py:92)")
-        l = _lib.lib()
-        dev = ind.device
-        slot = self.slot_bytes(h, w)
-        data = torch.empty((B, _lib.NUM_STREAMS, slot), dtype=torch.uint8, device=dev)
-        nbytes = torch.empty((B, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
-        wsb = l.cgic_compress_workspace_bytes(B, h, w)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        with _lib.on_device(dev):
-            _lib.call("cgic_compress_streams", self.huffman.table.handle, _lib.ptr(ind), _lib.ptr(mc), _lib.ptr(mm),
-                      _lib.ptr(mf), B, h, w, int(mode), _lib.ptr(data), slot, _lib.ptr(nbytes), _lib.ptr(hist),
-                      _lib.ptr(ws), _lib.current_stream(dev))
-        return CompressedBatch(data, nbytes, mode, h, w)
+        return compress_streams(self.huffman.table.handle, ind, masks, mode, hist)
 
     def rate_table(self, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, pixels=None):
         """control_gic_amd.rate.rate_table with this codec's code table: exact stream sizes per candidate ratio -> RateTable"""
@@ -206,38 +244,11 @@ class GrainCodec:
         (z_q, post_quant_conv(z_q)) -- what CGIC.decode feeds the decoder (model.py:114-116) -- from the same pass.
         decoder: "latency" / "throughput" / "auto" for THIS call (None: the enclosing decoder_mode block, else the process default).
         status: where to write the [B] status words (e.g. a slice of one buffer shared by several calls) instead of a new tensor."""
-        B, h, w, dev = cb.batch, cb.h, cb.w, cb.data.device
-        l = _lib.lib()
-        ind = torch.empty((B, h, w), dtype=torch.int64, device=dev)
-        masks = None
-        if want_masks:
-            masks = [torch.empty((B, 1, h // 4, w // 4), dtype=torch.int32, device=dev),
-                     torch.empty((B, 1, h // 2, w // 2), dtype=torch.int32, device=dev),
-                     torch.empty((B, 1, h, w), dtype=torch.int32, device=dev)]
-        zq = None
-        cbk = None
-        if want_zq:
-            if self.codebook is None:
-                raise ValueError("GrainCodec was built without a codebook")
-            cbk = self.codebook.detach().contiguous()
-            zq = torch.empty((B, cbk.shape[1], h, w), dtype=torch.float32, device=dev)
-        cbk2 = zq2 = None
+        if want_zq and self.codebook is None:
+            raise ValueError("GrainCodec was built without a codebook")
+        post = None
         if post_quant_conv is not None:
             if not want_zq:
                 raise ValueError("post_quant_conv needs want_zq")
-            cbk2 = self.post_conv_table(post_quant_conv, conv_bias_first)
-            zq2 = torch.empty_like(zq)
-        if status is None:
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-        elif status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous() or status.device != dev:
-            raise ValueError("status must be a contiguous int32 tensor with one element per image on the streams' device")
-        ws = torch.empty(l.cgic_decompress_workspace_bytes(B, h, w), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            _lib.call("cgic_decompress_streams", self.huffman.table.handle, _lib.ptr(cb.data), cb.data.shape[2],
-                      _lib.ptr(cb.nbytes), B, h, w, cb.mode, _lib.ptr(ind),
-                      _lib.ptr(masks[0]) if masks else None, _lib.ptr(masks[1]) if masks else None,
-                      _lib.ptr(masks[2]) if masks else None, _lib.ptr(cbk),
-                      cbk.shape[0] if cbk is not None else 0, cbk.shape[1] if cbk is not None else 0,
-                      _lib.ptr(zq), _lib.ptr(cbk2), _lib.ptr(zq2), _lib.ptr(status), _lib.ptr(ws), _decoder_flag(decoder),
-                      _lib.current_stream(dev))
-        return ind, masks, (zq, zq2) if post_quant_conv is not None else zq, status
+            post = self.post_conv_table(post_quant_conv, conv_bias_first)
+        return decompress_streams(self.huffman.table.handle, cb, self.codebook, want_masks, want_zq, post, decoder, status)

@@ -74,7 +74,6 @@ def entropy_maps_tiles(src, origins, th, tw, sigma=0.01):
     shape th x tw in unpadded coordinates -> (tiles [N*T,3,th,tw] fp32 image-major, e8, e16).  The tile batch comes back tagged with its
     maps (weakly: keep e8 / e16 alive for as long as they are wanted): entropy_maps(tiles) returns them without another pass, and the
     router finds pixels + flat8 on the maps as usual.  The tag is void once the batch has been modified in place."""
-    import ctypes
     _lib.require_device(src)
     u8 = src.dtype == torch.uint8
     if src.dim() != 4 or (src.shape[3] if u8 else src.shape[1]) != 3 or (not u8 and src.dtype != torch.float32):

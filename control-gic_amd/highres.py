@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .codec import GrainCodec
+from .pipeline import image_io_buffers
 
 TILE = 768
 
@@ -578,44 +579,27 @@ class TiledCall:
         l = _lib.lib()
         if len(self.groups) > l.cgic_group_max():
             raise ValueError(f"{len(self.groups)} tile shapes; cgic_compress_tiled takes at most {l.cgic_group_max()}")
-        f32, i32, i64, u8t = torch.float32, torch.int32, torch.int64, torch.uint8
         E = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         total = sum(len(ix) * th * tw for (th, tw), ix in self.groups)
         self._arr = (_lib.TileGroup * len(self.groups))()
         self._buf, self._keep = [], []
-        p = _lib.ptr
         for k, ((th, tw), idxs) in enumerate(self.groups):
             T, B, h, ww = len(idxs), N * len(idxs), th // 4, tw // 4
             slot = self.codec.slot_bytes(h, ww)
-            t = {"x": E((B, 3, th, tw), f32), "e8": E((B, th // 8, tw // 8), f32), "e16": E((B, th // 16, tw // 16), f32),
-                 "flat8": E((B, th // 8, tw // 8), f32), "ind": E((B * h * ww,), i64),
-                 "mask": [E((B, 1, h // 4, ww // 4), i32), E((B, 1, h // 2, ww // 2), i32), E((B, 1, h, ww), i32)],
-                 "data": E((B, _lib.NUM_STREAMS, slot), u8t), "nbytes": E((B, _lib.NUM_STREAMS), i32), "slot": slot, "h": h, "w": ww}
-            if decode:
-                t.update({"dind": E((B, h, ww), i64), "dz_q": E((B, 4, h, ww), f32), "status": E((B,), i32),
-                          "dmask": [E((B, 1, h // 4, ww // 4), i32), E((B, 1, h // 2, ww // 2), i32), E((B, 1, h, ww), i32)]})
-            ws_c = E((max(1, l.cgic_compress_workspace_bytes(B, h, ww)),), u8t)
-            ws_d = E((l.cgic_decompress_workspace_bytes(B, h, ww),), u8t) if decode else None
             if not l.cgic_router_refine_in_lds(B, th // 16, tw // 16, 1):
                 raise ValueError(f"TiledCall: tiles of {th}x{tw} are routed as one segment beyond the router workgroup's LDS; their refinement is a chain "
                                  "of launches that a launch group cannot record (cgic_router_refine_in_lds): use tiles of at most 768x768 "
                                  "(the reference's), or compress_tiled(..., chain=False)")
             nref = l.cgic_router_refine_scratch_bytes(B, th // 16, tw // 16, 1) if ((th // 16) * (tw // 16) >= _lib.REFINE_SPLIT_MIN_PATCHES or _lib.REFINE_FUSED_QUEUES) and _lib.REFINE_QUEUES else 0
-            ws_r = E((nref,), u8t) if nref else None                 # (large tiles: their row bands split a threshold band between them)
+            ws_r = E((nref,), torch.uint8) if nref else None         # (large tiles: their row bands split a threshold band between them)
+            # the tile batch is the entropy pass's x_out; z_q, the loss and the histogram are not this call's
+            t, io = image_io_buffers(slot, B, th, tw, decode, True, False, False, None, E, ws_refine=ws_r)
+            t.update(slot=slot, h=h, w=ww)
             org = (ctypes.c_int * (2 * T))(*[v for i in idxs for v in (self.tiles[i][0] - top, self.tiles[i][1] - left)])
             g = self._arr[k]
-            g.ntiles, g.th, g.tw, g.origins, g.share = T, th, tw, org, len(idxs) * th * tw / total
-            io = g.io
-            io.x_out, io.e8, io.e16, io.flat8, io.ind = p(t["x"]), p(t["e8"]), p(t["e16"]), p(t["flat8"]), p(t["ind"])
-            io.mask_c, io.mask_m, io.mask_f = (p(m) for m in t["mask"])
-            io.streams, io.slot, io.nbytes = p(t["data"]), slot, p(t["nbytes"])
-            if decode:
-                io.dind, io.dz_q, io.status = p(t["dind"]), p(t["dz_q"]), p(t["status"])
-                io.dmask_c, io.dmask_m, io.dmask_f = (p(m) for m in t["dmask"])
-            io.ws_compress, io.ws_decompress = p(ws_c), p(ws_d)
-            io.ws_refine, io.ws_refine_bytes = p(ws_r), nref
+            g.ntiles, g.th, g.tw, g.origins, g.share, g.io = T, th, tw, org, len(idxs) * th * tw / total, io
             self._buf.append(t)
-            self._keep += [org, ws_c, ws_d, ws_r]
+            self._keep.append(org)
         self._mode = ctypes.c_int(0)
         self._fn = l.cgic_compress_tiled
         self._bins = _lib.linspace_bins()

@@ -81,6 +81,40 @@ def _frequency_items(frequency):
     return keys, freq
 
 
+def stream_capacity(table, n):
+    """bytes a stream of n symbols can take under the code table `table` (a cgic_table* handle)"""
+    return int(_lib.lib().cgic_stream_capacity(table, int(n)))
+
+
+def encode_stream(table, info):
+    """cgic_encode_stream: info = 1-D contiguous int64 / int32 symbols on the device, at least one -> (bytes uint8 [capacity],
+    nbytes int32 [1]: the stream's length, or a negative error code), both on the device"""
+    n, dev = info.numel(), info.device
+    cap = stream_capacity(table, n)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    nbytes = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = _lib.lib().cgic_stream_workspace_bytes(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    with _lib.on_device(dev):
+        _lib.call("cgic_encode_stream", table, _lib.ptr(info), info.element_size(), n, _lib.ptr(out), cap, _lib.ptr(nbytes),
+                  _lib.ptr(ws), _lib.current_stream(dev))
+    return out, nbytes
+
+
+def decode_stream(table, buf, nbytes):
+    """cgic_decode_stream: buf = contiguous uint8 on the device with at least nbytes + 16 readable bytes -> (symbols int64
+    [(nbytes - 1) * 8] of which the first `count` are valid, count int64 [1]: -1 = the empty file's None, below that an error
+    code), both on the device"""
+    dev = buf.device
+    cap = max(1, (int(nbytes) - 1) * 8)
+    syms = torch.empty(cap, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("cgic_decode_stream", table, _lib.ptr(buf), int(nbytes), _lib.ptr(syms), cap, _lib.ptr(count),
+                  _lib.current_stream(dev))
+    return syms, count
+
+
 class _StreamCoder:
     """device-side single-stream encode/decode shared by HuffmanCoding and BinaryCoding"""
 
@@ -93,19 +127,9 @@ class _StreamCoder:
         if info.dtype not in (torch.int64, torch.int32):
             info = info.to(torch.int64)
         info = info.contiguous()
-        n = info.numel()
-        if n == 0:
+        if info.numel() == 0:
             return b""                                     # empty file (indices_coding.py:116-118)
-        l = _lib.lib()
-        cap = l.cgic_stream_capacity(self._table.handle, n)
-        dev = info.device
-        out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        nbytes = torch.empty(1, dtype=torch.int32, device=dev)
-        wsb = l.cgic_stream_workspace_bytes(n)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        with torch.cuda.device(dev):
-            _lib.call("cgic_encode_stream", self._table.handle, _lib.ptr(info), info.element_size(), n,
-                      _lib.ptr(out), cap, _lib.ptr(nbytes), _lib.ptr(ws), _lib.current_stream(dev))
+        out, nbytes = encode_stream(self._table.handle, info)
         nb = int(nbytes.item())
         if nb < 0:
             if nb == _lib.ERR_INVALID:
@@ -119,13 +143,7 @@ class _StreamCoder:
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         buf = torch.zeros(len(data) + 16, dtype=torch.uint8)
         buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8)
-        buf = buf.to(device)
-        cap = max(1, (len(data) - 1) * 8)
-        syms = torch.empty(cap, dtype=torch.int64, device=device)
-        count = torch.empty(1, dtype=torch.int64, device=device)
-        with torch.cuda.device(device):
-            _lib.call("cgic_decode_stream", self._table.handle, _lib.ptr(buf), len(data), _lib.ptr(syms), cap,
-                      _lib.ptr(count), _lib.current_stream(device))
+        syms, count = decode_stream(self._table.handle, buf.to(device), len(data))
         c = int(count.item())
         if c == -1:
             return None

@@ -10,13 +10,14 @@ import types
 
 import torch
 
-from . import _lib
 from . import draw as _draw
+from . import merge as _merge
 from . import rate as _rate
 from .codec import GrainCodec
 from .entropy import Entropy
 from .indices_coding import HuffmanCoding
 from .quantize import FusedQuantConv, VectorQuantize2
+from .router import routing_per_image
 
 ROUTER_TARGET = "control_gic_amd.router.TripleGrainFixedEntropyRouter"
 
@@ -39,17 +40,8 @@ def decoder_blend_medium(h, h_medium, mask, out=None):
     (torch.ops.cgic.decoder_blend_medium); with `out` (which may be `h`: in place) the raw kernel call, no autograd."""
     if out is None:
         return torch.ops.cgic.decoder_blend_medium(h, h_medium, mask[0], mask[1])
-    _lib.require_device(h, h_medium, mask[0], mask[1])
-    h, hm = h.contiguous().float(), h_medium.contiguous().float()
-    mc, mm = mask[0].contiguous(), mask[1].contiguous()
-    _lib.require_int32_masks(mc, mm)
-    B, C, hh, ww = h.shape
-    if tuple(hm.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 2) * (ww // 2) or mm.numel() != B * hh * ww:
-        raise ValueError("decoder_blend_medium: h, h_medium on the medium grid; mask[0] at half of it, mask[1] on it")
-    with torch.cuda.device(h.device):
-        _lib.call("cgic_decoder_blend_medium_f32", _lib.ptr(h), _lib.ptr(hm), _lib.ptr(mc), _lib.ptr(mm), B, C, hh, ww,
-                  _lib.ptr(out), _lib.current_stream(h.device))
-    return out
+    return _merge.decoder_blend_medium(h, h_medium, mask[0], mask[1],
+                                       "decoder_blend_medium: h, h_medium on the medium grid; mask[0] at half of it, mask[1] on it", out=out)
 
 
 def decoder_blend_fine(h, h_fine, mask, out=None):
@@ -57,18 +49,7 @@ def decoder_blend_fine(h, h_fine, mask, out=None):
     (torch.ops.cgic.decoder_blend_fine); with `out` the raw kernel call (in place if `out is h`), no autograd."""
     if out is None:
         return torch.ops.cgic.decoder_blend_fine(h, h_fine, mask[0], mask[1], mask[2])
-    _lib.require_device(h, h_fine, *mask)
-    h, hf = h.contiguous().float(), h_fine.contiguous().float()
-    mc, mm, mf = (m.contiguous() for m in mask)
-    _lib.require_int32_masks(mc, mm, mf)
-    B, C, hh, ww = h.shape
-    if tuple(hf.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 4) * (ww // 4) or mm.numel() != B * (hh // 2) * (ww // 2) \
-            or mf.numel() != B * hh * ww:
-        raise ValueError("decoder_blend_fine: h, h_fine on the fine grid; masks at 1/4, 1/2, 1/1 of it")
-    with torch.cuda.device(h.device):
-        _lib.call("cgic_decoder_blend_fine_f32", _lib.ptr(h), _lib.ptr(hf), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), B, C, hh, ww,
-                  _lib.ptr(out), _lib.current_stream(h.device))
-    return out
+    return _merge.decoder_blend_fine(h, h_fine, *mask, out=out)
 
 
 def _codec_for(model, h_indices=None):
@@ -109,17 +90,8 @@ def compress_batch(model, input, h_indices=None, decode=True, save_img=False):
     # for encode()/forward() are (the reference flattens the batch, RouterTriple.py:21-31)
     rc = getattr(model.encoder, "router_config", None)
     params = rc.get("params") if isinstance(rc, dict) or hasattr(rc, "get") else None
-    saved = params.get("per_image", None) if params is not None else None
-    if params is not None:
-        params["per_image"] = True
-    try:
+    with routing_per_image(params):
         quant, diff, grain_indices, grain_mask, ind, _, mode = model.encode(input)
-    finally:
-        if params is not None:
-            if saved is None:
-                params.pop("per_image", None)
-            else:
-                params["per_image"] = saved
     comp = codec.compress(ind, grain_mask, mode)
     bpp = comp.bpp(input.shape[2] * input.shape[3])                      # model.py:223,233
     dec = _decode(model, codec, comp) if decode else None

@@ -1,6 +1,6 @@
 """`torch.ops.cgic.*` -- the hot-path kernels as PyTorch custom ops (torch.library), so that they carry a schema, shape
-inference under FakeTensor / torch.compile, and (for the quantiser) an autograd formula.  The implementations are the same
-ctypes calls into libcgic_hip.so the module classes use; CPU tensors raise (there is no CPU fallback).
+inference under FakeTensor / torch.compile, and (for the quantiser) an autograd formula.  The implementations are one-line calls of the
+functions the module classes use (each entry point of libcgic_hip.so is bound once, in the module that owns it: DESIGN.md); CPU tensors raise (there is no CPU fallback).
 
     z_q, loss, idx = torch.ops.cgic.vq_forward(z, codebook, 0.25, True)
     e8, e16        = torch.ops.cgic.entropy_maps(x)
@@ -24,7 +24,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, codec as _codec, indices_coding as _coding, merge as _merge, quantize as _quantize
 from .entropy import entropy_maps as _entropy_maps, entropy_maps_u8 as _entropy_maps_u8
 from .quantize import _vq_forward, vq_backward as _vq_backward, vq_forward_route as _vq_forward_route
 from .router import TripleGrainFixedEntropyRouter
@@ -210,41 +210,19 @@ def _table(handle: int):
     return ctypes.c_void_p(int(handle))
 
 
-def _slot_bytes(table: int, h: int, w: int) -> int:
-    return int(_lib.lib().cgic_compress_slot_bytes(_table(table), int(h), int(w)))
-
-
 @torch.library.custom_op("cgic::compress_streams", mutates_args=("hist",), device_types=_DEV)
 def compress_streams(ind: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor, mask_f: torch.Tensor, mode: int, table: int,
                      hist: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """masked select + Huffman + mask packing of a batch (model.py:217-260): (data uint8 [B,5,slot], nbytes int32 [B,5];
     -1 = stream not written in this mode); `hist` (int64 [n_e]) accumulates the usage histogram of `ind` in the same launch"""
-    mc, mm, mf = (m.contiguous() for m in (mask_c, mask_m, mask_f))
-    _lib.require_device(ind, mc, mm, mf)
-    B, h, w = mf.shape[0], mf.shape[-2], mf.shape[-1]
-    ind = ind.contiguous()
-    if ind.numel() != B * h * w or ind.dtype != torch.int64:
-        raise ValueError("ind must be int64 with B*h*w elements")
-    for m in (mc, mm, mf):
-        if m.dtype != torch.int32:
-            raise TypeError("masks must be int32 like the router's (RouterTriple.py:92)")
-    l = _lib.lib()
-    dev = ind.device
-    slot = _slot_bytes(table, h, w)
-    data = torch.empty((B, _lib.NUM_STREAMS, slot), dtype=torch.uint8, device=dev)
-    nbytes = torch.empty((B, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
-    wsb = l.cgic_compress_workspace_bytes(B, h, w)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-    with torch.cuda.device(dev):
-        _lib.call("cgic_compress_streams", _table(table), _lib.ptr(ind), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), B, h, w, int(mode),
-                  _lib.ptr(data), slot, _lib.ptr(nbytes), _lib.ptr(hist), _lib.ptr(ws), _lib.current_stream(dev))
-    return data, nbytes
+    comp = _codec.compress_streams(_table(table), ind, (mask_c, mask_m, mask_f), mode, hist)
+    return comp.data, comp.nbytes
 
 
 @compress_streams.register_fake
 def _(ind, mask_c, mask_m, mask_f, mode, table, hist):
     B, h, w = mask_f.shape[0], mask_f.shape[-2], mask_f.shape[-1]
-    return (ind.new_empty((B, _lib.NUM_STREAMS, _slot_bytes(table, h, w)), dtype=torch.uint8),
+    return (ind.new_empty((B, _lib.NUM_STREAMS, _codec.slot_bytes(_table(table), h, w)), dtype=torch.uint8),
             ind.new_empty((B, _lib.NUM_STREAMS), dtype=torch.int32))
 
 
@@ -275,13 +253,8 @@ def rate_curve(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e1
     """exact .bin sizes of EVERY medium rank K = 0 .. n8 at the coarse ratio `coarse`, per-image routing on the maps as given
     (cgic_rate_curve): int32 [B,n8+1,5], 0 = stream not written in the curve's mode"""
     from .rate import rate_curve as _rate_curve
-
-    class _Codec:            # the op carries the table as its handle
-        class huffman:
-            class table:
-                handle = _table(table)
     # (ranks=(): the op returns the sizes only; which ranks a ratio reaches is host arithmetic the caller may not want)
-    return _rate_curve(_Codec, ind_c, ind_m, ind_f, e16, e8, coarse, ranks=()).nbytes
+    return _rate_curve(_table(table), ind_c, ind_m, ind_f, e16, e8, coarse, ranks=()).nbytes
 
 
 @rate_curve.register_fake
@@ -297,12 +270,7 @@ def route_to_bpp(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, 
     layouts, ind int64 [B,h,w], choice int64 [4] = {j, K, fits, batch bytes}; all -1, fits 0 and zero outputs when a requested
     entry holds a symbol outside the table)"""
     from .rate import route_to_bpp as _route_to_bpp
-
-    class _Codec:            # the op carries the table as its handle
-        class huffman:
-            class table:
-                handle = _table(table)
-    r = _route_to_bpp(_Codec, ind_c, ind_m, ind_f, e16, e8, coarse, budget=budget)
+    r = _route_to_bpp(_table(table), ind_c, ind_m, ind_f, e16, e8, coarse, budget=budget)
     return r.masks[0], r.masks[1], r.masks[2], r.ind, r.choice
 
 
@@ -314,9 +282,6 @@ def _(ind_c, ind_m, ind_f, e16, e8, coarse, budget, table):
             e16.new_empty((4,), dtype=torch.int64))
 
 
-_DECODERS = {"auto": 0, "latency": 1, "throughput": 2}
-
-
 @torch.library.custom_op("cgic::rate_table", mutates_args=(), device_types=_DEV)
 def rate_table(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e16: torch.Tensor, e8: torch.Tensor, coarse: List[float],
                medium: List[float], per_image: bool, table: int, pixels: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -325,12 +290,7 @@ def rate_table(ind_c: torch.Tensor, ind_m: torch.Tensor, ind_f: torch.Tensor, e1
     if len(coarse) != len(medium):
         raise ValueError("rate_table: one medium ratio per coarse ratio")
     from .rate import rate_table as _rate_table
-
-    class _Codec:            # the op carries the table as its handle
-        class huffman:
-            class table:
-                handle = _table(table)
-    return _rate_table(_Codec, ind_c, ind_m, ind_f, e16, e8, list(zip(coarse, medium)), per_image=per_image, pixels=pixels).nbytes
+    return _rate_table(_table(table), ind_c, ind_m, ind_f, e16, e8, list(zip(coarse, medium)), per_image=per_image, pixels=pixels).nbytes
 
 
 @rate_table.register_fake
@@ -345,22 +305,11 @@ def decompress_streams(data: torch.Tensor, nbytes: torch.Tensor, h: int, w: int,
     (ind int64 [B,h,w], mask_c, mask_m, mask_f int32 [B,1,.,.], z_q fp32 [B,4,h,w], status int32 [B]);
     decoder: "auto" / "latency" / "throughput" -- a property of this call"""
     _lib.require_device(data, nbytes, codebook)
-    if decoder not in _DECODERS:
-        raise ValueError(f"decoder {decoder!r}: expected one of {sorted(_DECODERS)}")
-    B, dev = data.shape[0], data.device
-    data, nbytes = data.contiguous(), nbytes.contiguous()
-    cbk = codebook.detach().contiguous()
-    ind = torch.empty((B, h, w), dtype=torch.int64, device=dev)
-    mc = torch.empty((B, 1, h // 4, w // 4), dtype=torch.int32, device=dev)
-    mm = torch.empty((B, 1, h // 2, w // 2), dtype=torch.int32, device=dev)
-    mf = torch.empty((B, 1, h, w), dtype=torch.int32, device=dev)
-    zq = torch.empty((B, cbk.shape[1], h, w), dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = torch.empty(_lib.lib().cgic_decompress_workspace_bytes(B, h, w), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("cgic_decompress_streams", _table(table), _lib.ptr(data), data.shape[2], _lib.ptr(nbytes), B, h, w, int(mode),
-                  _lib.ptr(ind), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), _lib.ptr(cbk), cbk.shape[0], cbk.shape[1], _lib.ptr(zq),
-                  None, None, _lib.ptr(status), _lib.ptr(ws), _DECODERS[decoder], _lib.current_stream(dev))
+    if decoder not in _codec.DECODERS:
+        raise ValueError(f"decoder {decoder!r}: expected one of {sorted(_codec.DECODERS)}")
+    comp = _codec.CompressedBatch(data.contiguous(), nbytes.contiguous(), mode, h, w)
+    # (the decoder is named explicitly, "auto" included: an enclosing decoder_mode block does not reach into an op)
+    ind, (mc, mm, mf), zq, status = _codec.decompress_streams(_table(table), comp, codebook, decoder=decoder)
     return ind, mc, mm, mf, zq, status
 
 
@@ -380,24 +329,14 @@ def encode_stream(symbols: torch.Tensor, table: int) -> Tuple[torch.Tensor, torc
     info = symbols.reshape(-1).contiguous()
     if info.dtype not in (torch.int64, torch.int32):
         raise TypeError("encode_stream: int64 / int32 symbols")
-    n = info.numel()
-    if n == 0:
+    if info.numel() == 0:
         raise ValueError("encode_stream: an empty input is an empty FILE in the reference (indices_coding.py:116-118), not a stream")
-    l, dev = _lib.lib(), info.device
-    cap = l.cgic_stream_capacity(_table(table), n)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    nbytes = torch.empty(1, dtype=torch.int32, device=dev)
-    wsb = l.cgic_stream_workspace_bytes(n)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-    with torch.cuda.device(dev):
-        _lib.call("cgic_encode_stream", _table(table), _lib.ptr(info), info.element_size(), n, _lib.ptr(out), cap, _lib.ptr(nbytes),
-                  _lib.ptr(ws), _lib.current_stream(dev))
-    return out, nbytes
+    return _coding.encode_stream(_table(table), info)
 
 
 @encode_stream.register_fake
 def _(symbols, table):
-    cap = int(_lib.lib().cgic_stream_capacity(_table(table), symbols.numel()))
+    cap = _coding.stream_capacity(_table(table), symbols.numel())
     return symbols.new_empty((cap,), dtype=torch.uint8), symbols.new_empty((1,), dtype=torch.int32)
 
 
@@ -409,14 +348,7 @@ def decode_stream(stream: torch.Tensor, nbytes: int, table: int) -> Tuple[torch.
     _lib.require_device(stream)
     if stream.dtype != torch.uint8 or stream.numel() < nbytes + 16:
         raise ValueError("decode_stream: uint8 buffer of at least nbytes + 16 bytes")
-    dev = stream.device
-    cap = max(1, (int(nbytes) - 1) * 8)
-    syms = torch.empty(cap, dtype=torch.int64, device=dev)
-    count = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("cgic_decode_stream", _table(table), _lib.ptr(stream.contiguous()), int(nbytes), _lib.ptr(syms), cap, _lib.ptr(count),
-                  _lib.current_stream(dev))
-    return syms, count
+    return _coding.decode_stream(_table(table), stream.contiguous(), nbytes)
 
 
 @decode_stream.register_fake
@@ -427,12 +359,7 @@ def _(stream, nbytes, table):
 @torch.library.custom_op("cgic::index_histogram", mutates_args=("hist",), device_types=_DEV)
 def index_histogram(indices: torch.Tensor, hist: torch.Tensor) -> None:
     """hist[indices[i]] += 1 (quantize.py:79-81), exact int64"""
-    _lib.require_device(indices, hist)
-    if indices.dtype != torch.int64 or hist.dtype != torch.int64:
-        raise TypeError("index_histogram: int64 indices and histogram")
-    idx = indices.contiguous()
-    with torch.cuda.device(idx.device):
-        _lib.call("cgic_index_histogram", _lib.ptr(idx), idx.numel(), hist.numel(), _lib.ptr(hist), _lib.current_stream(idx.device))
+    _quantize.index_histogram(indices, hist)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -446,20 +373,7 @@ def _up(m, k):
 def grain_merge(h_coarse: torch.Tensor, h_medium: torch.Tensor, h_fine: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor,
                 mask_f: torch.Tensor) -> torch.Tensor:
     """up4(h_coarse)*up4(mask_c) + up2(h_medium)*up2(mask_m) + h_fine*mask_f in one pass (vqvae_blocks.py:361-366), bit-identical"""
-    _lib.require_device(h_coarse, h_medium, h_fine, mask_c, mask_m, mask_f)
-    hc, hm, hf = (t.contiguous().float() for t in (h_coarse, h_medium, h_fine))
-    mc, mm, mf = (m.contiguous() for m in (mask_c, mask_m, mask_f))
-    _lib.require_int32_masks(mc, mm, mf)
-    B, C, h, w = hf.shape
-    if tuple(hc.shape) != (B, C, h // 4, w // 4) or tuple(hm.shape) != (B, C, h // 2, w // 2):
-        raise ValueError("h_coarse / h_medium must be the fine map's shape divided by 4 / 2")
-    if mc.numel() != B * (h // 4) * (w // 4) or mm.numel() != B * (h // 2) * (w // 2) or mf.numel() != B * h * w:
-        raise ValueError("grain_merge: masks at 1/4, 1/2, 1/1 of the fine grid, one per image")
-    out = torch.empty_like(hf)
-    with torch.cuda.device(hf.device):
-        _lib.call("cgic_grain_merge_f32", _lib.ptr(hc), _lib.ptr(hm), _lib.ptr(hf), _lib.ptr(mc), _lib.ptr(mm),
-                  _lib.ptr(mf), B, C, h, w, _lib.ptr(out), _lib.current_stream(hf.device))
-    return out
+    return _merge.grain_merge(h_coarse, h_medium, h_fine, mask_c, mask_m, mask_f)
 
 
 @grain_merge.register_fake
@@ -493,13 +407,7 @@ grain_merge.register_autograd(_grain_merge_bwd, setup_context=_grain_merge_setup
 def avg_pool(x: torch.Tensor, k: int) -> torch.Tensor:
     """torch.nn.AvgPool2d(k, k, 0) for k in (2, 4) (decoder.py:304-305,366-367): row-major window sum / k^2, bit-identical to the CPU kernel;
     H and W must be multiples of k (the decoder's are; cgic_avgpool_f32 refuses anything else)"""
-    _lib.require_device(x)
-    x = x.contiguous().float()
-    B, C, H, W = x.shape
-    out = torch.empty((B, C, H // k, W // k), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.call("cgic_avgpool_f32", _lib.ptr(x), B * C, H, W, int(k), _lib.ptr(out), _lib.current_stream(x.device))
-    return out
+    return _merge.avg_pool(x, k)
 
 
 @avg_pool.register_fake
@@ -523,18 +431,8 @@ avg_pool.register_autograd(_avg_pool_bwd, setup_context=_avg_pool_setup)
 @torch.library.custom_op("cgic::decoder_blend_medium", mutates_args=(), device_types=_DEV)
 def decoder_blend_medium(h: torch.Tensor, h_medium: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor) -> torch.Tensor:
     """h * up2(mask_c) + h_medium * mask_m on the medium grid (decoder.py:372-374)"""
-    _lib.require_device(h, h_medium, mask_c, mask_m)
-    h, hm = h.contiguous().float(), h_medium.contiguous().float()
-    mc, mm = mask_c.contiguous(), mask_m.contiguous()
-    _lib.require_int32_masks(mc, mm)
-    B, C, hh, ww = h.shape
-    if tuple(hm.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 2) * (ww // 2) or mm.numel() != B * hh * ww:
-        raise ValueError("decoder_blend_medium: h, h_medium on the medium grid; mask_c at half of it, mask_m on it")
-    out = torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        _lib.call("cgic_decoder_blend_medium_f32", _lib.ptr(h), _lib.ptr(hm), _lib.ptr(mc), _lib.ptr(mm), B, C, hh, ww,
-                  _lib.ptr(out), _lib.current_stream(h.device))
-    return out
+    return _merge.decoder_blend_medium(h, h_medium, mask_c, mask_m,
+                                       "decoder_blend_medium: h, h_medium on the medium grid; mask_c at half of it, mask_m on it")
 
 
 @decoder_blend_medium.register_fake
@@ -558,19 +456,7 @@ decoder_blend_medium.register_autograd(_blend_m_bwd, setup_context=_blend_m_setu
 @torch.library.custom_op("cgic::decoder_blend_fine", mutates_args=(), device_types=_DEV)
 def decoder_blend_fine(h: torch.Tensor, h_fine: torch.Tensor, mask_c: torch.Tensor, mask_m: torch.Tensor, mask_f: torch.Tensor) -> torch.Tensor:
     """h * up4(mask_c) + h * up2(mask_m) + h_fine * mask_f on the fine grid (decoder.py:375-378)"""
-    _lib.require_device(h, h_fine, mask_c, mask_m, mask_f)
-    h, hf = h.contiguous().float(), h_fine.contiguous().float()
-    mc, mm, mf = (m.contiguous() for m in (mask_c, mask_m, mask_f))
-    _lib.require_int32_masks(mc, mm, mf)
-    B, C, hh, ww = h.shape
-    if tuple(hf.shape) != (B, C, hh, ww) or mc.numel() != B * (hh // 4) * (ww // 4) or mm.numel() != B * (hh // 2) * (ww // 2) \
-            or mf.numel() != B * hh * ww:
-        raise ValueError("decoder_blend_fine: h, h_fine on the fine grid; masks at 1/4, 1/2, 1/1 of it")
-    out = torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        _lib.call("cgic_decoder_blend_fine_f32", _lib.ptr(h), _lib.ptr(hf), _lib.ptr(mc), _lib.ptr(mm), _lib.ptr(mf), B, C, hh, ww,
-                  _lib.ptr(out), _lib.current_stream(h.device))
-    return out
+    return _merge.decoder_blend_fine(h, h_fine, mask_c, mask_m, mask_f)
 
 
 @decoder_blend_fine.register_fake

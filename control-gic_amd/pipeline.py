@@ -106,6 +106,44 @@ class HotPathPipeline:
         return [self._chain(x, z, hist, decode)]
 
 
+def image_io_buffers(slot, B, H, W, decode, x_out, want_zq, want_loss, hist, alloc, ws_refine=None):
+    """the buffers of one cgic_compress_image call (struct cgic_image_io, include/cgic_hip.h) for B images of H x W, allocated by
+    alloc(shape, dtype) -> (tensors, io): the tensors by name (they own the memory: keep the dict for as long as `io` is used) and
+    the _lib.ImageIO that points at them.  slot: the codec's slot_bytes(H / 4, W / 4); decode: also the decoder's outputs and
+    workspace; x_out: the fp32 [B,3,H,W] image batch the entropy pass writes (uint8 frames in; a tile batch); want_zq / want_loss:
+    z_q, and the loss with the VQ workspace it needs; hist: the caller's int64 usage histogram or None; ws_refine: the caller's
+    refinement scratch or None (who gets one differs between the callers).  What is not wanted stays NULL.  io.x, io.z and
+    io.x_is_u8 are the caller's: they change per call, or mean something else to it"""
+    l = _lib.lib()
+    f32, i32, i64, u8 = torch.float32, torch.int32, torch.int64, torch.uint8
+    h, w = H // 4, W // 4
+    t = {"x_out": alloc((B, 3, H, W), f32) if x_out else None,
+         "e8": alloc((B, H // 8, W // 8), f32), "e16": alloc((B, H // 16, W // 16), f32), "flat8": alloc((B, H // 8, W // 8), f32),
+         "ind": alloc((B * h * w,), i64), "z_q": alloc((B, 4, h, w), f32) if want_zq else None, "loss": alloc((), f32) if want_loss else None,
+         "mask": _lib.grain_masks(B, h, w, alloc=alloc),
+         "data": alloc((B, _lib.NUM_STREAMS, slot), u8), "nbytes": alloc((B, _lib.NUM_STREAMS), i32), "hist": hist,
+         "ws_vq": alloc((l.cgic_vq_workspace_bytes(B * h * w),), u8) if want_loss else None,
+         "ws_compress": alloc((max(1, l.cgic_compress_workspace_bytes(B, h, w)),), u8),
+         "ws_decompress": alloc((l.cgic_decompress_workspace_bytes(B, h, w),), u8) if decode else None,
+         "ws_refine": ws_refine}
+    if decode:
+        t.update({"dind": alloc((B, h, w), i64), "dmask": _lib.grain_masks(B, h, w, alloc=alloc), "dz_q": alloc((B, 4, h, w), f32),
+                  "status": alloc((B,), i32)})
+    p = _lib.ptr
+    io = _lib.ImageIO()
+    io.x_out, io.e8, io.e16, io.flat8 = p(t["x_out"]), p(t["e8"]), p(t["e16"]), p(t["flat8"])
+    io.ind, io.z_q, io.loss = p(t["ind"]), p(t["z_q"]), p(t["loss"])
+    io.mask_c, io.mask_m, io.mask_f = (p(m) for m in t["mask"])
+    io.streams, io.slot, io.nbytes, io.hist = p(t["data"]), slot, p(t["nbytes"]), p(hist)
+    if decode:
+        io.dind, io.dz_q, io.status = p(t["dind"]), p(t["dz_q"]), p(t["status"])
+        io.dmask_c, io.dmask_m, io.dmask_f = (p(m) for m in t["dmask"])
+    io.ws_vq, io.ws_compress, io.ws_decompress = p(t["ws_vq"]), p(t["ws_compress"]), p(t["ws_decompress"])
+    if ws_refine is not None:
+        io.ws_refine, io.ws_refine_bytes = p(ws_refine), ws_refine.numel() * ws_refine.element_size()
+    return t, io
+
+
 class HotCall:
     """CGIC.compress (hot path: model.py:206-401 without the conv nets) for batches of ONE size as ONE foreign call per batch
     (cgic_compress_image: entropy maps -> [VQ + per-image router] -> stream coder (+ usage histogram) -> prefix decoder + merge)
@@ -127,40 +165,16 @@ class HotCall:
         self.codec = GrainCodec(frequency if frequency is not None else quantizer.embedding_counter, w)
         self.prepared = prepare_codebook(w) if prepare else None
         self.decoder = _decoder_flag(decoder)
-        h, ww = H // 4, W // 4
         l = _lib.lib()
-        f32, i32, i64, u8t = torch.float32, torch.int32, torch.int64, torch.uint8
         E = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        slot = self.codec.slot_bytes(h, ww)
-        t = {"e8": E((B, H // 8, W // 8), f32), "e16": E((B, H // 16, W // 16), f32), "flat8": E((B, H // 8, W // 8), f32),
-             "x_out": E((B, 3, H, W), f32) if u8 else None,
-             "ind": E((B * h * ww,), i64), "z_q": E((B, 4, h, ww), f32) if want_zq else None, "loss": E((), f32) if want_loss else None,
-             "mask": [E((B, 1, h // 4, ww // 4), i32), E((B, 1, h // 2, ww // 2), i32), E((B, 1, h, ww), i32)],
-             "data": E((B, _lib.NUM_STREAMS, slot), u8t), "nbytes": E((B, _lib.NUM_STREAMS), i32), "hist": hist}
-        if decode:
-            t.update({"dind": E((B, h, ww), i64), "dmask": [E((B, 1, h // 4, ww // 4), i32), E((B, 1, h // 2, ww // 2), i32), E((B, 1, h, ww), i32)],
-                      "dz_q": E((B, 4, h, ww), f32), "status": E((B,), i32)})
-        ws = {"vq": E((l.cgic_vq_workspace_bytes(B * h * ww),), u8t) if want_loss else None,
-              "c": E((max(1, l.cgic_compress_workspace_bytes(B, h, ww)),), u8t),
-              "d": E((l.cgic_decompress_workspace_bytes(B, h, ww),), u8t) if decode else None}
-        self._t, self._ws, self._decode, self._slot = t, ws, bool(decode), slot
-        p = _lib.ptr
-        io = _lib.ImageIO()
-        io.x_is_u8 = int(self.u8)
-        io.x_out, io.e8, io.e16, io.flat8 = p(t["x_out"]), p(t["e8"]), p(t["e16"]), p(t["flat8"])
-        io.ind, io.z_q, io.loss = p(t["ind"]), p(t["z_q"]), p(t["loss"])
-        io.mask_c, io.mask_m, io.mask_f = (p(m) for m in t["mask"])
-        io.streams, io.slot, io.nbytes, io.hist = p(t["data"]), slot, p(t["nbytes"]), p(hist)
-        if decode:
-            io.dind, io.dz_q, io.status = p(t["dind"]), p(t["dz_q"]), p(t["status"])
-            io.dmask_c, io.dmask_m, io.dmask_f = (p(m) for m in t["dmask"])
-        io.ws_vq, io.ws_compress, io.ws_decompress = p(ws["vq"]), p(ws["c"]), p(ws["d"])
         # the refinement scratch: the launch's queues (images with long threshold bands publish them, the other routers help; large
         # tiles: their row bands split a band) -- or, for an image beyond ~768x768 routed as one segment, the patched copies of its maps
         nref = l.cgic_router_refine_scratch_bytes(B, H // 16, W // 16, 1)
-        if nref and (_lib.REFINE_FUSED_QUEUES or not l.cgic_router_refine_in_lds(B, H // 16, W // 16, 1)):
-            ws["r"] = E((nref,), u8t)
-            io.ws_refine, io.ws_refine_bytes = p(ws["r"]), nref
+        wanted = nref and (_lib.REFINE_FUSED_QUEUES or not l.cgic_router_refine_in_lds(B, H // 16, W // 16, 1))
+        self._slot, self._decode = self.codec.slot_bytes(H // 4, W // 4), bool(decode)
+        self._t, io = image_io_buffers(self._slot, B, H, W, decode, u8, want_zq, want_loss, hist, E,
+                                       ws_refine=E((nref,), torch.uint8) if wanted else None)
+        io.x_is_u8 = int(self.u8)
         self._io = io
         self._mode = ctypes.c_int(0)
         self._CompressedBatch = CompressedBatch

@@ -5,12 +5,14 @@ Same constructor, attributes, forward signature and state_dict keys; the
 forward body is one fused HIP kernel (csrc/cgic_vq.hip) instead of an N x K
 distance matrix in HBM.
 """
+import ctypes
 from collections.abc import MutableMapping
 
 import torch
 from torch import nn
 
 from . import _lib
+from .router import refine_source
 
 
 class _CounterView(MutableMapping):
@@ -127,6 +129,16 @@ def prepare_codebook(weight, out=None):
     return img
 
 
+def index_histogram(indices, hist):
+    """hist[indices[i]] += 1 (quantize.py:79-81), exact int64 (cgic_index_histogram)"""
+    _lib.require_device(indices, hist)
+    if indices.dtype != torch.int64 or hist.dtype != torch.int64:
+        raise TypeError("index_histogram: int64 indices and histogram")
+    idx = indices.contiguous()
+    with _lib.on_device(idx.device):
+        _lib.call("cgic_index_histogram", _lib.ptr(idx), idx.numel(), hist.numel(), _lib.ptr(hist), _lib.current_stream(idx.device))
+
+
 def _vq_forward(z, weight, beta, legacy, hist, want_zq=True, want_loss=True, kernel="mfma", quant_conv=None, conv_bias_first=False,
                 prepared=None):
     """quant_conv: optional Conv2d(4, 4, 1) (or (weight, bias)) applied to z inside the kernel -- CGIC.quant_conv
@@ -169,13 +181,11 @@ def vq_forward_route(z, weight, beta, legacy, e16, e8, coarse_ratio, medium_rati
     whose threshold band is long starts over with the launch's refinement queues and the routers that are done help (tie-heavy
     batches: 71 -> 50 us on smooth 8-bit content; that kernel variant costs the ordinary launch ~2 us alone); None: the process
     default (_lib.REFINE_FUSED_QUEUES, off); pipeline.HotPathPipeline decides per stream of batches.  Same masks either way."""
-    import ctypes
     _lib.require_device(z, weight, e16, e8)
     if refine_queues is None:
         refine_queues = _lib.REFINE_FUSED_QUEUES
-    if flat8 is None and pixels is not None:
-        from .router import _flat_of
-        flat8 = _flat_of(pixels, e8, e16)
+    if pixels is not None:                  # (only the caller's pixels: this call never takes them from the maps' tags)
+        pixels, flat8, _ = refine_source(e16, e8, pixels, flat8)
     B, C, h, w = z.shape
     z = z.contiguous()
     weight = weight.detach().contiguous()
@@ -190,9 +200,7 @@ def vq_forward_route(z, weight, beta, legacy, e16, e8, coarse_ratio, medium_rati
     z_q = torch.empty_like(z) if want_zq else None
     loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
     ws = torch.empty(_lib.lib().cgic_vq_workspace_bytes(N), dtype=torch.uint8, device=dev) if want_loss else None
-    mc = torch.empty((B, 1, h16, w16), dtype=torch.int32, device=dev)
-    mm = torch.empty((B, 1, 2 * h16, 2 * w16), dtype=torch.int32, device=dev)
-    mf = torch.empty((B, 1, 4 * h16, 4 * w16), dtype=torch.int32, device=dev)
+    mc, mm, mf = _lib.grain_masks(B, 4 * h16, 4 * w16, dev)
     gate = torch.empty((B, 1, 4 * h16, 12 * w16), dtype=torch.float32, device=dev) if want_gate else None
     mode = ctypes.c_int(0)
     qc, keep = _lib.conv_arg(quant_conv, conv_bias_first)

@@ -28,10 +28,17 @@ import torch
 
 from . import _lib
 from .quantize import FusedQuantConv, _vq_forward
-from .router import TripleGrainFixedEntropyRouter, _flat_of
+from .router import TripleGrainFixedEntropyRouter, refine_source, routing_per_image
 
 #: the most candidates one rate_table call takes (cgic_rate_table)
 MAX_CANDIDATES = 64
+
+
+def _table_handle(codec):
+    """the cgic_table* handle of a code table: from a GrainCodec (codec.huffman.table.handle), or the handle itself -- how the
+    torch.ops.cgic rate ops, which carry the table as its handle, reach the same calls"""
+    huffman = getattr(codec, "huffman", None)
+    return codec if huffman is None else huffman.table.handle
 
 
 def _head_indices(quantizer, h, quant_conv):
@@ -141,12 +148,7 @@ def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, 
     control_gic_amd.Entropy / entropy_maps, like the router does.  per_image as the router's.  -> RateTable"""
     cand = _check_candidates(candidates)
     inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
-    explicit = pixels is not None
-    if pixels is None:
-        p16, p8 = getattr(e16, "_cgic_pixels", None), getattr(e8, "_cgic_pixels", None)
-        pixels = p16 if (p16 is not None and p16 is p8) else None
-    if flat8 is None and pixels is not None:
-        flat8 = _flat_of(pixels, e8, e16)
+    pixels, flat8, explicit = refine_source(e16, e8, pixels, flat8)
     dev = e16c.device
     C = len(cand)
     cr = (ctypes.c_double * C)(*[c for c, _ in cand])
@@ -156,7 +158,7 @@ def rate_table(codec, ind_c, ind_m, ind_f, e16, e8, candidates, per_image=True, 
     nbytes = torch.empty((C, B, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(_lib.lib().cgic_rate_table_workspace_bytes(B, h16, w16, C, pi)), 1), dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.call("cgic_rate_table", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+        _lib.call("cgic_rate_table", _table_handle(codec), _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
                   _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, C, cr, mr, pi, px, _lib.ptr(nbytes), _lib.ptr(ws),
                   _lib.current_stream(dev))
     del keep
@@ -317,7 +319,7 @@ def rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, ranks=None):
     nbytes = torch.empty((B, n8 + 1, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(_lib.lib().cgic_rate_curve_workspace_bytes(B, h16, w16)), 16), dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.call("cgic_rate_curve", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+        _lib.call("cgic_rate_curve", _table_handle(codec), _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
                   _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, float(coarse_ratio), _lib.ptr(nbytes), _lib.ptr(ws),
                   _lib.current_stream(dev))
     n_coarse = ws[:B * 16].view(torch.int32).view(B, 4)[:, 0].to(torch.int64).cpu()
@@ -432,14 +434,12 @@ def route_to_bpp(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, target_bpp=N
     elif not (isinstance(budget, torch.Tensor) and budget.dtype == torch.int64 and budget.numel() == 1 and budget.device == dev
               and budget.is_contiguous()):
         raise ValueError("route_to_bpp: budget must be an int64 tensor of one element on the maps' device")
-    mc = torch.empty((B, 1, h16, w16), dtype=torch.int32, device=dev)
-    mm = torch.empty((B, 1, 2 * h16, 2 * w16), dtype=torch.int32, device=dev)
-    mf = torch.empty((B, 1, 4 * h16, 4 * w16), dtype=torch.int32, device=dev)
+    mc, mm, mf = _lib.grain_masks(B, 4 * h16, 4 * w16, dev)
     ind = torch.empty((B, 4 * h16, 4 * w16), dtype=torch.int64, device=dev)
     choice = torch.empty((4,), dtype=torch.int64, device=dev)
     ws = torch.empty(max(int(_lib.lib().cgic_route_to_budget_workspace_bytes(B, h16, w16, R)), 16), dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.call("cgic_route_to_budget", codec.huffman.table.handle, _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
+        _lib.call("cgic_route_to_budget", _table_handle(codec), _lib.ptr(inds[0]), _lib.ptr(inds[1]), _lib.ptr(inds[2]),
                   _lib.ptr(e16c), _lib.ptr(e8c), B, h16, w16, c, _lib.ptr(ranks_dev), R, _lib.ptr(budget), _lib.ptr(mc), _lib.ptr(mm),
                   _lib.ptr(mf), _lib.ptr(ind), _lib.ptr(choice), _lib.ptr(ws), _lib.current_stream(dev))
     return BppRoute([mc, mm, mf], ind, 0 if c > 0.0 else 1, choice, c, ranks, mediums)
@@ -451,9 +451,7 @@ def gather_grain_indices(ind_c, ind_m, ind_f, masks):
     _lib.require_device(ind_c, ind_m, ind_f, *masks)
     mc, mm, mf = (m.contiguous() for m in masks)
     B, h, w = mf.shape[0], mf.shape[-2], mf.shape[-1]
-    for m in (mc, mm, mf):
-        if m.dtype != torch.int32:
-            raise TypeError("masks must be int32 like the router's")
+    _lib.require_int32_masks(mc, mm, mf, msg="masks must be int32 like the router's")
     if mc.numel() != B * (h // 4) * (w // 4) or mm.numel() != B * (h // 2) * (w // 2):
         raise ValueError("masks at 1/4, 1/2, 1/1 of the fine grid expected")
     ic, im, if_ = (t.contiguous() for t in (ind_c, ind_m, ind_f))
@@ -571,7 +569,7 @@ def rate_curve_tiled(codec, tiles, coarse_ratio, image_hw=None, settings=None, e
     tile_nbytes = torch.empty((T, M, _lib.NUM_STREAMS), dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(_lib.lib().cgic_rate_curve_tiles_workspace_bytes(max(T, 1), M, 1)), 16), dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.call("cgic_rate_curve_tiles", codec.huffman.table.handle, *[_lib.ptr(b) for b in bufs], count, desc, _lib.ptr(desc_dev),
+        _lib.call("cgic_rate_curve_tiles", _table_handle(codec), *[_lib.ptr(b) for b in bufs], count, desc, _lib.ptr(desc_dev),
                   T, N, c, _lib.ptr(ranks_dev), S, M, _lib.ptr(image_nbytes), _lib.ptr(tile_nbytes), _lib.ptr(ws),
                   _lib.current_stream(dev))
     curve = TiledRateCurve(image_nbytes, tile_nbytes, c, mediums, ranks, shapes, num_pixels, tile_shape, tile_image)
@@ -607,18 +605,12 @@ def _encode_captured(model, x, entropy=False):
         mods.update(e8=model.entropy_calculation_p8, e16=model.entropy_calculation_p16)
     got = {}
     hooks = [mod.register_forward_hook(lambda mod, args, out, name=name: got.__setitem__(name, out)) for name, mod in mods.items()]
-    saved = params.get("per_image", None)
-    params["per_image"] = True
     try:
-        with torch.no_grad():
+        with routing_per_image(params), torch.no_grad():
             model.encode(x)
     finally:
         for hk in hooks:
             hk.remove()
-        if saved is None:
-            params.pop("per_image", None)
-        else:
-            params["per_image"] = saved
     return got
 
 
