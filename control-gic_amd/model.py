@@ -22,11 +22,20 @@ from .router import routing_per_image
 ROUTER_TARGET = "control_gic_amd.router.TripleGrainFixedEntropyRouter"
 
 
-def grain_merge(h_coarse, h_medium, h_fine, mask):
+def _raw(*feats):
+    """no autograd is needed for these features: the raw kernel call may serve them"""
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in feats))
+
+
+def grain_merge(h_coarse, h_medium, h_fine, mask, out_dtype=None):
     """h = up4(h_coarse)*up4(mask[0]) + up2(h_medium)*up2(mask[1]) + h_fine*mask[2]
     (vqvae_blocks.py:361-366) in one pass; mask = the router's three int32 tensors.  Differentiable w.r.t. the three
-    latents (torch.ops.cgic.grain_merge: the op sits inside the reference's training graph)."""
-    return torch.ops.cgic.grain_merge(h_coarse, h_medium, h_fine, mask[0], mask[1], mask[2])
+    latents (torch.ops.cgic.grain_merge: the op sits inside the reference's training graph).  The result is fp32 like the
+    reference's expression, also for fp16 / bf16 latents; out_dtype = their half type (the raw kernel call, no autograd) rounds it
+    once to that type."""
+    if out_dtype is None:
+        return torch.ops.cgic.grain_merge(h_coarse, h_medium, h_fine, mask[0], mask[1], mask[2])
+    return _merge.grain_merge(h_coarse, h_medium, h_fine, mask[0], mask[1], mask[2], out_dtype=out_dtype)
 
 
 def avg_pool(x, k):
@@ -35,21 +44,24 @@ def avg_pool(x, k):
     return torch.ops.cgic.avg_pool(x, int(k))
 
 
-def decoder_blend_medium(h, h_medium, mask, out=None):
+def decoder_blend_medium(h, h_medium, mask, out=None, out_dtype=None):
     """h * up2(mask[0]) + h_medium * mask[1] on the medium grid (decoder.py:372-374).  Differentiable
-    (torch.ops.cgic.decoder_blend_medium); with `out` (which may be `h`: in place) the raw kernel call, no autograd."""
-    if out is None:
+    (torch.ops.cgic.decoder_blend_medium); with `out` (which may be `h`: in place) or `out_dtype` the raw kernel call, no
+    autograd.  fp32 out, also for fp16 / bf16 features (the reference's promotion), unless `out` / `out_dtype` is their half type."""
+    if out is None and out_dtype is None:
         return torch.ops.cgic.decoder_blend_medium(h, h_medium, mask[0], mask[1])
     return _merge.decoder_blend_medium(h, h_medium, mask[0], mask[1],
-                                       "decoder_blend_medium: h, h_medium on the medium grid; mask[0] at half of it, mask[1] on it", out=out)
+                                       "decoder_blend_medium: h, h_medium on the medium grid; mask[0] at half of it, mask[1] on it", out=out,
+                                       out_dtype=out_dtype)
 
 
-def decoder_blend_fine(h, h_fine, mask, out=None):
+def decoder_blend_fine(h, h_fine, mask, out=None, out_dtype=None):
     """h * up4(mask[0]) + h * up2(mask[1]) + h_fine * mask[2] on the fine grid (decoder.py:375-378).  Differentiable
-    (torch.ops.cgic.decoder_blend_fine); with `out` the raw kernel call (in place if `out is h`), no autograd."""
-    if out is None:
+    (torch.ops.cgic.decoder_blend_fine); with `out` (in place if `out is h`) or `out_dtype` the raw kernel call, no autograd.
+    fp32 out, also for fp16 / bf16 features (the reference's promotion), unless `out` / `out_dtype` is their half type."""
+    if out is None and out_dtype is None:
         return torch.ops.cgic.decoder_blend_fine(h, h_fine, mask[0], mask[1], mask[2])
-    return _merge.decoder_blend_fine(h, h_fine, *mask, out=out)
+    return _merge.decoder_blend_fine(h, h_fine, *mask, out=out, out_dtype=out_dtype)
 
 
 def _codec_for(model, h_indices=None):
@@ -131,16 +143,23 @@ def compress(self, input, path, h_indices=None, h_mask=None, save_img=False):
 
 
 class AvgPool(torch.nn.Module):
-    """torch.nn.AvgPool2d(k, k, 0) on the library's kernel (decoder.py:304-305): bit-identical to the CPU kernel, differentiable"""
+    """torch.nn.AvgPool2d(k, k, 0) on the library's kernel (decoder.py:304-305): bit-identical to the CPU kernel, differentiable.
+    A fp16 / bf16 input keeps its type like AvgPool2d's (the fp32 window sum / k^2 rounded once: the CPU kernel's value) on the half
+    kernel when no autograd is needed, and takes torch's own pool when it is"""
 
     def __init__(self, k):
         super().__init__()
         self.k = int(k)
 
     def forward(self, x):
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[2] % self.k or x.shape[3] % self.k:
+        if not x.is_cuda or x.dim() != 4 or x.shape[2] % self.k or x.shape[3] % self.k:
             return torch.nn.functional.avg_pool2d(x, self.k, self.k, 0)
-        return torch.ops.cgic.avg_pool(x, self.k)
+        if x.dtype == torch.float32:
+            return torch.ops.cgic.avg_pool(x, self.k)
+        # fp16 / bf16 (the decoder under torch.autocast): AvgPool2d keeps the type; the half kernel has no autograd formula
+        if x.dtype in (torch.float16, torch.bfloat16) and _raw(x):
+            return _merge.avg_pool(x, self.k, out_dtype=x.dtype)
+        return torch.nn.functional.avg_pool2d(x, self.k, self.k, 0)
 
 
 def install(model, per_image=False, fuse_convs=True, patch_pools=True):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 15
+#define CGIC_ABI_VERSION 16
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -600,6 +600,41 @@ int cgic_decoder_blend_medium_f32(const float *h, const float *h_medium, const i
 int cgic_decoder_blend_fine_f32(const float *h, const float *h_fine, const int32_t *mask_c, const int32_t *mask_m,
                                 const int32_t *mask_f, int64_t B, int C, int64_t hh, int64_t ww, float *out,
                                 cgic_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The merge, the pools and the blends on half-precision features (ABI 16): what the reference computes when its conv
+ * nets run under torch.autocast in fp16 or bf16.  There `h * upsample(mask.float()) + own * mask` promotes to fp32 and
+ * AvgPool2d keeps the half type, so:
+ *   in_dtype   CGIC_DT_F16 or CGIC_DT_BF16: the type of EVERY feature tensor of the call (CGIC_DT_F32 is
+ *              CGIC_ERR_UNSUPPORTED: that is the _f32 entry point's)
+ *   out_dtype  CGIC_DT_F32 (the reference's promotion for the merge and the blends) or in_dtype (AvgPool2d's result; for the
+ *              merge and the blends an option the reference does not have: its fp32 value rounded once)
+ * Arithmetic: the features are upcast exactly (fp16 subnormals included), the products, the left-to-right sums and the
+ * pool's row-major running sum / (float)(k*k) are the fp32 operations of the _f32 kernels, a half output is rounded once to
+ * nearest-even (fp16 overflow: +-Inf).  Bit-identical to the reference's expression on the CPU.  Products and sums, not
+ * selects: an Inf or NaN under a zero mask is a NaN.
+ * Shapes and masks as the _f32 siblings.  A pointer must be aligned to its own element; wider alignment and a row width
+ * that is a multiple of 8 let a thread take 8 consecutive x with 16-byte accesses, otherwise 4, 2 or 1 (csrc/cgic_merge_plan.h).
+ * `out` may be `h` itself for the two blends when out_dtype == in_dtype (in place); any other overlap of `out` with an input
+ * is CGIC_ERR_INVALID.  Every check precedes the one launch; not available inside a launch group.
+ *   cgic_grain_merge_h            vqvae_blocks.py:361-366
+ *   cgic_avgpool_h                decoder.py:304-305,366-367
+ *   cgic_decoder_blend_medium_h   decoder.py:372-374
+ *   cgic_decoder_blend_fine_h     decoder.py:375-378
+ * ------------------------------------------------------------------------- */
+#define CGIC_DT_F32 0
+#define CGIC_DT_F16 1
+#define CGIC_DT_BF16 2
+int cgic_grain_merge_h(const void *h_coarse, const void *h_medium, const void *h_fine, int in_dtype, const int32_t *mask_c,
+                       const int32_t *mask_m, const int32_t *mask_f, int64_t B, int C, int64_t h, int64_t w, void *out,
+                       int out_dtype, cgic_stream_t stream);
+int cgic_avgpool_h(const void *x, int in_dtype, int64_t planes, int64_t H, int64_t W, int k, void *out, int out_dtype,
+                   cgic_stream_t stream);
+int cgic_decoder_blend_medium_h(const void *h, const void *h_medium, int in_dtype, const int32_t *mask_c, const int32_t *mask_m,
+                                int64_t B, int C, int64_t hh, int64_t ww, void *out, int out_dtype, cgic_stream_t stream);
+int cgic_decoder_blend_fine_h(const void *h, const void *h_fine, int in_dtype, const int32_t *mask_c, const int32_t *mask_m,
+                              const int32_t *mask_f, int64_t B, int C, int64_t hh, int64_t ww, void *out, int out_dtype,
+                              cgic_stream_t stream);
 
 /* embedding gather on its own (model.py:121,391-392): out[b, c, p] = codebook[ind[b, p], c] */
 int cgic_embedding_gather_f32(const int64_t *ind, int64_t B, int64_t hw, const float *codebook, int K,
