@@ -3,7 +3,7 @@ their checks, no autograd.  torch.ops.cgic.grain_merge / avg_pool / decoder_blen
 autograd formula); model.decoder_blend_*(..., out=) call them directly.  The masks are the router's int32 tensors.
 
 Feature types.  fp32 features take the _f32 kernels.  Features that are ALL fp16 or ALL bf16 (the conv nets under torch.autocast)
-take the _h kernels (csrc/cgic_merge_half.hip), which read the halves themselves: no cast pass.  Any mixture of types is cast to
+take the _h calls (csrc/cgic_merge.hip: the same kernels), which read the halves themselves: no cast pass.  Any mixture of types is cast to
 fp32 first, as every type was before the _h kernels existed.  The result is fp32 -- what the reference's expressions promote to,
 the masks being .float() -- unless `out_dtype` (or the dtype of `out`) asks for the features' own half type: the same fp32 value
 rounded once to nearest-even, an option the reference does not have.

@@ -460,6 +460,7 @@ int cgic_decompress_streams(const cgic_table *t, const uint8_t *in, int64_t slot
  *   h_coarse device [B,C,h/4,w/4], h_medium [B,C,h/2,w/2], h_fine [B,C,h,w] fp32
  *   mask_c/m/f device int32 [B,h/4,w/4] / [B,h/2,w/2] / [B,h,w] (the router's)
  *   out device [B,C,h,w] fp32 -- same products, same left-to-right sums: bit-identical
+ * Pointers: see the decoder-side calls below (aligned to 4 bytes; out overlaps no input).
  * ------------------------------------------------------------------------- */
 int cgic_grain_merge_f32(const float *h_coarse, const float *h_medium, const float *h_fine,
                          const int32_t *mask_c, const int32_t *mask_m, const int32_t *mask_f, int64_t B,
@@ -471,11 +472,21 @@ int cgic_grain_merge_f32(const float *h_coarse, const float *h_medium, const flo
  * coarse / medium branch), :372-374 and :375-378 (inside the up path):
  *   medium grid:  h = h * up2(mask0) + h_medium * mask1
  *   fine grid:    h = h * up4(mask0) + h * up2(mask1) + h_fine * mask2
- *   h, h_medium / h_fine, out   device [B,C,hh,ww] fp32 on the grid of the call (out may alias h)
+ *   h, h_medium / h_fine, out   device [B,C,hh,ww] fp32 on the grid of the call (out may be h itself: in place)
  *   mask_c / mask_m / mask_f    device int32 [B,·,·] at 1/4, 1/2, 1/1 of the FINE grid (the router's / the decoded ones)
  *   same products, same left-to-right sums as the reference expressions: bit-identical.
  * cgic_avgpool_f32: x [planes,H,W] -> out [planes,H/k,W/k], k in {2,4}; row-major running sum of the window
  *   divided by k*k (the order of ATen's CPU kernel: bit-identical to the CPU reference).
+ * Pointers of the four _f32 calls (cgic_grain_merge_f32 above, cgic_avgpool_f32, cgic_decoder_blend_medium_f32 / _fine_f32; they share
+ * the _h calls' kernels and launch plan, csrc/cgic_merge_plan.h, and so their rules):
+ *   - every pointer must be aligned to its 4-byte element: CGIC_ERR_INVALID otherwise (it used to be dereferenced);
+ *   - a thread takes 4 consecutive x with 16-byte accesses (the pools: one output from k-element row loads) where the row width and
+ *     every pointer's alignment allow; a pointer aligned to 4 or 8 bytes only (a view at a storage offset) gets 1 or 2 x per thread
+ *     (the pools: element-wise loads) instead of misaligned wide accesses -- the same bits;
+ *   - out == h is the blends' in-place form; ANY other overlap of out with an input (out on h_medium / h_fine or on a mask, out
+ *     partly inside h, the merge's or the pool's out on an input) is CGIC_ERR_INVALID -- such calls used to compute wrong values
+ *     silently, or to work by accident.
+ * Every check precedes the one launch; not available inside a launch group.
  * ------------------------------------------------------------------------- */
 int cgic_avgpool_f32(const float *x, int64_t planes, int64_t H, int64_t W, int k, float *out, cgic_stream_t stream);
 
@@ -613,7 +624,7 @@ int cgic_decoder_blend_fine_f32(const float *h, const float *h_fine, const int32
  * pool's row-major running sum / (float)(k*k) are the fp32 operations of the _f32 kernels, a half output is rounded once to
  * nearest-even (fp16 overflow: +-Inf).  Bit-identical to the reference's expression on the CPU.  Products and sums, not
  * selects: an Inf or NaN under a zero mask is a NaN.
- * Shapes and masks as the _f32 siblings.  A pointer must be aligned to its own element; wider alignment and a row width
+ * Shapes, masks and kernels as the _f32 siblings (one kernel family, one plan).  A pointer must be aligned to its own element; wider alignment and a row width
  * that is a multiple of 8 let a thread take 8 consecutive x with 16-byte accesses, otherwise 4, 2 or 1 (csrc/cgic_merge_plan.h).
  * `out` may be `h` itself for the two blends when out_dtype == in_dtype (in place); any other overlap of `out` with an input
  * is CGIC_ERR_INVALID.  Every check precedes the one launch; not available inside a launch group.

@@ -1,7 +1,8 @@
-// merge_plan_main.cpp -- prints the launch plan of the half-precision merge / pool / blend calls (csrc/cgic_merge_plan.h) for the
-// cases it is given (no GPU, no library).  A case is 15 numbers, from the arguments or, without arguments, from stdin:
-//   op in_dtype out_dtype B C h w k feat0 feat1 feat2 mask0 mask1 mask2 out
-// (op: 0 merge, 1 pool, 2 medium blend, 3 fine blend; the seven addresses as plain integers, 0 = NULL).
+// merge_plan_main.cpp -- prints the launch plan of the merge / pool / blend calls (csrc/cgic_merge_plan.h) for the cases it is
+// given (no GPU, no library).  A case is 16 numbers, from the arguments or, without arguments, from stdin:
+//   op in_dtype out_dtype B C h w k feat0 feat1 feat2 mask0 mask1 mask2 out entry
+// (op: 0 merge, 1 pool, 2 medium blend, 3 fine blend; the seven addresses as plain integers, 0 = NULL; entry: 0 the _h call,
+// 1 the _f32 call).
 // One line per case: the plan's fields as name=value, or err=<code> and the reason.
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,21 +21,21 @@ int main(int argc, char **argv)
         char buf[64];
         while (scanf("%63s", buf) == 1) tok.push_back(buf);
     }
-    const size_t per_case = 15;
+    const size_t per_case = 16;
     if (tok.empty() || tok.size() % per_case != 0) {
         fprintf(stderr, "merge_plan_main: %zu numbers, expected a multiple of %zu\n", tok.size(), per_case);
         return 2;
     }
     for (size_t at = 0; at < tok.size(); at += per_case) {
         const auto num = [&](int i) { return strtoll(tok[at + i].c_str(), nullptr, 10); };
-        cgic::MergeHalfCall c{};
+        cgic::MergeCall c{};
         c.op = (int)num(0); c.in_dtype = (int)num(1); c.out_dtype = (int)num(2);
         c.B = num(3); c.C = (int)num(4); c.h = num(5); c.w = num(6); c.k = (int)num(7);
         for (int i = 0; i < 3; ++i) { c.feat[i] = (uintptr_t)num(8 + i); c.mask[i] = (uintptr_t)num(11 + i); }
-        c.out = (uintptr_t)num(14);
-        cgic::MergeHalfPlan p;
+        c.out = (uintptr_t)num(14); c.entry = (int)num(15);
+        cgic::MergePlan p;
         const char *why = "";
-        const int rc = cgic::merge_half_plan(c, &p, &why);
+        const int rc = cgic::merge_plan(c, &p, &why);
         if (rc != CGIC_OK) {
             printf("err=%d why=%s\n", rc, why);
             continue;

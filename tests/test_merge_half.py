@@ -1,4 +1,4 @@
-"""GPU: the merge, the pools and the blends on fp16 / bf16 features (csrc/cgic_merge_half.hip, ABI 16) against values computed ON THE
+"""GPU: the merge, the pools and the blends on fp16 / bf16 features (the _h calls of csrc/cgic_merge.hip, ABI 16) against values computed ON THE
 CPU: the reference's own expressions on CPU half tensors for the merge and the blends (they promote to fp32, the masks being
 .float(); `.to(half)` of that where the half output is asked for), torch's CPU avg_pool2d on the half tensor for the pools.
 Everything is compared bit for bit; where the expected value is a NaN, a NaN is expected (payloads are not compared)."""

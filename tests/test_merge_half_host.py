@@ -68,9 +68,28 @@ def test_the_library_refuses_before_it_launches():
     refused(_lib.ERR_INVALID, "decoder_blend_fine: out overlaps an input", "cgic_decoder_blend_fine_h", A, Bm, 1, M0, M1, M2, 1, 3, 8, 8, A, 0, None)
     refused(_lib.ERR_INVALID, "decoder_blend_fine: out overlaps an input", "cgic_decoder_blend_fine_h", A, Bm, 1, M0, M1, M2, 1, 3, 8, 8, Bm, 1, None)
     refused(_lib.ERR_INVALID, "grain_merge: out overlaps an input", "cgic_grain_merge_h", A, Bm, Cm, 2, M0, M1, M2, 1, 3, 8, 8, Cm, 2, None)
+    # the _f32 calls go through the same plan: the texts they have always had ...
+    refused(_lib.ERR_UNSUPPORTED, "avgpool: window 3; the decoder uses 4 and 2 (decoder.py:304-305)", "cgic_avgpool_f32", A, 3, 9, 9, 3, OUT, None)
+    refused(_lib.ERR_INVALID, "avgpool: 8x7 is not a multiple of the window", "cgic_avgpool_f32", A, 3, 8, 7, 2, OUT, None)
+    refused(_lib.ERR_INVALID, "grain_merge: fine grid 6x8 must be positive multiples of 4", "cgic_grain_merge_f32", A, Bm, Cm, M0, M1, M2, 1, 3, 6, 8,
+            OUT, None)
+    refused(_lib.ERR_INVALID, "decoder_blend_medium: medium grid 3x4 (need even height and width)", "cgic_decoder_blend_medium_f32", A, Bm, M0, M1,
+            1, 3, 3, 4, OUT, None)
+    refused(_lib.ERR_INVALID, "decoder_blend_fine: fine grid 8x10 must be positive multiples of 4", "cgic_decoder_blend_fine_f32", A, Bm, M0, M1, M2,
+            1, 3, 8, 10, OUT, None)
+    refused(_lib.ERR_INVALID, "decoder_blend_fine: NULL tensor", "cgic_decoder_blend_fine_f32", A, Bm, M0, M1, None, 1, 3, 8, 8, OUT, None)
+    refused(_lib.ERR_INVALID, "grain_merge: NULL tensor", "cgic_grain_merge_f32", A, None, Cm, M0, M1, M2, 1, 3, 8, 8, OUT, None)
+    refused(_lib.ERR_INVALID, "avgpool: NULL tensor", "cgic_avgpool_f32", A, 3, 8, 8, 2, None, None)
+    # ... and the two that the plan added to them: the pointers' alignment and the half calls' aliasing rule
+    refused(_lib.ERR_INVALID, "decoder_blend_fine: a pointer is not aligned to its 4-byte element", "cgic_decoder_blend_fine_f32", A + 2, Bm, M0, M1,
+            M2, 1, 3, 8, 8, OUT, None)
+    refused(_lib.ERR_INVALID, "decoder_blend_medium: out overlaps an input", "cgic_decoder_blend_medium_f32", A, Bm, M0, M1, 1, 3, 8, 8, Bm, None)
+    refused(_lib.ERR_INVALID, "grain_merge: out overlaps an input", "cgic_grain_merge_f32", A, Bm, Cm, M0, M1, M2, 1, 3, 8, 8, Cm, None)
     # an empty batch asks for nothing: CGIC_OK with NULL tensors, nothing launched
     assert _lib.call("cgic_grain_merge_h", None, None, None, 1, None, None, None, 0, 3, 8, 8, None, 0, None) == _lib.OK
     assert _lib.call("cgic_avgpool_h", None, 2, 0, 8, 8, 4, None, 2, None) == _lib.OK
+    assert _lib.call("cgic_grain_merge_f32", None, None, None, None, None, None, 0, 3, 8, 8, None, None) == _lib.OK
+    assert _lib.call("cgic_avgpool_f32", None, 0, 8, 8, 4, None, None) == _lib.OK
 
 
 # ---------------------------------------------------------------------------- refusals (FakeTensorMode)

@@ -1,5 +1,5 @@
 """The kernels of the reference's training graph and of the decoder's feature path at their edges: the VQ backward
-(csrc/cgic_vq_bwd.hip) and the merge / pool / blend streams (csrc/cgic_merge.hip) against references computed ON THE CPU
+(csrc/cgic_vq_bwd.hip) and the merge / pool / blend streams on fp32 features (csrc/cgic_merge.hip) against references computed ON THE CPU
 (numpy fp32 / fp64, or the reference's own expressions on torch CPU tensors), plus the argument checks of their wrappers.
 
 The VQ backward's codebook gradient is held to a bound DERIVED from the documented scheme (cgic_vq_bwd.hip): every workgroup
@@ -404,7 +404,7 @@ def check_streams(B, C, h, w, mode, seed=0, plant=None):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("B,C,h,w", [(1, 1, 4, 4), (2, 3, 4, 8), (1, 2, 8, 4), (2, 1, 12, 20), (0, 3, 8, 8)])
 def test_streams_small_shapes_in_every_mode(B, C, h, w, mode):
-    """medium grids 2 / 4 / 2 / 10 wide: widths 2 and 10 take decoder_blend_medium2_kernel (1 and 5 threads per row)"""
+    """medium grids 2 / 4 / 2 / 10 wide: widths 2 and 10 take unit 2 (1 and 5 threads per row)"""
     check_streams(B, C, h, w, mode)
 
 
@@ -412,7 +412,7 @@ def test_streams_small_shapes_in_every_mode(B, C, h, w, mode):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("B,C,hh,ww", [(2, 2, 4, 2), (1, 3, 6, 6), (2, 1, 2, 6)])
 def test_medium_blend_on_grids_2_and_6_wide(B, C, hh, ww, mode):
-    """decoder_blend_medium2_kernel with one and three threads per row"""
+    """unit 2 with one and three threads per row"""
     gen = torch.Generator().manual_seed(hh * ww)
     mk = make_masks(mode, B, 2 * hh, 2 * ww)[:2]
     hin, own = randn(gen, B, C, hh, ww), randn(gen, B, C, hh, ww)
@@ -434,7 +434,7 @@ def test_grain_merge_beyond_its_grid_cap():
 @gpu
 @pytest.mark.parametrize("which,w", [("fine", 508), ("medium", 508), ("medium", 510)])
 def test_blends_beyond_the_grid_cap(which, w):
-    """508: decoder_blend_kernel with 127 threads per row; 510: decoder_blend_medium2_kernel with 255"""
+    """508: unit 4 with 127 threads per row; 510: unit 2 with 255"""
     B, C, h = 2, 130, 128
     assert B * C * h * (w // 4) > 16384 * 256
     gen = torch.Generator().manual_seed(w)
@@ -518,6 +518,73 @@ def test_avg_pool_overflow_order_and_subnormal_windows():
         assert ref[0, 0, 1, 0] == tiny and 0 < ref[0, 0, 1, 1] < 1.2e-38             # the CPU reference kept the subnormals
         assert torch.isnan(ref[0, 0, 2, 1]) and torch.isnan(ref[0, 0, 2, 2]) and torch.isfinite(ref[0, 0, 3, 2])
         same_bits(cg.avg_pool(x.cuda(), k), ref)
+
+
+# ---------------------------------------------------------------------------- fp32 pointers that allow only a narrower unit
+def offset_view(t, elements):
+    """t's values in a device tensor whose storage begins `elements` elements before it: a contiguous view at that storage offset"""
+    buf = torch.empty(t.numel() + elements, dtype=t.dtype, device="cuda")
+    v = buf[elements:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.storage_offset() == elements and v.data_ptr() % 16 == (4 * elements) % 16
+    return v
+
+
+def _f32_call(name, tensors, dims, out):
+    """the raw _f32 entry point on exactly these device tensors (no copy, no cast in between)"""
+    from control_gic_amd import _lib
+    _lib.call(name, *(_lib.ptr(t) for t in tensors), *dims, _lib.ptr(out), _lib.current_stream(out.device))
+    return out
+
+
+@gpu
+@pytest.mark.parametrize("elements", [1, 2])
+@pytest.mark.parametrize("mode", ["cmf", "overlap"])
+def test_fp32_tensors_at_a_storage_offset_take_units_2_and_1(mode, elements):
+    """widths that allow 4 floats per thread, one tensor at a time -- each feature, each mask, `out` -- at a pointer aligned to 4
+    bytes (offset 1) or 8 bytes (offset 2) only: the 1- or 2-element unit (the plan: tests/test_merge_plan_host.py), the same bits"""
+    B, C, h, w = 2, 3, 8, 16
+    gen = torch.Generator().manual_seed(10 * elements + MODES.index(mode))
+    mk = make_masks(mode, B, h, w)
+    hc, hm, hf, own = randn(gen, B, C, h // 4, w // 4), randn(gen, B, C, h // 2, w // 2), randn(gen, B, C, h, w), randn(gen, B, C, h, w)
+    own_m = randn(gen, B, C, h // 2, w // 2)
+    calls = [      # entry point, inputs, dims, the CPU expression
+        ("cgic_grain_merge_f32", (hc, hm, hf, *mk), (B, C, h, w), ref_merge(hc, hm, hf, mk)),
+        ("cgic_decoder_blend_fine_f32", (hf, own, *mk), (B, C, h, w), ref_blend_fine(hf, own, mk)),
+        ("cgic_decoder_blend_medium_f32", (hm, own_m, *mk[:2]), (B, C, h // 2, w // 2), ref_blend_medium(hm, own_m, mk[:2])),
+    ]
+    for name, inputs, dims, want in calls:
+        for which in range(len(inputs) + 1):                                             # the last one: out
+            dev = [offset_view(t, elements) if i == which else t.cuda() for i, t in enumerate(inputs)]
+            out = torch.zeros_like(want)
+            out = offset_view(out, elements) if which == len(inputs) else out.cuda()
+            same_bits(_f32_call(name, dev, dims, out), want)
+        if "blend" in name:                                                              # in place: out is h, at the offset with it
+            for which in range(len(inputs)):
+                dev = [offset_view(t, elements) if i == which else t.cuda() for i, t in enumerate(inputs)]
+                same_bits(_f32_call(name, dev, dims, dev[0]), want)
+    for k in (2, 4):
+        want = torch.nn.functional.avg_pool2d(hf, k, k, 0)
+        same_bits(_f32_call("cgic_avgpool_f32", [offset_view(hf, elements)], (B * C, h, w, k), torch.zeros_like(want).cuda()), want)
+        if elements == 1:
+            same_bits(_f32_call("cgic_avgpool_f32", [hf.cuda()], (B * C, h, w, k), offset_view(torch.zeros_like(want), 1)), want)
+
+
+@gpu
+@pytest.mark.parametrize("k", [2, 4])
+def test_fp32_avg_pool_keeps_the_sign_of_a_negative_average_that_underflows(k):
+    """a window of zeros and one -2^-149: the running sum is -2^-149 and the quotient by k*k rounds to -0.0, which is what the kernel
+    stores; the all-zero window next to it gives +0.0.  ATen's CPU kernel returns +0 in the first place (it adds the average onto a
+    zeroed output element, and 0 + -0 is +0); the kernel's value is kept on purpose, as it has been since the fp32 pool was
+    written (the half pools store +0: tests/test_merge_half.py)"""
+    x = torch.zeros(1, 1, 2 * k, 2 * k)
+    x[0, 0, 1, 1] = -2.0 ** -149
+    want = np.zeros((1, 1, 2, 2), F32)
+    with np.errstate(under="ignore"):
+        want[0, 0, 0, 0] = np.float32(-2.0 ** -149) / np.float32(k * k)
+    assert want.view(np.uint32).reshape(-1).tolist() == [0x80000000, 0, 0, 0]
+    got = cg.avg_pool(x.cuda(), k).cpu().numpy()
+    assert got.dtype == F32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 # ---------------------------------------------------------------------------- autograd at the edges (fp64 CPU autograd = the reference)

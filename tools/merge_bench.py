@@ -8,7 +8,7 @@ bf16 and fp16, with the fp32 and with the half result:
   (a) the route before ABI 16, written out here: `.float()` of every feature, the _f32 entry point, `.to(half)` where a half
       result is wanted;
   (b) the half call (control_gic_amd.merge.*: one launch, no cast);
-  (k) the _f32 kernel alone on features that are fp32 already (the fp32 siblings' rate at the same shape).
+  (k) the _f32 call alone on features that are fp32 already (the same kernel family on fp32 elements, at the same shape).
 The three run in ONE process and alternate round by round; a round is HIP events around --calls calls -- issued from Python (`ms`),
 and again as one captured graph of the same calls per route (`graph_ms`: no host work between the launches; the same buffers every
 call, so a tensor set that fits the last-level cache is read from there).  Per route: the median, the lowest and the highest
