@@ -167,6 +167,10 @@ PROTOTYPES = {
     "cgic_avgpool_h": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _int, _vp]),
     "cgic_decoder_blend_medium_h": (_int, [_vp, _vp, _int, _vp, _vp, _i64, _int, _i64, _i64, _vp, _int, _vp]),
     "cgic_decoder_blend_fine_h": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _i64, _int, _i64, _i64, _vp, _int, _vp]),
+    "cgic_spatial_norm": (_int, [_vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int,
+                                 _vp, _sz, _vp]),
+    "cgic_spatial_norm_workspace_bytes": (_sz, [_int, _i64, _int, _i64, _i64, _int]),
+    "cgic_spatial_norm_one_launch": (_int, [_int, _i64, _int, _i64, _i64, _int]),
     "cgic_embedding_gather_f32": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp]),
     "cgic_rate_table_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int]),
     "cgic_rate_table": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, C.POINTER(_f64), C.POINTER(_f64), _int, _px, _vp, _vp,

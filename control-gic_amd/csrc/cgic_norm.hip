@@ -1,0 +1,416 @@
+// cgic_norm.hip -- the decoder's SpatialNorm (decoder.py:34-53) as one pass over the features, on fp32, fp16 and bf16:
+//     zq    = interpolate(zq, size=f.shape[-2:], mode="nearest")
+//     new_f = GroupNorm(groups, eps, affine)(f) * conv_y(zq) + conv_b(zq)          conv_y, conv_b: 1x1, 4 -> C
+// and, on request, the swish that ResnetBlock puts directly behind it (decoder.py:29-31).  torch runs this as six element-wise
+// passes over [B,C,H,W] (two conv outputs written in full from a 4-channel input, GroupNorm, a multiply, an add, the swish); here
+// the features are read once or twice and written once, and zq (4 channels, at most a few KB per image row) comes out of the caches.
+//
+// Values.  A group (b, g) is one contiguous span of (C / groups) * H * W elements.  Its mean and biased variance are accumulated in
+// float64 as sums of x - K and (x - K)^2, K the span's first element (so the variance does not cancel), rstd = 1 / sqrt(var + eps);
+// mean and rstd are each rounded once to fp32.  Per element, in fp32 and without contraction (-ffp-contract=off):
+//     n = ((x - mean) * rstd) * gamma[c] + beta[c]
+//     y = by[c] + sum_k wy[c,k] * zq[b,k,sy,sx]    (k = 0..3 in order; b likewise from wb, bb)
+//     v = n * y + b;    with swish  v / (1 + exp(-v))
+// Half features are upcast exactly; a half output is the fp32 value rounded once to nearest-even.
+//
+// Two forms, chosen by cgic_norm_plan.h (which also holds every check of the call); no workgroup ever waits for another:
+//   norm_one_kernel                       one workgroup per span: the span goes to LDS in the feature type while it is summed, then
+//                                         the waves apply from LDS, each wave one channel (or a piece of one) at a time;
+//   norm_stats_kernel + norm_apply_kernel ordered by the stream: a (span, chunk) grid writes one (sum, sum of squares) pair of
+//                                         doubles per chunk (and K per span) to the caller's workspace; the apply workgroups add
+//                                         their span's partials in chunk order, so the result does not depend on scheduling.
+// A workgroup's (the one-launch form: a wave's) channel is uniform: its twelve parameters are scalar loads.  A thread takes U
+// consecutive elements of a row: 16 bytes of the feature type where the plan allows, else fewer.  Where x is at ratio 1 it reads
+// its pixels of each zq channel as 16-byte vectors, all issued before the first is used; otherwise the four zq values of a pixel
+// are loaded once and serve every x of the thread that falls on that pixel.  The index divisions (by the row width and the two ratios) are multiplications by the plan's magic numbers.
+// Every element is read before it is written in both forms, so out may be f.
+#include "cgic_common.h"
+#include "cgic_norm_plan.h"
+
+namespace cgic {
+namespace norm {
+
+// a feature type: its raw element, the exact upcast and, for a half, the rounding of a fp32 value to it
+struct F32 {
+    using raw = uint32_t;
+    static __device__ __forceinline__ float up(uint32_t v) { return __uint_as_float(v); }
+};
+struct F16 {
+    using raw = uint16_t;
+    static __device__ __forceinline__ float up(uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+    static __device__ __forceinline__ uint16_t down(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+};
+struct BF16 {
+    using raw = uint16_t;
+    static __device__ __forceinline__ float up(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+    static __device__ __forceinline__ uint16_t down(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
+};
+
+template <int BYTES> struct RawOf;
+template <> struct RawOf<2> { using type = uint16_t; };
+template <> struct RawOf<4> { using type = uint32_t; };
+template <> struct RawOf<8> { using type = uint2; };
+template <> struct RawOf<16> { using type = uint4; };
+
+// N consecutive elements as ONE access of their size
+template <class E, int N>
+__device__ __forceinline__ void load_n(const E *p, E (&v)[N])
+{
+    using R = typename RawOf<sizeof(E) * N>::type;
+    const R r = *reinterpret_cast<const R *>(p);
+    __builtin_memcpy(v, &r, sizeof(R));
+}
+template <class E, int N>
+__device__ __forceinline__ void store_n(E *p, const E (&v)[N])
+{
+    using R = typename RawOf<sizeof(E) * N>::type;
+    R r;
+    __builtin_memcpy(&r, v, sizeof(R));
+    *reinterpret_cast<R *>(p) = r;
+}
+// N results to out[idx ...]: rounded to T's half type (HOUT), or as they are (8 floats: two 16-byte stores)
+template <class T, bool HOUT, int N>
+__device__ __forceinline__ void store_out(void *out, int64_t idx, const float (&o)[N])
+{
+    if constexpr (HOUT) {
+        typename T::raw v[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = T::down(o[i]);
+        store_n<typename T::raw, N>(reinterpret_cast<typename T::raw *>(out) + idx, v);
+    } else if constexpr (N == 8) {
+        float4 *dst = reinterpret_cast<float4 *>(reinterpret_cast<float *>(out) + idx);
+        dst[0] = make_float4(o[0], o[1], o[2], o[3]);
+        dst[1] = make_float4(o[4], o[5], o[6], o[7]);
+    } else {
+        store_n<float, N>(reinterpret_cast<float *>(out) + idx, o);
+    }
+}
+
+// U consecutive floats of zq as one access (8: two)
+template <int U>
+__device__ __forceinline__ void load_zq(const float *p, float (&z)[U])
+{
+    if constexpr (U == 8) {
+        float lo[4], hi[4];
+        load_n<float, 4>(p, lo);
+        load_n<float, 4>(p + 4, hi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { z[j] = lo[j]; z[4 + j] = hi[j]; }
+    } else {
+        load_n<float, U>(p, z);
+    }
+}
+
+// n / d by the plan's magic multiplier (exact for the plan's dividends), or plainly where the plan has none
+__device__ __forceinline__ unsigned fdiv(unsigned n, unsigned m, unsigned d) { return m ? __umulhi(n, m) : d == 1 ? n : n / d; }
+
+// what the kernels know of a call besides the features
+struct Geom {
+    int C, cpg, groups;             // channels, channels per group, groups
+    int H, W, hq, wq;
+    int ymul, ydiv, xmul, xdiv;     // the nearest index: src = dst * mul / div (one of the two is 1)
+    unsigned mg_w, mg_y, mg_x;      // magic multipliers of the divisions by W, ydiv, xdiv (0: divide)
+    int zq_vec;                     // x at ratio 1 and zq aligned: a thread's pixels of a channel are one access
+    int swish;
+    double eps;
+    const float *zq, *gamma, *beta, *wy, *by, *wb, *bb;
+};
+
+// the twelve parameters of a channel; c is uniform where this is called, so these are scalar loads
+struct Chan {
+    float gamma, beta, by, bb, wy[kNormZq], wb[kNormZq];
+};
+__device__ __forceinline__ Chan load_chan(const Geom &g, int c)
+{
+    Chan w;
+    w.gamma = g.gamma[c]; w.beta = g.beta[c]; w.by = g.by[c]; w.bb = g.bb[c];
+#pragma unroll
+    for (int k = 0; k < kNormZq; ++k) { w.wy[k] = g.wy[c * kNormZq + k]; w.wb[k] = g.wb[c * kNormZq + k]; }
+    return w;
+}
+
+// mean and rstd of a span from its two sums about K, each rounded once to fp32.  A NaN or an Inf in the span makes both sums
+// non-finite and the variance a NaN: the whole span comes out NaN, as in the reference.
+__device__ __forceinline__ void finish_stats(double K, double s1, double s2, double n, double eps, float *mean, float *rstd)
+{
+    const double m = s1 / n;
+    double var = s2 / n - m * m;
+    if (var < 0.0) var = 0.0;                       // (a NaN stays a NaN)
+    *mean = (float)(K + m);
+    *rstd = (float)(1.0 / sqrt(var + eps));
+}
+
+// the two sums of a thread's elements about K
+template <class T, int U>
+__device__ __forceinline__ void accumulate(const typename T::raw (&v)[U], double K, double *s1, double *s2)
+{
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const double d = (double)T::up(v[j]) - K;
+        *s1 += d;
+        *s2 += d * d;
+    }
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;                                       // (lane 0 holds the wave's sum)
+}
+
+// units [first, end) of one channel's plane, `step` apart: src is the plane (in global memory or in LDS), out_plane the index of
+// its first element in out, zq_b the image's zq
+template <class T, bool HOUT, int U>
+__device__ __forceinline__ void apply_units(const typename T::raw *src, void *out, int64_t out_plane, unsigned first, unsigned end,
+                                            unsigned step, const Geom &g, const float *zq_b, const Chan &w, float mean, float rstd)
+{
+    const unsigned W = (unsigned)g.W, plane_q = (unsigned)g.hq * (unsigned)g.wq;
+    for (unsigned i = first; i < end; i += step) {
+        const unsigned e = i * U;
+        const unsigned y = fdiv(e, g.mg_w, W), x = e - y * W;
+        const unsigned sy = fdiv(y * (unsigned)g.ymul, g.mg_y, (unsigned)g.ydiv);
+        typename T::raw v[U];
+        load_n<typename T::raw, U>(src + e, v);
+        const float *zrow = zq_b + (size_t)sy * (unsigned)g.wq;
+        float o[U];
+        const auto element = [&](int j, float yv, float bv) {
+            const float n = ((T::up(v[j]) - mean) * rstd) * w.gamma + w.beta;
+            float val = n * yv + bv;
+            if (g.swish) val = val / (1.0f + expf(-val));
+            o[j] = val;
+        };
+        if (g.zq_vec) {
+            // x at ratio 1: the thread's U consecutive pixels of each zq channel as one access, all issued before the first is used
+            float z[kNormZq][U];
+#pragma unroll
+            for (int k = 0; k < kNormZq; ++k) load_zq<U>(zrow + (size_t)k * plane_q + x, z[k]);
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                float yv = w.by, bv = w.bb;
+#pragma unroll
+                for (int k = 0; k < kNormZq; ++k) {
+                    yv = yv + w.wy[k] * z[k][j];
+                    bv = bv + w.wb[k] * z[k][j];
+                }
+                element(j, yv, bv);
+            }
+        } else {
+            const unsigned acc = x * (unsigned)g.xmul;
+            unsigned sx = fdiv(acc, g.mg_x, (unsigned)g.xdiv), rem = acc - sx * (unsigned)g.xdiv;
+            float yv = 0.f, bv = 0.f;
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                if (j == 0 || rem == 0) {           // a new zq pixel: its four values once, for every x that falls on it
+                    yv = w.by;
+                    bv = w.bb;
+#pragma unroll
+                    for (int k = 0; k < kNormZq; ++k) {
+                        const float z = zrow[(size_t)k * plane_q + sx];
+                        yv = yv + w.wy[k] * z;
+                        bv = bv + w.wb[k] * z;
+                    }
+                }
+                element(j, yv, bv);
+                // the next x: sub-sampling (xdiv == 1) moves on by xmul pixels, up-sampling by one pixel every xdiv steps
+                if (g.xdiv == 1) {
+                    sx += (unsigned)g.xmul;
+                } else if (++rem == (unsigned)g.xdiv) {
+                    rem = 0;
+                    ++sx;
+                }
+            }
+        }
+        store_out<T, HOUT, U>(out, out_plane + e, o);
+    }
+}
+
+// ---- one launch: one workgroup per span
+template <class T, bool HOUT, int U>
+__global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typename T::raw *f, Geom g, unsigned span_bytes16, void *out)
+{
+    using E = typename T::raw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char norm_lds[];
+    E *sp = reinterpret_cast<E *>(norm_lds);
+    double *part = reinterpret_cast<double *>(norm_lds + span_bytes16);
+    const int64_t spn = blockIdx.x;
+    const unsigned plane = (unsigned)g.H * (unsigned)g.W, span = (unsigned)g.cpg * plane, units = span / U;
+    const E *src = f + spn * (int64_t)span;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id(), nw = (int)(blockDim.x >> 6);
+    // the span to LDS, summed on the way
+    const double K = (double)T::up(src[0]);
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll 4
+    for (unsigned i = threadIdx.x; i < units; i += blockDim.x) {
+        E v[U];
+        load_n<E, U>(src + (size_t)i * U, v);
+        store_n<E, U>(sp + (size_t)i * U, v);
+        accumulate<T, U>(v, K, &s1, &s2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (lane == 0) { part[2 * wave] = s1; part[2 * wave + 1] = s2; }
+    __syncthreads();                                // (the span and the waves' sums are in LDS; global f is not read again)
+    double t1 = 0.0, t2 = 0.0;
+    for (int k = 0; k < nw; ++k) { t1 += part[2 * k]; t2 += part[2 * k + 1]; }
+    float mean, rstd;
+    finish_stats(K, t1, t2, (double)span, g.eps, &mean, &rstd);
+    // apply from LDS: a wave takes one channel, or 256 units of one, at a time
+    const int64_t b = spn / g.groups;
+    const int grp = (int)(spn - b * g.groups);
+    const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
+    const unsigned plane_units = plane / U, seg_units = 4 * kWave;
+    const unsigned segs = (plane_units + seg_units - 1) / seg_units, items = (unsigned)g.cpg * segs;
+    for (unsigned it = (unsigned)wave; it < items; it += (unsigned)nw) {
+        const unsigned cl = it / segs, sg = it - cl * segs;
+        const Chan w = load_chan(g, grp * g.cpg + (int)cl);
+        const unsigned first = sg * seg_units, last = first + seg_units < plane_units ? first + seg_units : plane_units;
+        apply_units<T, HOUT, U>(sp + (size_t)cl * plane, out, spn * (int64_t)span + (int64_t)cl * plane, first + (unsigned)lane, last, kWave,
+                                g, zq_b, w, mean, rstd);
+    }
+}
+
+// ---- two launches.  The workspace: spans * chunks pairs (sum, sum of squares), then one K per span
+template <class T, int U>
+__global__ __launch_bounds__(kNormThreads) void norm_stats_kernel(const typename T::raw *f, unsigned units, int chunks, unsigned chunk_units,
+                                                                  int64_t spans, double *ws)
+{
+    using E = typename T::raw;
+    __shared__ double part[2 * (kNormThreads / kWave)];
+    const int64_t spn = blockIdx.x / (unsigned)chunks;
+    const unsigned ch = (unsigned)(blockIdx.x - spn * chunks);
+    const E *src = f + spn * (int64_t)units * U;
+    const double K = (double)T::up(src[0]);
+    const unsigned first = ch * chunk_units;
+    const unsigned last = first + chunk_units < units ? first + chunk_units : units;
+    double s1 = 0.0, s2 = 0.0;
+    for (unsigned i = first + threadIdx.x; i < last; i += blockDim.x) {
+        E v[U];
+        load_n<E, U>(src + (size_t)i * U, v);
+        accumulate<T, U>(v, K, &s1, &s2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const int wave = (int)(threadIdx.x >> 6);
+    if (lane_id() == 0) { part[2 * wave] = s1; part[2 * wave + 1] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int k = 0; k < kNormThreads / kWave; ++k) { t1 += part[2 * k]; t2 += part[2 * k + 1]; }
+        double *dst = ws + ((int64_t)blockIdx.x) * 2;
+        dst[0] = t1;
+        dst[1] = t2;
+        if (ch == 0) ws[spans * chunks * 2 + spn] = K;
+    }
+}
+
+template <class T, bool HOUT, int U>
+__global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename T::raw *f, Geom g, const double *ws, int chunks, int64_t spans,
+                                                                  int64_t items, unsigned parts, void *out)
+{
+    const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_units = plane / U;
+    const double n = (double)g.cpg * (double)plane;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int64_t bc = it / parts;
+        const unsigned part = (unsigned)(it - bc * parts);
+        const int64_t b = bc / g.C;
+        const int c = (int)(bc - b * g.C);
+        const int64_t spn = b * g.groups + c / g.cpg;
+        // the span's partials in chunk order (uniform: every thread adds the same numbers in the same order)
+        const double *p = ws + spn * chunks * 2;
+        double t1 = 0.0, t2 = 0.0;
+        for (int k = 0; k < chunks; ++k) { t1 += p[2 * k]; t2 += p[2 * k + 1]; }
+        float mean, rstd;
+        finish_stats(ws[spans * chunks * 2 + spn], t1, t2, n, g.eps, &mean, &rstd);
+        const Chan w = load_chan(g, c);
+        const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
+        const unsigned first = part * (unsigned)kNormPartUnits;
+        const unsigned last = first + (unsigned)kNormPartUnits < plane_units ? first + (unsigned)kNormPartUnits : plane_units;
+        apply_units<T, HOUT, U>(f + bc * (int64_t)plane, out, bc * (int64_t)plane, first + threadIdx.x, last, blockDim.x, g, zq_b, w, mean, rstd);
+    }
+}
+
+// ---- the launches: the plan's form and unit and the call's type pair pick the instantiation
+template <class T, bool HOUT, int U>
+static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, hipStream_t s)
+{
+    using E = const typename T::raw *;
+    if (p.form == 1) {
+        const auto kernel = norm_one_kernel<T, HOUT, U>;
+        const int rc = ensure_lds_above_48k((const void *)kernel, p.lds_bytes);
+        if (rc) return rc;
+        const unsigned span_bytes16 = (unsigned)(p.lds_bytes - 2 * sizeof(double) * (size_t)(kNormOneThreads / kWave));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid_one), dim3(p.threads_one), p.lds_bytes, s, (E)c.f, g, span_bytes16, (void *)c.out);
+        return launch_check("norm_one_kernel");
+    }
+    const unsigned units = (unsigned)(p.span / U);
+    hipLaunchKernelGGL((norm_stats_kernel<T, U>), dim3((unsigned)p.grid_stats), dim3(p.threads), 0, s, (E)c.f, units, p.chunks,
+                       (unsigned)p.chunk_units, p.spans, (double *)c.workspace);
+    int rc = launch_check("norm_stats_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL((norm_apply_kernel<T, HOUT, U>), dim3((unsigned)p.grid_apply), dim3(p.threads), 0, s, (E)c.f, g,
+                       (const double *)c.workspace, p.chunks, p.spans, c.B * c.C * p.parts, (unsigned)p.parts, (void *)c.out);
+    return launch_check("norm_apply_kernel");
+}
+
+template <class T, bool HOUT>
+static int launch_typed(const NormCall &c, const NormPlan &p, const Geom &g, hipStream_t s)
+{
+    if constexpr (sizeof(typename T::raw) == 2)
+        if (p.unit == 8) return launch_unit<T, HOUT, 8>(c, p, g, s);
+    switch (p.unit) {
+    case 4: return launch_unit<T, HOUT, 4>(c, p, g, s);
+    case 2: return launch_unit<T, HOUT, 2>(c, p, g, s);
+    default: return launch_unit<T, HOUT, 1>(c, p, g, s);
+    }
+}
+
+}  // namespace norm
+}  // namespace cgic
+
+using namespace cgic;
+
+extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
+                                 int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy, const float *by,
+                                 const float *wb, const float *bb, int swish, void *out, int out_dtype, void *workspace,
+                                 size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_spatial_norm");
+    NormCall c{};
+    c.in_dtype = in_dtype; c.out_dtype = out_dtype; c.B = B; c.C = C; c.H = H; c.W = W; c.hq = hq; c.wq = wq; c.groups = groups;
+    c.f = (uintptr_t)f; c.zq = (uintptr_t)zq; c.gn_weight = (uintptr_t)gn_weight; c.gn_bias = (uintptr_t)gn_bias;
+    c.wy = (uintptr_t)wy; c.by = (uintptr_t)by; c.wb = (uintptr_t)wb; c.bb = (uintptr_t)bb; c.out = (uintptr_t)out;
+    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes;
+    NormPlan p;
+    const char *why = "";
+    const int rc = norm_plan(c, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+    CGIC_REQUIRE(eps >= 0.0, CGIC_ERR_INVALID, "spatial_norm: eps %g", eps);
+    if (p.form == 0) return CGIC_OK;
+    norm::Geom g{};
+    g.C = C; g.groups = groups; g.cpg = C / groups; g.H = (int)H; g.W = (int)W; g.hq = (int)hq; g.wq = (int)wq;
+    g.ymul = p.ymul; g.ydiv = p.ydiv; g.xmul = p.xmul; g.xdiv = p.xdiv; g.mg_w = p.mg_w; g.mg_y = p.mg_y; g.mg_x = p.mg_x; g.zq_vec = p.zq_vec ? 1 : 0;
+    g.swish = swish ? 1 : 0; g.eps = eps;
+    g.zq = zq; g.gamma = gn_weight; g.beta = gn_bias; g.wy = wy; g.by = by; g.wb = wb; g.bb = bb;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool hout = out_dtype != CGIC_DT_F32;
+    if (in_dtype == CGIC_DT_F32) return norm::launch_typed<norm::F32, false>(c, p, g, s);
+    if (in_dtype == CGIC_DT_F16) return hout ? norm::launch_typed<norm::F16, true>(c, p, g, s) : norm::launch_typed<norm::F16, false>(c, p, g, s);
+    return hout ? norm::launch_typed<norm::BF16, true>(c, p, g, s) : norm::launch_typed<norm::BF16, false>(c, p, g, s);
+}
+
+extern "C" size_t cgic_spatial_norm_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)
+{
+    NormPlan p;
+    const char *why = "";
+    return norm_form(in_dtype, B, C, H, W, groups, &p, &why) == CGIC_OK ? p.workspace_needed : 0;
+}
+
+extern "C" int cgic_spatial_norm_one_launch(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)
+{
+    NormPlan p;
+    const char *why = "";
+    const int rc = norm_form(in_dtype, B, C, H, W, groups, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+    return p.form == 1 ? 1 : 0;
+}

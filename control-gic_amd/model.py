@@ -12,6 +12,7 @@ import torch
 
 from . import draw as _draw
 from . import merge as _merge
+from . import norm as _norm
 from . import rate as _rate
 from .codec import GrainCodec
 from .entropy import Entropy
@@ -162,7 +163,7 @@ class AvgPool(torch.nn.Module):
         return torch.nn.functional.avg_pool2d(x, self.k, self.k, 0)
 
 
-def install(model, per_image=False, fuse_convs=True, patch_pools=True):
+def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False):
     """swap VectorQuantize2 / Entropy / router target / compress of a reference CGIC instance in place.
     patch_pools: the decoder's two average pools in front of its masked blends (decoder.avgpool_layer1 / _layer2,
     decoder.py:304-305,366-367) become control_gic_amd.model.AvgPool -- they are modules, so they can be swapped.  The three
@@ -173,7 +174,11 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
     fuse_convs: move quant_conv into the VQ kernel and post_quant_conv into the decode-side gather (under no_grad).  The
     hand-off is explicit: under no_grad `model.quant_conv(h)` returns a quantize.PendingQuantConv (its input, tagged) that
     `model.quantize` convolves inside its kernel; used anywhere else it behaves as the convolved latent, and a latent that
-    reaches `model.quantize` as an ordinary tensor is quantised as it is."""
+    reaches `model.quantize` as an ordinary tensor is quantised as it is.
+    patch_norms: every module with the shape of the reference's SpatialNorm (decoder.py:34-53: norm_layer, 1x1 conv_y / conv_b,
+    add_conv) becomes control_gic_amd.norm.SpatialNorm on the same parameters (csrc/cgic_norm.hip under no_grad; torch's expression
+    when a gradient is needed).  Off by default, unlike patch_pools: the pools are bit-identical to torch, a normalisation agrees
+    with torch's only within rounding, and the default install() keeps producing exactly what it produced before."""
     old = model.quantize
     dev = old.embedding.weight.device
     q = VectorQuantize2(old.n_e, old.e_dim, beta=old.beta, legacy=getattr(old, "legacy", True))
@@ -199,6 +204,8 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True):
             m = getattr(dec, name, None)
             if isinstance(m, torch.nn.AvgPool2d) and m.kernel_size in (k, (k, k)) and m.stride in (k, (k, k)) and m.padding in (0, (0, 0)):
                 setattr(dec, name, AvgPool(k))
+    if patch_norms:
+        _norm.patch_norms(model)
     model.compress = types.MethodType(compress, model)
     model.compress_batch = types.MethodType(compress_batch, model)
     model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 16
+#define CGIC_ABI_VERSION 17
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -646,6 +646,36 @@ int cgic_decoder_blend_medium_h(const void *h, const void *h_medium, int in_dtyp
 int cgic_decoder_blend_fine_h(const void *h, const void *h_fine, int in_dtype, const int32_t *mask_c, const int32_t *mask_m,
                               const int32_t *mask_f, int64_t B, int C, int64_t hh, int64_t ww, void *out, int out_dtype,
                               cgic_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The decoder's SpatialNorm (ABI 17) -- CGIC/modules/vqvae/decoder.py:34-53, and on request the swish behind it (:29-31):
+ *     zq = interpolate(zq, size=f.shape[-2:], mode="nearest");  new_f = GroupNorm(groups, eps, affine)(f) * conv_y(zq) + conv_b(zq)
+ * as one pass over the features (csrc/cgic_norm.hip; every check and the launch plan: csrc/cgic_norm_plan.h).
+ *   f          device [B, C, H, W] of in_dtype (CGIC_DT_F32, CGIC_DT_F16 or CGIC_DT_BF16), contiguous
+ *   zq         device [B, 4, hq, wq] fp32.  Each axis at an integer ratio of the features', up-sampled (H % hq == 0: source row
+ *              y / (H / hq)) or sub-sampled (hq % H == 0: source row y * (hq / H)), the two axes independently: torch's "nearest" at
+ *              these ratios.  Any other ratio is CGIC_ERR_UNSUPPORTED.
+ *   groups, eps, gn_weight, gn_bias    the GroupNorm: C % groups == 0; weight and bias device fp32 [C]
+ *   wy, by, wb, bb    conv_y and conv_b: device fp32 [C, 4] (the 1x1 conv weight's own memory) and [C]
+ *   swish      != 0: x * sigmoid(x) of the result, as v / (1 + exp(-v))
+ *   out        device [B, C, H, W] of out_dtype: CGIC_DT_F32, or in_dtype (the fp32 value rounded once to nearest-even).  May be f
+ *              itself when the types are equal (in place); any other overlap of out with an input is CGIC_ERR_INVALID.
+ *   workspace  device, cgic_spatial_norm_workspace_bytes(...) bytes, 8-byte aligned (NULL where that is 0)
+ * Values: mean and biased variance of a group in float64 about the group's first element, each of mean and rstd rounded once to
+ * fp32; then per element in fp32, without contraction: n = ((x - mean) * rstd) * gamma + beta, y = by + sum_k wy[k] * zq_k (k in
+ * order), b likewise, v = n * y + b.  A NaN or Inf anywhere in a group makes that group's output NaN throughout, as in the reference.
+ * Deterministic: one launch (one workgroup per group) where a group fits a workgroup's LDS budget and the batch has groups enough
+ * to fill the chip, otherwise two launches ordered by the stream whose partial sums are added in a fixed order.
+ * cgic_spatial_norm_one_launch says which: 1, 0, or CGIC_ERR_* for a shape the call refuses.  A pointer must be aligned to its own
+ * element; wider alignment and a row width that is a multiple of 8 (fp32: 4) give 16-byte accesses.  Every check precedes the
+ * first launch; not available inside a launch group.
+ * ------------------------------------------------------------------------- */
+int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
+                      int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy, const float *by,
+                      const float *wb, const float *bb, int swish, void *out, int out_dtype, void *workspace,
+                      size_t workspace_bytes, cgic_stream_t stream);
+size_t cgic_spatial_norm_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
+int cgic_spatial_norm_one_launch(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
 
 /* embedding gather on its own (model.py:121,391-392): out[b, c, p] = codebook[ind[b, p], c] */
 int cgic_embedding_gather_f32(const int64_t *ind, int64_t B, int64_t hw, const float *codebook, int K,
