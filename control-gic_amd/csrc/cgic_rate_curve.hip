@@ -11,10 +11,13 @@
 //
 // One launch, one workgroup per image, everything in LDS:
 //   1. sort the image's e16 (bitonic, in place), take the coarse threshold sorted[k_c - 1]; sum the coarse stream
-//   2. one 64-bit word per 8x8 patch: the entropy's bit pattern (non-negative floats order as unsigned integers) above its
-//      two payloads; coarse patches: 0.  Bitonic sort in place
+//   2. one 64-bit word per 8x8 patch: an order-preserving key of the medium list's element (entropy_key: any float, NaN last
+//      like torch.sort, -0 with +0) above its two payloads; coarse patches: the key of the fp32 product e8 * 0 -- a zero, or NaN
+//      under a NaN or an infinite entropy -- and no payload.  Bitonic sort in place
 //   3. inclusive scan of both payloads in sorted order
 //   4. every K: a binary search for cnt(K), two prefix reads, five sizes out
+// The comparisons are the router's on every float (cgic_router_dev.h: f2key, float '<'): nothing is below a NaN threshold, a NaN
+// is below nothing, the zeros of either sign are equal, and the gated zeros count as medium-list elements below t only when t > 0.
 //
 // cgic_rate_curve_tiles (section I, ABI 11) runs the same steps 1-3 (curve_sort_scan: ONE body for both kernels) for T tiles of
 // mixed shapes, one workgroup per tile, its shape and offsets read from a descriptor; step 4 answers the M requested ranks of the
@@ -44,11 +47,22 @@ struct RateCurveArgs {
     int32_t *summary;                                // [B, 4]: coarse patches, coarse threshold (bit pattern), medium / fine bits of all non-coarse patches
 };
 
-// finite, non-negative floats order as their bit patterns; -0.0 is 0.0
+// Order-preserving key of any float: key(a) < key(b) == (a < b) for every pair without a NaN; -0.0 is 0.0 (they compare equal), every
+// NaN is the largest key (torch.sort puts NaN last).  Key 0 would be a negative NaN: no element has it, so nothing is below 0.
+constexpr unsigned int kKeyNaN = 0xFFFFFFFFu, kKeyZero = 0x80000000u;
 __device__ __forceinline__ unsigned int entropy_key(float e)
 {
-    return e == 0.0f ? 0u : __float_as_uint(e);
+    if (e != e) return kKeyNaN;
+    const unsigned int u = __float_as_uint(e);
+    return (u << 1) == 0u ? kKeyZero : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// the fp32 bit pattern of a key's float (NaN: the quiet NaN; key 0 -- no threshold -- gives 0)
+__device__ __forceinline__ unsigned int entropy_key_bits(unsigned int k)
+{
+    return k == kKeyNaN ? 0x7FC00000u : k == 0u ? 0u : (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+}
+// float '<' on keys: a NaN threshold has nothing below it
+__device__ __forceinline__ bool key_below(unsigned int k, unsigned int t) { return t != kKeyNaN && k < t; }
 
 __device__ __forceinline__ void cmp_swap(unsigned long long *a, int lo, int hi)
 {
@@ -110,7 +124,7 @@ struct CurveSorted {
     const unsigned long long *kv;
     const unsigned int *sf;
     int n8;
-    unsigned int ncoarse, thr, total_m, total_f, first_bad_m, last_bad_f;
+    unsigned int ncoarse, gzeros, thr, total_m, total_f, first_bad_m, last_bad_f;      // gzeros: coarse 8x8 patches whose product e8 * 0 is a zero
     int32_t size_c, size_mc, size_mm;
 };
 
@@ -120,7 +134,7 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
                                                        unsigned char *dyn)
 {
     __shared__ unsigned long long scan_tmp[kCurveThreads / kWave + 1];
-    __shared__ unsigned int sh_thr, sh_ncoarse, sh_cbits, sh_cbad, sh_first_bad_m, sh_last_bad_f;
+    __shared__ unsigned int sh_thr, sh_ncoarse, sh_gzeros, sh_cbits, sh_cbad, sh_first_bad_m, sh_last_bad_f;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n16 = c.h16 * c.w16, n8 = 4 * n16, w8 = 2 * c.w16, w4 = 4 * c.w16;
     unsigned long long *kv = reinterpret_cast<unsigned long long *>(dyn);        // [n8] key << 32 | payload
@@ -132,7 +146,7 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
     if (staged)
         for (int i = tid; i < nsym; i += nt) slen[i] = glen[i];
     const int32_t *len = staged ? slen : glen;
-    if (tid == 0) { sh_thr = 0; sh_ncoarse = 0; sh_cbits = 0; sh_cbad = 0; sh_first_bad_m = 0xFFFFFFFFu; sh_last_bad_f = 0; }
+    if (tid == 0) { sh_thr = 0; sh_ncoarse = 0; sh_gzeros = 0; sh_cbits = 0; sh_cbad = 0; sh_first_bad_m = 0xFFFFFFFFu; sh_last_bad_f = 0; }
 
     // ---- 1. the coarse threshold s16[k_c - 1] (k_c == 0: nothing is below the smallest, RouterTriple.py:24-25) and the coarse stream
     if (c.k_c > 0) {
@@ -146,7 +160,7 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
     {
         unsigned int bits = 0, cnt = 0, bad = 0;
         for (int i = tid; i < n16; i += nt) {
-            if (entropy_key(e16[i]) < thr) {
+            if (key_below(entropy_key(e16[i]), thr)) {
                 const int64_t s = ind_c[i];
                 if (s < 0 || s >= nsym) bad = 1;
                 else bits += (unsigned int)len[s];
@@ -161,10 +175,15 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
     __syncthreads();                                 // (also: the sorted e16 keys are dead, the words may be written)
 
     // ---- 2. one word per 8x8 patch: key | medium bad, fine bad, len[ind_m] (14 bits), the four len[ind_f] (16 bits)
+    unsigned int gz = 0;
     for (int p = tid; p < n8; p += nt) {
         const int y = p / w8, x = p - y * w8;
-        unsigned long long word = 0;                 // a coarse patch: the zero of e8 * (1 - gate), no symbols
-        if (!(entropy_key(e16[(y >> 1) * c.w16 + (x >> 1)]) < thr)) {
+        // a coarse patch: the fp32 product e8 * (1 - gate) as the reference forms it (RouterTriple.py:27), no symbols
+        const unsigned int gkey = entropy_key(e8[p] * 0.0f);
+        unsigned long long word = (unsigned long long)gkey << 32;
+        if (key_below(entropy_key(e16[(y >> 1) * c.w16 + (x >> 1)]), thr)) {
+            gz += gkey == kKeyZero ? 1u : 0u;
+        } else {
             unsigned int pm = 0, pf = 0, flags = 0;
             const int64_t sm = ind_m[p];
             if (sm < 0 || sm >= nsym) flags |= 0x80000000u;
@@ -179,6 +198,10 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
             word = (unsigned long long)entropy_key(e8[p]) << 32 | flags | pm << 16 | pf;
         }
         kv[p] = word;
+    }
+    if (thr) {                                       // (workgroup-uniform; without a coarse threshold there is no coarse patch)
+        gz = curve_wave_sum(gz);
+        if ((tid & (kWave - 1)) == 0 && gz) atomicAdd(&sh_gzeros, gz);
     }
     __syncthreads();
     lds_sort_u64(kv, n8, tid, nt);
@@ -207,7 +230,7 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
 
     CurveSorted r;
     r.kv = kv; r.sf = sf; r.n8 = n8;
-    r.ncoarse = sh_ncoarse; r.thr = thr;
+    r.ncoarse = sh_ncoarse; r.gzeros = sh_gzeros; r.thr = thr;
     r.total_m = (unsigned int)total; r.total_f = (unsigned int)(total >> 32);
     r.first_bad_m = sh_first_bad_m; r.last_bad_f = sh_last_bad_f;
     r.size_c = (streams & 1) ? stream_bytes(r.ncoarse, sh_cbits, sh_cbad != 0) : 0;
@@ -220,7 +243,6 @@ __device__ __forceinline__ CurveSorted curve_sort_scan(const CurveTile &c, const
 __device__ __forceinline__ void curve_rank_sizes(const CurveSorted &r, int K, int streams, int32_t *o)
 {
     const unsigned long long *kv = r.kv;
-    const unsigned int zeros = 4u * r.ncoarse;
     const unsigned int t = (unsigned int)(kv[K ? K - 1 : 0] >> 32);              // sorted[K - 1] (K == 0: index 0, RouterTriple.py:31)
     int lo = 0, hi = K ? K - 1 : 0;                                              // lower bound of t: the first element not below it
     while (lo < hi) {
@@ -228,9 +250,10 @@ __device__ __forceinline__ void curve_rank_sizes(const CurveSorted &r, int K, in
         if ((unsigned int)(kv[mid] >> 32) < t) lo = mid + 1;
         else hi = mid;
     }
-    const unsigned int cnt = (unsigned int)lo;                                   // elements with e8 < t; with t > 0 all coarse zeros are among them
-    const unsigned int n_med = t ? cnt - zeros : 0u;
-    const unsigned int n_fine = (unsigned int)r.n8 - zeros - n_med;
+    // elements of the medium list below t (none below a NaN); the gated zeros are among them exactly when t > 0, the gated NaNs never
+    const unsigned int cnt = t != kKeyNaN ? (unsigned int)lo : 0u;
+    const unsigned int n_med = cnt - (cnt && t > kKeyZero ? r.gzeros : 0u);
+    const unsigned int n_fine = (unsigned int)r.n8 - 4u * r.ncoarse - n_med;
     const unsigned int bits_m = cnt ? (unsigned int)kv[cnt - 1] : 0u;
     const unsigned int bits_f = r.total_f - (cnt ? r.sf[cnt - 1] : 0u);
     o[0] = r.size_c;
@@ -243,7 +266,7 @@ __device__ __forceinline__ void curve_rank_sizes(const CurveSorted &r, int K, in
 __device__ __forceinline__ void curve_summary(const CurveSorted &r, int32_t *s)
 {
     s[0] = (int32_t)r.ncoarse;
-    s[1] = (int32_t)r.thr;
+    s[1] = (int32_t)entropy_key_bits(r.thr);
     s[2] = (int32_t)r.total_m;
     s[3] = (int32_t)r.total_f;
 }
@@ -355,7 +378,7 @@ struct RateRanksArgs {
     const int32_t *ranks;                            // device [R], ascending
     int R;
     int32_t *total;                                  // [B, R]: the five sizes summed; negative: a selected symbol outside the table
-    uint32_t *tkey;                                  // [B, R]: the medium threshold's key at that rank
+    uint32_t *tkey;                                  // [B, R]: the medium threshold at that rank (fp32 bit pattern)
     int32_t *summary;                                // [B, 4], as rate_curve_kernel's
 };
 
@@ -386,7 +409,7 @@ __global__ __launch_bounds__(kCurveThreads) void rate_curve_ranks_kernel(RateRan
 #pragma unroll
             for (int s = 0; s < CGIC_NUM_STREAMS; ++s) { bad |= o[s] < 0; sum += o[s]; }
             if (bad) sum = (int32_t)(CGIC_ERR_INVALID - 10);
-            t = (uint32_t)(r.kv[K ? K - 1 : 0] >> 32);
+            t = entropy_key_bits((uint32_t)(r.kv[K ? K - 1 : 0] >> 32));
         }
         total[j] = sum;
         tkey[j] = t;
@@ -476,13 +499,15 @@ struct RateApplyArgs {
     const int64_t *ind_c, *ind_m, *ind_f;
     const float *e16, *e8;
     int B, h16, w16, R;
+    int k_c;                                         // 0: no coarse patch
     int32_t *mc, *mm, *mf;
     int64_t *ind;
 };
 
 // One thread per row of a 4x4 fine block (= one 16x16 pixel patch): four fine mask elements and four merged indices in 16-byte
-// stores, the two medium elements of even rows, the coarse element of the block's first row.  The comparisons are the sort's
-// (entropy_key): coarse = e16 < thr_c, medium = not coarse and e8 < t, fine = the rest (RouterTriple.py:25,32,34)
+// stores, the two medium elements of even rows, the coarse element of the block's first row.  The comparisons are the router's float
+// '<' against the thresholds the sort found (on keys, which order as '<' does): coarse = e16 < thr_c, medium = not coarse and e8 < t,
+// fine = the rest (RouterTriple.py:25,32,34)
 __global__ __launch_bounds__(kApplyThreads) void rate_apply_kernel(RateApplyArgs a)
 {
     const int64_t j = a.choice[0];
@@ -501,12 +526,12 @@ __global__ __launch_bounds__(kApplyThreads) void rate_apply_kernel(RateApplyArgs
         int c = 0;
         longlong2 v0 = {0, 0}, v1 = {0, 0};
         if (j >= 0) {
-            const unsigned int thr = (unsigned int)a.summary[b * kCurveSummary + 1];
-            const unsigned int t = a.tkey[b * a.R + j];
-            c = entropy_key(a.e16[o16]) < thr;
+            const float thr = __uint_as_float((unsigned int)a.summary[b * kCurveSummary + 1]);
+            const float t = __uint_as_float(a.tkey[b * a.R + j]);
+            c = a.k_c > 0 && a.e16[o16] < thr;
             const float2 e = *reinterpret_cast<const float2 *>(a.e8 + o8);
-            m.x = !c && entropy_key(e.x) < t;
-            m.y = !c && entropy_key(e.y) < t;
+            m.x = !c && e.x < t;
+            m.y = !c && e.y < t;
             const int f0 = !c && !m.x, f1 = !c && !m.y;
             f = make_int4(f0, f0, f1, f1);
             if (c) {
@@ -766,7 +791,7 @@ extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, c
     RateApplyArgs q;
     q.choice = choice_dev; q.tkey = a.tkey; q.summary = a.summary;
     q.ind_c = ind_c; q.ind_m = ind_m; q.ind_f = ind_f; q.e16 = e16; q.e8 = e8;
-    q.B = (int)B; q.h16 = (int)h16; q.w16 = (int)w16; q.R = (int)R;
+    q.B = (int)B; q.h16 = (int)h16; q.w16 = (int)w16; q.R = (int)R; q.k_c = (int)k_c;
     q.mc = mask_c; q.mm = mask_m; q.mf = mask_f; q.ind = ind;
     const int64_t rows = B * 4 * h16 * w16;
     int64_t grid = (rows + kApplyThreads - 1) / kApplyThreads;

@@ -311,7 +311,8 @@ class RateCurve(_Rates):
 def rate_curve(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, ranks=None):
     """exact sizes of the streams GrainCodec.compress would write for EVERY medium rank at `coarse_ratio`, every image routed on
     its own thresholds on the maps as given (cgic_rate_curve; no threshold-band refinement: maps of
-    entropy_maps(x, reference_order=True) make that the reference's routing from the pixels).  Arguments as rate_table's;
+    entropy_maps(x, reference_order=True) make that the reference's routing from the pixels).  The maps may hold any float (NaN,
+    +-Inf, negatives, signed zeros, denormals): the sizes are those of the router's masks on them.  Arguments as rate_table's;
     ranks: ((K, medium ratio), ...) to carry instead of reachable_ranks(n16, coarse_ratio).  -> RateCurve"""
     inds, e16c, e8c, (B, h16, w16) = _curve_inputs(ind_c, ind_m, ind_f, e16, e8)
     dev = e16c.device
@@ -416,7 +417,7 @@ def route_to_bpp(codec, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, target_bpp=N
     (cgic_route_to_budget): among the ranks a medium ratio reaches at `coarse_ratio` in the curve's mode (0, or 1 at coarse
     ratio 0; the two ends of the medium axis are other modes: compress_to_bpp(search="curve") covers them), what
     choose(rate_curve(...), target_bpp) picks, then the masks of TripleGrainFixedEntropyRouter(per_image=True) at that rank on
-    the maps as given and gather_grain_indices of them.  Arguments as rate_curve's.  budget: an int64 device tensor of one
+    the maps as given (any float, as rate_curve) and gather_grain_indices of them.  Arguments as rate_curve's.  budget: an int64 device tensor of one
     element, the byte budget of the batch (budget_bytes), used as it is -- a captured graph is replayed with a new target by
     writing into it; else it is made from target_bpp.  The call does not synchronise and copies nothing to the host.
     -> BppRoute"""
@@ -509,7 +510,7 @@ def _tile_groups(tiles):
 
 def rate_curve_tiled(codec, tiles, coarse_ratio, image_hw=None, settings=None, ends=True):
     """exact sizes of the streams of N tiled images for EVERY setting of the medium ratio at `coarse_ratio`: ONE ratio pair for
-    all tiles, every tile routed on its own thresholds on the maps as given (the reference's tiling driver,
+    all tiles, every tile routed on its own thresholds on the maps as given, any float in them (the reference's tiling driver,
     inference_high_resolution.py:236-251; maps of entropy_maps(tiles, reference_order=True) make that its routing from the pixels).
     tiles: one entry per shape group, (ind_c, ind_m, ind_f, e16, e8, images) -- or a dict with those keys --: the group's
     grain_indices and maps ([B_g, ...], as rate_curve takes them) and the image index of each of its tiles.  image_hw: the

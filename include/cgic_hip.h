@@ -787,7 +787,9 @@ int cgic_gather_grain_indices(const int64_t *ind_c, const int64_t *ind_m, const 
  * 4 h16 w16 + 1 settings per image, of which a rate table samples at most 64.
  *
  * cgic_rate_curve:
- *   t, ind_c / ind_m / ind_f, e16, e8, B, h16, w16   as cgic_rate_table; finite, non-negative maps
+ *   t, ind_c / ind_m / ind_f, e16, e8, B, h16, w16   as cgic_rate_table.  The maps may hold ANY float: NaN (what a NaN pixel
+ *            makes of its patches), +-Inf, negatives, zeros of either sign, denormals -- every comparison below is the router's
+ *            (torch.sort's order with NaN last, float '<', the fp32 product e8 * 0 under a coarse patch)
  *   coarse_ratio  in [0, 1].  > 0: the coarse rank k_c = round(n16 * coarse_ratio) and the stream set of mode 0; == 0: mode 1
  *            (no coarse patch; K = round(n8 * medium))
  *   nbytes   device int32 [B, n8 + 1, 5]: nbytes[b, K, :] == nbytes[c, b, :] of cgic_rate_table with per_image = 1 and
@@ -798,9 +800,10 @@ int cgic_gather_grain_indices(const int64_t *ind_c, const int64_t *ind_m, const 
  *            in 0 .. n8 are written; which of them a ratio reaches is host arithmetic (cgic_router_ranks).  <= -10: a selected
  *            symbol outside the table, as cgic_rate_table.
  *   workspace device, cgic_rate_curve_workspace_bytes(...) bytes, 16-byte aligned; on return int32 [B, 4] per image: the
- *            number of coarse patches, the coarse threshold's bit pattern, the medium / fine code bits of all non-coarse patches
- * One launch, one workgroup per image: the image's patches are sorted ONCE by entropy in LDS (64-bit words: the entropy's
- * bit pattern above the code lengths of the patch's medium symbol and of its four fine symbols), both payloads are prefix-
+ *            number of coarse patches, the coarse threshold's fp32 bit pattern (+-0 as +0, any NaN as 0x7FC00000; 0 when k_c == 0),
+ *            the medium / fine code bits of all non-coarse patches
+ * One launch, one workgroup per image: the image's patches are sorted ONCE by entropy in LDS (64-bit words: an order-preserving
+ * key of the medium list's element above the code lengths of the patch's medium symbol and of its four fine symbols), both payloads are prefix-
  * summed in that order, and every K is a binary search and two prefix reads.  LIMIT: 12 bytes of LDS per 8x8 patch, at most
  * 12288 patches per image (n8 <= 12288: up to 768x1024 pixels; a 768x768 tile has 9216), codes of at most 4095 bits; beyond:
  * CGIC_ERR_UNSUPPORTED.  Every argument is checked before anything is enqueued.  Not inside a launch group.
@@ -842,7 +845,7 @@ int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64_t n16, int
  * sized to the largest tile, the descriptor read with scalar loads; then the M ranks of the tile's class: a binary search and two
  * prefix reads each), and the fold (one thread per image and setting, int64 sums in descriptor order).  No workgroup waits on
  * another, no atomics on global memory: the results do not depend on T, on the order of the descriptors or on which tiles share a
- * call.  LIMITS per tile as cgic_rate_curve (n8 <= 12288, codes of at most 4095 bits, finite non-negative maps).  Every argument
+ * call.  LIMITS per tile as cgic_rate_curve (n8 <= 12288, codes of at most 4095 bits).  Every argument
  * and every descriptor is checked before anything is enqueued: CGIC_ERR_INVALID / _UNSUPPORTED with nothing written.  Not inside
  * a launch group. */
 typedef struct cgic_rate_tile {
@@ -883,7 +886,7 @@ int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64
  *            what makes cgic_rate_curve's table negative there): { -1, -1, 0, -1 }, and the masks and ind are all zeros
  *   workspace device, cgic_route_to_budget_workspace_bytes(B, h16, w16, R) bytes, 16-byte aligned
  * Three launches ordered by the stream alone: the curve (one workgroup per image, steps 1-3 of cgic_rate_curve -- the same
- * device body -- then per requested rank the image's bytes and the medium threshold's key), the pick (one workgroup; integer
+ * device body -- then per requested rank the image's bytes and the medium threshold), the pick (one workgroup; integer
  * sums, so the result does not depend on any order) and the apply (elementwise, 16-byte stores).  No workgroup waits on another.
  * LIMITS as cgic_rate_curve.  Every host argument is checked before anything is enqueued.  Not inside a launch group. */
 size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int64_t R);

@@ -115,6 +115,12 @@ R_CASES = [
     _r("40x32x32-mode3", 40, 32, 32, 0.3, 0.7, 1, _routed(3, 307, 0, 1, 40)),
     _r("1x85x128", 1, 85, 128, 0.1, 0.8, 1, _routed(0, 1088, 39168, 8, 8)),
     _r("3x5x7", 3, 5, 7, 0.1, 0.8, 1, _routed(0, 4, 126, 1, 3)),
+    # the shapes tests/test_special_entropies.py routes on special values, one per path of the stand-alone launch: a 768x768 tile's row
+    # bands (stage 1), a batch-global segment that stages only e8 (4096 + 640 + 16 x 5120 bytes), and two that stage nothing
+    _r("specials-tile-row-bands", 1, 48, 48, 0.1, 0.8, 1, _routed(0, 230, 8294, 8, 8, stage=1, lds=4096 + 288 + 20 * 2304)),
+    _r("specials-20x16x16-batch", 20, 16, 16, 0.1, 0.8, 0, _routed(0, 512, 18432, 1, 1, stage=2, lds=4096 + 640 + 16 * 5120)),
+    _r("specials-32x16x16-batch", 32, 16, 16, 0.1, 0.8, 0, _routed(0, 819, 29491, 1, 1, stage=0, lds=4096 + 1024)),
+    _r("specials-48x16x16-batch", 48, 16, 16, 0.1, 0.8, 0, _routed(0, 1229, 44237, 1, 1, stage=0, lds=4096 + 1536)),
     # round-half-even: the products are 0.5
     _r("1x2x2-half", 1, 2, 2, 0.125, 0.5, 1, _routed(0, 0, 10, 1, 1)),
     _r("1x1x1-half", 1, 1, 1, 0.5, 0.25, 1, _routed(0, 0, 3, 1, 1)),

@@ -39,6 +39,26 @@ def test_router_matches_reference(orc, golden, shape):
         assert np.array_equal(gate[..., :4 * w16], np.repeat(np.repeat(mc, 4, 2), 4, 3).astype(np.float32))
 
 
+def test_router_matches_reference_on_special_values(orc, golden):
+    """NaN, +-Inf, negatives, signed zeros and denormals in the maps (tests/golden/make_golden_specials.py): the oracle's router ==
+    the real router's masks at ratio pairs of all seven modes, over the flattened batch and image by image"""
+    import specials_ref as sr
+    g = golden("router_specials")
+    assert [tuple(r) for r in g["ratios"]] == sr.RATIOS and [tuple(s) for s in g["shapes"]] == sr.SHAPES
+    assert list(g["classes"]) == sr.CLASSES
+    assert {int(g[f"r{ri}_mode"]) for ri in range(len(sr.RATIOS))} == set(range(7))
+    for si in range(len(sr.SHAPES)):
+        for cls in sr.CLASSES:
+            e16, e8 = g[f"s{si}_{cls}_e16"], g[f"s{si}_{cls}_e8"]
+            want = sr.fixture_masks(g, si, cls)
+            for ri, (c, m) in enumerate(sr.RATIOS):
+                for how in ("batch", "per"):
+                    mc, mm, mf, _, mode = orc.router(e16, e8, c, m, per_image=how == "per")
+                    assert mode == int(g[f"r{ri}_mode"])
+                    for got, w in zip((mc, mm, mf), want[(ri, how)]):
+                        assert np.array_equal(got, w), (si, cls, c, m, how)
+
+
 def test_router_float64_mode_quirks(orc):
     # 1 - 0.7 - 0.3 = 5.55e-17 != 0 -> mode 0; 1 - 0.3 - 0.7 == 0.0 -> mode 3 (SURVEY 8a-C)
     assert orc.router_mode(0.7, 0.3) == 0 and orc.router_mode(0.3, 0.7) == 3
