@@ -65,6 +65,21 @@ inline size_t router_queue_scratch_bytes(int64_t nseg, int64_t N16)
     return 2 * nseg <= kRouterMaxQueues ? (size_t)nseg * refine_scratch_bytes_per_segment(N16, 4 * N16) : 0;
 }
 
+// Python's round() of the float64 product n * ratio (RouterTriple.py:23,30,42,54,65): round-half-even
+inline double rank_round(int64_t n, double ratio) { return nearbyint((double)n * ratio); }
+
+// THE rank arithmetic: the reference's two k for a segment of N16 coarse patches in `mode`, 0 where the mode uses none.  false: a k
+// outside its list (the reference raises IndexError).  As float64, the way they are made: a NaN or a huge ratio gives no integer
+inline bool router_ranks(int mode, int64_t N16, double c_ratio, double m_ratio, double *k_c, double *k_m)
+{
+    const int64_t N8 = 4 * N16;
+    *k_c = *k_m = 0;
+    if (mode == 0 || mode == 2 || mode == 3) *k_c = rank_round(N16, c_ratio);
+    if (mode == 0) *k_m = nearbyint((double)(4 * N16) * c_ratio + (double)N8 * m_ratio);
+    if (mode == 1) *k_m = rank_round(N8, m_ratio);
+    return *k_c >= 0 && *k_c <= (double)N16 && *k_m >= 0 && *k_m <= (double)N8;
+}
+
 struct RouterShape {
     int64_t B, h16, w16;        // images, coarse grid of one image
     double c_ratio, m_ratio;
@@ -106,11 +121,12 @@ inline int router_plan(const RouterShape &s, RouterPlan *p, RouterWhy *why)
     const int64_t nseg = p->nseg = s.per_image ? s.B : 1;
     const int64_t N16 = p->N16 = p->per * s.h16 * s.w16, N8 = p->N8 = 4 * N16;
     if (!(N8 < (int64_t)1 << 31)) { *why = ROUTER_SEGMENT_TOO_LARGE; return CGIC_ERR_UNSUPPORTED; }
-    // Python round() == round-half-even on the float64 product (:23,30,42,54,65)
-    if (mode == 0 || mode == 2 || mode == 3) p->k_c = (int64_t)nearbyint((double)N16 * s.c_ratio);
-    if (mode == 0) p->k_m = (int64_t)nearbyint((double)(4 * N16) * s.c_ratio + (double)N8 * s.m_ratio);
-    if (mode == 1) p->k_m = (int64_t)nearbyint((double)N8 * s.m_ratio);
-    if (!(p->k_c >= 0 && p->k_c <= N16 && p->k_m >= 0 && p->k_m <= N8)) { *why = ROUTER_K_RANGE; return CGIC_ERR_INVALID; }
+    double k_c, k_m;
+    const bool in_range = router_ranks(mode, N16, s.c_ratio, s.m_ratio, &k_c, &k_m);
+    // (for the message of a k out of range: what has no int64 reads as the smallest one, as the conversion instruction gives it)
+    const auto whole = [](double k) { return k >= -9.0e18 && k <= 9.0e18 ? (int64_t)k : INT64_MIN; };
+    p->k_c = whole(k_c); p->k_m = whole(k_m);
+    if (!in_range) { *why = ROUTER_K_RANGE; return CGIC_ERR_INVALID; }
     p->rank_c = (unsigned int)(p->k_c != 0 ? p->k_c - 1 : 0);      // sorted[k-1 if k != 0 else k]
     p->rank_m = (unsigned int)(p->k_m != 0 ? p->k_m - 1 : 0);
     {

@@ -13,6 +13,7 @@
 //                          one through cgic_router_f32 instead (sequential on the caller's stream).
 //   2. rate_reduce_kernel  grid B x C: per (image, candidate) the count and the summed code lengths of the selected symbols of
 //                          each grain (code lengths staged in LDS, DPP wave reductions), five int32 sizes out.
+#include "cgic_rate_plan.h"
 #include "cgic_router_dev.h"
 
 namespace cgic {
@@ -21,9 +22,7 @@ namespace cgic {
 int refine_source(const cgic_pixels *refine, int64_t h16, int64_t w16, RefineSrc *out);
 size_t router_big_scratch_bytes(int64_t B, int64_t h16, int64_t w16, int per_image);
 
-constexpr int kRateMaxCand = 64;
-constexpr int kRateThreads = 256;
-constexpr int kRateLdsSyms = 16384;          // code-length tables up to this many symbols are staged in LDS (64 KB)
+static_assert((size_t)kRateLdsSyms * sizeof(int32_t) <= 64 * 1024, "rate_reduce_kernel stages the code lengths without the dynamic-LDS opt-in");
 
 struct RateRouteArgs {
     RouterArgs base;                         // candidate 0's arguments; the fields below replace its per-candidate ones
@@ -142,22 +141,15 @@ __global__ __launch_bounds__(256) void gather_grain_indices_kernel(GatherArgs a)
     }
 }
 
-// one candidate's masks in the stack: [B, h16 w16], [B, 4 h16 w16], [B, 16 h16 w16] int32, each padded to 256 bytes
-static int64_t rate_slab(int64_t elems) { return (elems + 63) & ~(int64_t)63; }
-static size_t rate_mask_stack_bytes(int64_t B, int64_t h16, int64_t w16, int C)
-{
-    const int64_t n16 = B * h16 * w16;
-    return (size_t)C * (size_t)(rate_slab(n16) + rate_slab(4 * n16) + rate_slab(16 * n16)) * sizeof(int32_t);
-}
-
 }  // namespace cgic
 
 using namespace cgic;
 
 extern "C" size_t cgic_rate_table_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int C, int per_image)
 {
-    if (B <= 0 || h16 <= 0 || w16 <= 0 || C <= 0 || C > kRateMaxCand) return 0;
-    return rate_mask_stack_bytes(B, h16, w16, C);
+    RateTablePlan p;
+    const char *why = "";
+    return rate_table_form(B, h16, w16, C, &p, &why) == CGIC_OK ? p.workspace_needed : 0;
 }
 
 extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
@@ -166,24 +158,22 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
                                int32_t *nbytes, void *workspace, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_rate_table");
-    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && nbytes && coarse && medium, CGIC_ERR_INVALID, "rate_table: NULL argument");
-    CGIC_REQUIRE(C >= 1 && C <= kRateMaxCand, CGIC_ERR_INVALID, "rate_table: %d candidates (1..%d)", C, kRateMaxCand);
-    CGIC_REQUIRE(B >= 0 && h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "rate_table: bad shape");
-    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "rate_table: batch %lld exceeds the grid limit", (long long)B);
-    if (B == 0) return CGIC_OK;
-    const int64_t n16 = h16 * w16;
-    CGIC_REQUIRE(16 * n16 < ((int64_t)1 << 26), CGIC_ERR_UNSUPPORTED, "rate_table: latent grid too large");
-    const int nsym = cgic_table_num_symbols(t);
-    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "rate_table: table of %d symbols", nsym);
-    CGIC_REQUIRE((uint64_t)cgic_table_max_len(t) * (uint64_t)(16 * n16) < 0xFFFFFF00ull, CGIC_ERR_UNSUPPORTED,
-                 "rate_table: a stream could exceed 2^32 bits");
-    const size_t need = rate_mask_stack_bytes(B, h16, w16, C);
-    CGIC_REQUIRE(workspace, CGIC_ERR_INVALID, "rate_table: workspace of %zu bytes required (cgic_rate_table_workspace_bytes)", need);
-    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "rate_table: the workspace must be 16-byte aligned");
-    const int64_t sc = rate_slab(B * n16), sm = rate_slab(4 * B * n16), sf = rate_slab(16 * B * n16);
-    int32_t *stk_c = reinterpret_cast<int32_t *>(workspace);
-    int32_t *stk_m = stk_c + C * sc;
-    int32_t *stk_f = stk_m + C * sm;
+    RateTableCall call{};
+    call.table = t != nullptr;
+    if (t) { call.nsym = cgic_table_num_symbols(t); call.max_len = cgic_table_max_len(t); }
+    call.B = B; call.h16 = h16; call.w16 = w16; call.C = C;
+    call.inputs = ind_c && ind_m && ind_f && e16 && e8 && nbytes && coarse && medium;
+    call.workspace = (uintptr_t)workspace;
+    RateTablePlan p;
+    const char *why = "";
+    const int prc = rate_table_plan(call, &p, &why);
+    CGIC_REQUIRE(prc == CGIC_OK, prc, "%s", why);
+    if (p.nothing_to_do) return CGIC_OK;
+    const int64_t n16 = h16 * w16, sc = p.stride_c, sm = p.stride_m, sf = p.stride_f;
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+    int32_t *stk_c = reinterpret_cast<int32_t *>(ws + p.off_c);
+    int32_t *stk_m = reinterpret_cast<int32_t *>(ws + p.off_m);
+    int32_t *stk_f = reinterpret_cast<int32_t *>(ws + p.off_f);
 
     // ---- every candidate is checked before anything is enqueued (router_plan_args' checks; for the launch chain of segments
     // beyond the LDS also router_big's: the scratch, the pixels, the final launch's arguments)
@@ -257,7 +247,7 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
 
     // ---- 2. the sizes
     RateReduceArgs r;
-    r.len = tab.len; r.nsym = nsym;
+    r.len = tab.len; r.nsym = call.nsym;
     r.ind[0] = ind_c; r.ind[1] = ind_m; r.ind[2] = ind_f;
     r.mask[0] = stk_c; r.mask[1] = stk_m; r.mask[2] = stk_f;
     r.n[0] = n16; r.n[1] = 4 * n16; r.n[2] = 16 * n16;
@@ -265,9 +255,7 @@ extern "C" int cgic_rate_table(const cgic_table *t, const int64_t *ind_c, const 
     r.B = B;
     for (int c = 0; c < kRateMaxCand; ++c) r.streams[c] = c < C ? cgic_mode_streams(cgic_router_mode(coarse[c], medium[c])) : 0;
     r.nbytes = nbytes;
-    const size_t rlds = nsym <= kRateLdsSyms ? (size_t)nsym * sizeof(int32_t) : 0;
-    if (rlds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)rate_reduce_kernel, rlds); if (rc) return rc; }
-    hipLaunchKernelGGL(rate_reduce_kernel, dim3((unsigned)B, (unsigned)C), dim3(kRateThreads), rlds, s, r);
+    hipLaunchKernelGGL(rate_reduce_kernel, dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(kRateThreads), p.lds_bytes, s, r);
     return launch_check("rate_reduce_kernel");
 }
 

@@ -23,16 +23,11 @@
 // mixed shapes, one workgroup per tile, its shape and offsets read from a descriptor; step 4 answers the M requested ranks of the
 // tile's shape class, and a second launch sums the tiles of each image per setting and stream.
 #include "cgic_common.h"
+#include "cgic_rate_plan.h"
 
 #include <math.h>
 
 namespace cgic {
-
-constexpr int kCurveThreads = 1024;
-constexpr int64_t kCurveMaxN8 = 12288;               // 8x8 patches of one image (a 768x768 tile has 9216): 12 bytes of LDS each
-constexpr size_t kCurveLdsBudget = 152 * 1024;       // dynamic LDS of the workgroup; what the words leave of it stages code lengths
-constexpr int kCurveMaxLen = 4095;                   // payload fields: 14 bits medium, 16 bits for the sum of four fine lengths
-constexpr int kCurveSummary = 4;                     // int32 per image in the workspace
 
 struct RateCurveArgs {
     const int32_t *len;                              // device [nsym] code lengths (TableDev.len)
@@ -288,10 +283,6 @@ __global__ __launch_bounds__(kCurveThreads) void rate_curve_kernel(RateCurveArgs
 }
 
 // ---- cgic_rate_curve_tiles: T tiles of mixed shapes, the M requested ranks of each tile's shape class ------------------------
-constexpr int kTilesMaxShapes = 16;
-constexpr int kTilesMaxSettings = 65536;
-constexpr int kTilesMaxTiles = 65535;
-constexpr int kFoldThreads = 256;
 constexpr int32_t kTilesBadRank = CGIC_ERR_INVALID - 11;          // a rank outside 0 .. n8 of the tile (negative: folds to -1)
 
 struct RateTilesArgs {
@@ -363,9 +354,6 @@ __global__ __launch_bounds__(kFoldThreads) void rate_fold_tiles_kernel(const cgi
 }
 
 // ---- cgic_route_to_budget: curve at R requested ranks -> pick under a byte budget read from the device -> masks and indices -----
-constexpr int kPickThreads = 1024;
-constexpr int kApplyThreads = 256;
-
 struct RateRanksArgs {
     const int32_t *len;
     int nsym;
@@ -556,132 +544,84 @@ __global__ __launch_bounds__(kApplyThreads) void rate_apply_kernel(RateApplyArgs
 
 using namespace cgic;
 
-// the rank arithmetic of the router (router_plan in cgic_encode_plan.h restated: Python's round() is round-half-even on the float64
-// product, RouterTriple.py:23,30,42,54,65; ranks a mode does not use are 0)
+// the rank arithmetic of the router (cgic_encode_plan.h: router_ranks; ranks a mode does not use are 0)
 extern "C" int cgic_router_ranks(double coarse_ratio, double medium_ratio, int64_t n16, int64_t *k_coarse, int64_t *k_medium)
 {
     CGIC_REQUIRE(n16 > 0 && n16 < ((int64_t)1 << 29), CGIC_ERR_INVALID, "router_ranks: %lld coarse patches", (long long)n16);
-    const int mode = cgic_router_mode(coarse_ratio, medium_ratio);
-    const int64_t n8 = 4 * n16;
-    double k_c = 0, k_m = 0;
-    if (mode == 0 || mode == 2 || mode == 3) k_c = nearbyint((double)n16 * coarse_ratio);
-    if (mode == 0) k_m = nearbyint((double)(4 * n16) * coarse_ratio + (double)n8 * medium_ratio);
-    if (mode == 1) k_m = nearbyint((double)n8 * medium_ratio);
-    CGIC_REQUIRE(k_c >= 0 && k_c <= (double)n16 && k_m >= 0 && k_m <= (double)n8, CGIC_ERR_INVALID,
+    double k_c, k_m;
+    CGIC_REQUIRE(router_ranks(router_mode(coarse_ratio, medium_ratio), n16, coarse_ratio, medium_ratio, &k_c, &k_m), CGIC_ERR_INVALID,
                  "router: k out of range (k_coarse=%g of %lld, k_medium=%g of %lld); the reference raises IndexError",
-                 k_c, (long long)n16, k_m, (long long)n8);
+                 k_c, (long long)n16, k_m, (long long)(4 * n16));
     if (k_coarse) *k_coarse = (int64_t)k_c;
     if (k_medium) *k_medium = (int64_t)k_m;
     return CGIC_OK;
 }
 
-// ---- the host side of the three curve entry points: ONE set of checks, ONE LDS / launch plan ---------------------------------------
-// cgic_rate_curve, cgic_rate_curve_tiles and cgic_route_to_budget launch the same steps 1-3 under the same limits; what differs between
-// them is stated at the call: `who` (the name at the front of every message), whether coarse ratio 1 is allowed, the smallest batch
+// ---- the host side of the three curve entry points: each fills a CurveCall, asks cgic_rate_plan.h for the plan once and issues it ----
 
-// the coarse ratio's range (its top end included or not) and the table
-static int curve_setup_check(const char *who, const cgic_table *t, double coarse_ratio, bool one_allowed)
+// what the three calls share: the table as the plan wants it, the five inputs, the workspace
+static CurveCall curve_call(CurveEntry entry, const cgic_table *t, const void *ind_c, const void *ind_m, const void *ind_f, const void *e16,
+                            const void *e8, double coarse_ratio, const void *workspace)
 {
-    CGIC_REQUIRE(coarse_ratio >= 0.0 && (one_allowed ? coarse_ratio <= 1.0 : coarse_ratio < 1.0), CGIC_ERR_INVALID, "%s: coarse ratio %g outside [0, 1%s",
-                 who, coarse_ratio, one_allowed ? "]" : "): the curve's mode is 0, or 1 at coarse ratio 0");
-    const int nsym = cgic_table_num_symbols(t);
-    CGIC_REQUIRE(nsym > 0 && nsym <= 65536, CGIC_ERR_UNSUPPORTED, "%s: table of %d symbols", who, nsym);
-    CGIC_REQUIRE(cgic_table_max_len(t) <= kCurveMaxLen, CGIC_ERR_UNSUPPORTED, "%s: codes of up to %d bits (at most %d)", who,
-                 cgic_table_max_len(t), kCurveMaxLen);
-    return CGIC_OK;
+    CurveCall c{};
+    c.shape.entry = entry;
+    c.table = t != nullptr;
+    if (t) { c.nsym = cgic_table_num_symbols(t); c.max_len = cgic_table_max_len(t); }
+    c.coarse_ratio = coarse_ratio;
+    c.ind_c = (uintptr_t)ind_c; c.ind_m = (uintptr_t)ind_m; c.ind_f = (uintptr_t)ind_f; c.e16 = (uintptr_t)e16; c.e8 = (uintptr_t)e8;
+    c.workspace = (uintptr_t)workspace;
+    return c;
 }
 
-// the coarse rank of mode 0 (coarse ratio > 0); coarse ratio == 0 is mode 1: no coarse patch
-static int64_t curve_coarse_rank(int64_t n16, double coarse_ratio) { return coarse_ratio > 0.0 ? (int64_t)nearbyint((double)n16 * coarse_ratio) : 0; }
-
-static const char *curve_item(char (&buf)[32], int64_t tile)
-{
-    if (tile < 0) snprintf(buf, sizeof buf, "an image");
-    else snprintf(buf, sizeof buf, "tile %lld", (long long)tile);
-    return buf;
-}
-
-// one shape (tile >= 0: that tile's; else the batch's): positive, within one workgroup's LDS, and the coarse rank the ratio gives it
-static int curve_shape_check(const char *who, int64_t tile, int64_t h16, int64_t w16, double coarse_ratio, int64_t *k_c)
-{
-    char item[32];
-    CGIC_REQUIRE(h16 > 0 && w16 > 0, CGIC_ERR_INVALID, "%s: %s: bad shape", who, curve_item(item, tile));
-    CGIC_REQUIRE(h16 <= kCurveMaxN8 && w16 <= kCurveMaxN8 && 4 * h16 * w16 <= kCurveMaxN8, CGIC_ERR_UNSUPPORTED,
-                 "%s: %s of %lld x %lld coarse patches does not fit one workgroup's LDS (at most %lld 8x8 patches: 768x1024 pixels)", who,
-                 curve_item(item, tile), (long long)h16, (long long)w16, (long long)kCurveMaxN8);
-    const int64_t n16 = h16 * w16;
-    *k_c = curve_coarse_rank(n16, coarse_ratio);
-    CGIC_REQUIRE(*k_c >= 0 && *k_c <= n16, CGIC_ERR_INVALID, "%s: %s: k_coarse=%lld of %lld", who, curve_item(item, tile), (long long)*k_c,
-                 (long long)n16);
-    return CGIC_OK;
-}
-
-static int curve_workspace_check(const char *who, const void *workspace, size_t need)
-{
-    CGIC_REQUIRE(need > 0 && workspace, CGIC_ERR_INVALID, "%s: workspace of %zu bytes required (cgic_%s_workspace_bytes)", who, need, who);
-    CGIC_REQUIRE(((uintptr_t)workspace & 15u) == 0, CGIC_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
-    return CGIC_OK;
-}
-
-// every part of a workspace starts on a 256-byte boundary
-static size_t slab(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-static size_t summary_slab(int64_t n) { return slab((size_t)n * kCurveSummary * sizeof(int32_t)); }
-
-// THE launch plan of steps 1-3: one workgroup per image / tile, LDS and threads by the call's largest (n8_max 8x8 patches); fills what the
-// three argument blocks share (table, mode's streams, staging) and launches
+// steps 1-3 as the plan laid them out; fills what the three argument blocks share (table, mode's streams, staging) and launches
 template <class A>
-static int curve_launch(void (*kernel)(A), const char *name, const cgic_table *t, double coarse_ratio, int64_t grid, int64_t n8_max, A a,
-                        hipStream_t stream)
+static int curve_launch(void (*kernel)(A), const char *name, const cgic_table *t, const CurveCall &c, const CurvePlan &p, A a, hipStream_t stream)
 {
     TableDev tab;
     int rc = table_device_view(t, &tab);
     if (rc) return rc;
-    a.len = tab.len; a.nsym = cgic_table_num_symbols(t);
-    a.streams = cgic_mode_streams(coarse_ratio > 0.0 ? 0 : 1);
-    const size_t words = (size_t)n8_max * 12, lens = (size_t)a.nsym * sizeof(int32_t);
-    a.staged = words + lens <= kCurveLdsBudget;      // the code lengths fit the LDS behind the words
-    const size_t lds = words + (a.staged ? lens : 0);
-    if (lds > 64 * 1024) { rc = ensure_dynamic_lds((const void *)kernel, lds); if (rc) return rc; }
-    int threads = kCurveThreads;                     // one comparator per thread and pass while the image is small; whole waves
-    while (threads > 256 && threads >= n8_max) threads >>= 1;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, a);
+    a.len = tab.len; a.nsym = c.nsym;
+    a.streams = cgic_mode_streams(p.mode);
+    a.staged = p.staged;
+    if (p.lds_opt_in) { rc = ensure_dynamic_lds((const void *)kernel, p.lds_bytes); if (rc) return rc; }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.threads), p.lds_bytes, stream, a);
     return launch_check(name);
 }
 
 extern "C" size_t cgic_rate_curve_workspace_bytes(int64_t B, int64_t h16, int64_t w16)
 {
-    if (B <= 0 || h16 <= 0 || w16 <= 0) return 0;
-    return summary_slab(B);
+    CurveShape s{};
+    s.entry = CURVE_IMAGES; s.B = B; s.h16 = h16; s.w16 = w16;
+    return curve_workspace_bytes(s);
 }
 
 extern "C" int cgic_rate_curve(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
                                const float *e16, const float *e8, int64_t B, int64_t h16, int64_t w16, double coarse_ratio,
                                int32_t *nbytes, void *workspace, cgic_stream_t stream)
 {
-    static const char who[] = "rate_curve";
     CGIC_NOT_IN_GROUP("cgic_rate_curve");
-    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && nbytes, CGIC_ERR_INVALID, "%s: NULL argument", who);
-    int64_t k_c;
-    int rc;
-    if ((rc = curve_setup_check(who, t, coarse_ratio, true))) return rc;
-    CGIC_REQUIRE(B >= 0, CGIC_ERR_INVALID, "%s: bad shape", who);
-    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "%s: batch %lld exceeds the grid limit", who, (long long)B);
-    if ((rc = curve_shape_check(who, -1, h16, w16, coarse_ratio, &k_c))) return rc;
-    if ((rc = curve_workspace_check(who, workspace, cgic_rate_curve_workspace_bytes(B > 0 ? B : 1, h16, w16)))) return rc;
-    if (B == 0) return CGIC_OK;                      // (an empty batch is not an error here; cgic_route_to_budget has nothing to pick from)
+    CurveCall c = curve_call(CURVE_IMAGES, t, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, workspace);
+    c.shape.B = B; c.shape.h16 = h16; c.shape.w16 = w16;
+    c.nbytes = (uintptr_t)nbytes;
+    CurvePlan p;
+    const char *why = "";
+    const int rc = curve_plan(c, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+    if (p.nothing_to_do) return CGIC_OK;
 
     RateCurveArgs a;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
-    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)k_c;
+    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)p.k_c;
     a.nbytes = nbytes;
-    a.summary = reinterpret_cast<int32_t *>(workspace);
-    return curve_launch(rate_curve_kernel, "rate_curve_kernel", t, coarse_ratio, B, 4 * h16 * w16, a, (hipStream_t)stream);
+    a.summary = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + p.off_summary);
+    return curve_launch(rate_curve_kernel, "rate_curve_kernel", t, c, p, a, (hipStream_t)stream);
 }
 
 extern "C" size_t cgic_rate_curve_tiles_workspace_bytes(int64_t T, int64_t M, int tile_nbytes_given)
 {
-    if (T <= 0 || M <= 0 || T > kTilesMaxTiles || M > kTilesMaxSettings) return 0;
-    return summary_slab(T) + (tile_nbytes_given ? 0 : (size_t)T * (size_t)M * CGIC_NUM_STREAMS * sizeof(int32_t));
+    CurveShape s{};
+    s.entry = CURVE_TILES; s.T = T; s.N = 1; s.S = 1; s.M = M; s.tile_nbytes_given = tile_nbytes_given != 0;
+    return curve_workspace_bytes(s);
 }
 
 extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
@@ -690,65 +630,33 @@ extern "C" int cgic_rate_curve_tiles(const cgic_table *t, const int64_t *ind_c, 
                                      const int32_t *ranks_dev, int64_t S, int64_t M, int64_t *image_nbytes, int32_t *tile_nbytes,
                                      void *workspace, cgic_stream_t stream)
 {
-    static const char who[] = "rate_curve_tiles";
     CGIC_NOT_IN_GROUP("cgic_rate_curve_tiles");
-    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && count && tiles && tiles_dev && ranks_dev && image_nbytes, CGIC_ERR_INVALID,
-                 "%s: NULL argument", who);
-    CGIC_REQUIRE(T >= 0 && N >= 1 && S >= 1 && M >= 1, CGIC_ERR_INVALID, "rate_curve_tiles: bad counts (T=%lld, N=%lld, S=%lld, M=%lld)",
-                 (long long)T, (long long)N, (long long)S, (long long)M);
-    int rc;
-    if ((rc = curve_setup_check(who, t, coarse_ratio, true))) return rc;
-    CGIC_REQUIRE(T <= kTilesMaxTiles && N <= kTilesMaxTiles, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tiles of %lld images exceed the grid limit (%d)",
-                 (long long)T, (long long)N, kTilesMaxTiles);
-    CGIC_REQUIRE(S <= kTilesMaxShapes, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld tile shapes (at most %d)", (long long)S, kTilesMaxShapes);
-    CGIC_REQUIRE(M <= kTilesMaxSettings, CGIC_ERR_UNSUPPORTED, "rate_curve_tiles: %lld settings (at most %d)", (long long)M, kTilesMaxSettings);
-    for (int i = 0; i < 5; ++i) CGIC_REQUIRE(count[i] >= 0, CGIC_ERR_INVALID, "rate_curve_tiles: negative element count");
-    // every descriptor: its shape fits one workgroup, its class has ONE shape, its coarse rank is the one cgic_rate_curve takes,
-    // and its five parts lie inside the buffers
-    int64_t class_h[kTilesMaxShapes], class_w[kTilesMaxShapes];
-    for (int s = 0; s < kTilesMaxShapes; ++s) class_h[s] = class_w[s] = 0;
-    int64_t n8_max = 0;
-    for (int64_t i = 0; i < T; ++i) {
-        const cgic_rate_tile &d = tiles[i];
-        const int64_t h16 = d.h16, w16 = d.w16;
-        int64_t k_c;
-        if ((rc = curve_shape_check(who, i, h16, w16, coarse_ratio, &k_c))) return rc;
-        const int64_t n16 = h16 * w16, n8 = 4 * n16;
-        CGIC_REQUIRE(d.shape >= 0 && d.shape < S && d.image >= 0 && d.image < N && d.reserved == 0, CGIC_ERR_INVALID,
-                     "rate_curve_tiles: tile %lld: shape class %d of %lld, image %d of %lld", (long long)i, d.shape, (long long)S, d.image, (long long)N);
-        if (class_h[d.shape] == 0) { class_h[d.shape] = h16; class_w[d.shape] = w16; }
-        CGIC_REQUIRE(class_h[d.shape] == h16 && class_w[d.shape] == w16, CGIC_ERR_INVALID,
-                     "rate_curve_tiles: tile %lld: shape class %d holds tiles of two shapes", (long long)i, d.shape);
-        CGIC_REQUIRE(d.k_c == k_c, CGIC_ERR_INVALID, "rate_curve_tiles: tile %lld: k_coarse=%d, the ratio gives %lld of %lld", (long long)i, d.k_c,
-                     (long long)k_c, (long long)n16);
-        const int64_t off[5] = {d.off_c, d.off_m, d.off_f, d.off_e16, d.off_e8};
-        const int64_t len[5] = {n16, n8, 4 * n8, n16, n8};
-        for (int k = 0; k < 5; ++k)
-            CGIC_REQUIRE(off[k] >= 0 && off[k] <= count[k] && len[k] <= count[k] - off[k], CGIC_ERR_INVALID,
-                         "rate_curve_tiles: tile %lld: part %d at offset %lld + %lld elements is outside its buffer of %lld", (long long)i, k,
-                         (long long)off[k], (long long)len[k], (long long)count[k]);
-        if (n8 > n8_max) n8_max = n8;
-    }
-    if ((rc = curve_workspace_check(who, workspace, cgic_rate_curve_tiles_workspace_bytes(T > 0 ? T : 1, M, tile_nbytes != nullptr)))) return rc;
+    CurveCall c = curve_call(CURVE_TILES, t, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, workspace);
+    c.shape.T = T; c.shape.N = N; c.shape.S = S; c.shape.M = M; c.shape.tile_nbytes_given = tile_nbytes != nullptr;
+    c.count = count; c.tiles = tiles;
+    c.tiles_dev = (uintptr_t)tiles_dev; c.ranks_dev = (uintptr_t)ranks_dev; c.image_nbytes = (uintptr_t)image_nbytes;
+    CurvePlan p;
+    const char *why = "";
+    int rc = curve_plan(c, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
 
+    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
     RateTilesArgs a;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
     a.tiles = tiles_dev; a.ranks = ranks_dev; a.M = (int)M;
-    a.summary = reinterpret_cast<int32_t *>(workspace);
-    a.tile_nbytes = tile_nbytes ? tile_nbytes : reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + summary_slab(T > 0 ? T : 1));
-    if (T > 0 && (rc = curve_launch(rate_curve_tiles_kernel, "rate_curve_tiles_kernel", t, coarse_ratio, T, n8_max, a, (hipStream_t)stream))) return rc;
-    hipLaunchKernelGGL(rate_fold_tiles_kernel, dim3((unsigned)((M + kFoldThreads - 1) / kFoldThreads), (unsigned)N), dim3(kFoldThreads), 0,
-                       (hipStream_t)stream, tiles_dev, (int)T, (int)M, (const int32_t *)a.tile_nbytes, image_nbytes);
+    a.summary = reinterpret_cast<int32_t *>(ws + p.off_summary);
+    a.tile_nbytes = tile_nbytes ? tile_nbytes : reinterpret_cast<int32_t *>(ws + p.off_tile_nbytes);
+    if (p.grid > 0 && (rc = curve_launch(rate_curve_tiles_kernel, "rate_curve_tiles_kernel", t, c, p, a, (hipStream_t)stream))) return rc;
+    hipLaunchKernelGGL(rate_fold_tiles_kernel, dim3((unsigned)p.fold_grid_x, (unsigned)p.fold_grid_y), dim3(kFoldThreads), 0, (hipStream_t)stream,
+                       tiles_dev, (int)T, (int)M, (const int32_t *)a.tile_nbytes, image_nbytes);
     return launch_check("rate_fold_tiles_kernel");
 }
 
 extern "C" size_t cgic_route_to_budget_workspace_bytes(int64_t B, int64_t h16, int64_t w16, int64_t R)
 {
-    if (B <= 0 || h16 <= 0 || w16 <= 0 || R <= 0 || B > 65535 || h16 > kCurveMaxN8 || w16 > kCurveMaxN8 || 4 * h16 * w16 > kCurveMaxN8
-        || R > 4 * h16 * w16 + 1)
-        return 0;
-    // the per-image summary, then per image and requested rank the bytes (int32) and the medium threshold's key (uint32)
-    return summary_slab(B) + 2 * slab((size_t)B * (size_t)R * sizeof(int32_t));
+    CurveShape s{};
+    s.entry = CURVE_BUDGET; s.B = B; s.h16 = h16; s.w16 = w16; s.R = R;
+    return curve_workspace_bytes(s);
 }
 
 extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, const int64_t *ind_m, const int64_t *ind_f,
@@ -756,46 +664,36 @@ extern "C" int cgic_route_to_budget(const cgic_table *t, const int64_t *ind_c, c
                                     const int32_t *ranks_dev, int64_t R, const int64_t *budget_dev, int32_t *mask_c, int32_t *mask_m,
                                     int32_t *mask_f, int64_t *ind, int64_t *choice_dev, void *workspace, cgic_stream_t stream)
 {
-    static const char who[] = "route_to_budget";
     CGIC_NOT_IN_GROUP("cgic_route_to_budget");
-    CGIC_REQUIRE(t && ind_c && ind_m && ind_f && e16 && e8 && ranks_dev && budget_dev && mask_c && mask_m && mask_f && ind && choice_dev,
-                 CGIC_ERR_INVALID, "%s: NULL argument", who);
-    int64_t k_c;
-    int rc;
-    if ((rc = curve_setup_check(who, t, coarse_ratio, false))) return rc;       // (coarse ratio 1 leaves the curve's mode)
-    CGIC_REQUIRE(B >= 1, CGIC_ERR_INVALID, "%s: bad shape", who);           // (no image: nothing to pick from)
-    CGIC_REQUIRE(B <= 65535, CGIC_ERR_UNSUPPORTED, "%s: batch %lld exceeds the grid limit", who, (long long)B);
-    if ((rc = curve_shape_check(who, -1, h16, w16, coarse_ratio, &k_c))) return rc;
-    const int64_t n8 = 4 * h16 * w16;
-    CGIC_REQUIRE(R >= 1 && R <= n8 + 1, CGIC_ERR_INVALID, "route_to_budget: %lld requested ranks (1 .. %lld)", (long long)R, (long long)(n8 + 1));
-    if ((rc = curve_workspace_check(who, workspace, cgic_route_to_budget_workspace_bytes(B, h16, w16, R)))) return rc;
-    CGIC_REQUIRE((((uintptr_t)ind_m | (uintptr_t)ind_f | (uintptr_t)mask_m | (uintptr_t)mask_f | (uintptr_t)ind) & 15u) == 0 && ((uintptr_t)e8 & 7u) == 0
-                     && ((uintptr_t)budget_dev & 7u) == 0 && ((uintptr_t)choice_dev & 7u) == 0,
-                 CGIC_ERR_INVALID, "route_to_budget: ind_m, ind_f, mask_m, mask_f and ind must be 16-byte aligned, e8, the budget and the choice 8-byte aligned");
+    CurveCall c = curve_call(CURVE_BUDGET, t, ind_c, ind_m, ind_f, e16, e8, coarse_ratio, workspace);
+    c.shape.B = B; c.shape.h16 = h16; c.shape.w16 = w16; c.shape.R = R;
+    c.ranks_dev = (uintptr_t)ranks_dev; c.budget_dev = (uintptr_t)budget_dev; c.choice_dev = (uintptr_t)choice_dev;
+    c.mask_c = (uintptr_t)mask_c; c.mask_m = (uintptr_t)mask_m; c.mask_f = (uintptr_t)mask_f; c.ind = (uintptr_t)ind;
+    CurvePlan p;
+    const char *why = "";
+    int rc = curve_plan(c, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
 
     unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
     RateRanksArgs a;
     a.ind_c = ind_c; a.ind_m = ind_m; a.ind_f = ind_f; a.e16 = e16; a.e8 = e8;
-    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)k_c;
+    a.h16 = (int)h16; a.w16 = (int)w16; a.k_c = (int)p.k_c;
     a.ranks = ranks_dev; a.R = (int)R;
-    a.summary = reinterpret_cast<int32_t *>(ws);
-    a.total = reinterpret_cast<int32_t *>(ws + summary_slab(B));
-    a.tkey = reinterpret_cast<uint32_t *>(ws + summary_slab(B) + slab((size_t)B * (size_t)R * sizeof(int32_t)));
-    if ((rc = curve_launch(rate_curve_ranks_kernel, "rate_curve_ranks_kernel", t, coarse_ratio, B, n8, a, (hipStream_t)stream))) return rc;
+    a.summary = reinterpret_cast<int32_t *>(ws + p.off_summary);
+    a.total = reinterpret_cast<int32_t *>(ws + p.off_total);
+    a.tkey = reinterpret_cast<uint32_t *>(ws + p.off_tkey);
+    if ((rc = curve_launch(rate_curve_ranks_kernel, "rate_curve_ranks_kernel", t, c, p, a, (hipStream_t)stream))) return rc;
 
-    hipLaunchKernelGGL(rate_pick_kernel, dim3(1), dim3(kPickThreads), 0, (hipStream_t)stream, (const int32_t *)a.total, ranks_dev, (int)B, (int)R,
-                       budget_dev, choice_dev);
+    hipLaunchKernelGGL(rate_pick_kernel, dim3((unsigned)p.pick_grid), dim3(kPickThreads), 0, (hipStream_t)stream, (const int32_t *)a.total, ranks_dev,
+                       (int)B, (int)R, budget_dev, choice_dev);
     rc = launch_check("rate_pick_kernel");
     if (rc) return rc;
 
     RateApplyArgs q;
     q.choice = choice_dev; q.tkey = a.tkey; q.summary = a.summary;
     q.ind_c = ind_c; q.ind_m = ind_m; q.ind_f = ind_f; q.e16 = e16; q.e8 = e8;
-    q.B = (int)B; q.h16 = (int)h16; q.w16 = (int)w16; q.R = (int)R; q.k_c = (int)k_c;
+    q.B = (int)B; q.h16 = (int)h16; q.w16 = (int)w16; q.R = (int)R; q.k_c = (int)p.k_c;
     q.mc = mask_c; q.mm = mask_m; q.mf = mask_f; q.ind = ind;
-    const int64_t rows = B * 4 * h16 * w16;
-    int64_t grid = (rows + kApplyThreads - 1) / kApplyThreads;
-    if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL(rate_apply_kernel, dim3((unsigned)grid), dim3(kApplyThreads), 0, (hipStream_t)stream, q);
+    hipLaunchKernelGGL(rate_apply_kernel, dim3((unsigned)p.apply_grid), dim3(kApplyThreads), 0, (hipStream_t)stream, q);
     return launch_check("rate_apply_kernel");
 }

@@ -183,6 +183,12 @@ def coarse_rank(n16, c):
     return round(n16 * c) if c > 0 else 0
 
 
+def curve_staged(n8, nsym):
+    """the curve's launch plan (cgic_rate_plan.h, curve_plan): the code lengths are staged in LDS behind the 12 bytes per 8x8 patch
+    when both fit 152 KB (tests/test_rate_plan_host.py holds this to the plan itself)"""
+    return 12 * n8 + 4 * nsym <= 152 * 1024
+
+
 def properties(e16, e8, k_c, K):
     """what a (k_c, K) pair exercises on one segment: the set of names that hold"""
     gc, gm, gf, info = route_at_ranks(e16, e8, k_c, K)

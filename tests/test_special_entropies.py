@@ -59,12 +59,6 @@ def _big_table():
     return coder, lens
 
 
-def _curve_staged(n8, nsym):
-    """the curve's launch plan (cgic_rate_curve.hip, curve_launch): the code lengths are staged in LDS behind the 12 bytes per 8x8
-    patch when both fit 152 KB"""
-    return 12 * n8 + 4 * nsym <= 152 * 1024
-
-
 @functools.lru_cache(maxsize=None)
 def _heads_indices(B, h16, w16, seed, nsym=1024):
     """grain indices [B, h, w] x 3 (device int64, host numpy): of finite random heads through the Zipf codebook, or -- for a table
@@ -324,7 +318,7 @@ def test_rate_curve_at_the_limit(cls, table):
     else:
         coder, lens = _big_table()
         codec, nsym = coder.table.handle, 4096                       # (the rate calls take a GrainCodec or the table's handle)
-    assert _curve_staged(n8, nsym) == (table == "zipf") and _curve_staged(n8, 2048) and not _curve_staged(n8, 2049)
+    assert sr.curve_staged(n8, nsym) == (table == "zipf") and sr.curve_staged(n8, 2048) and not sr.curve_staged(n8, 2049)
     inds, hinds = _heads_indices(1, h16, w16, 400, nsym)
     e16, e8 = sr.special_maps(1, h16, w16, cls, seed=64, levels=40)
     _assert_curve(codec, lens, inds, hinds, e16, e8, _edge_ranks, (cls, table))
@@ -334,6 +328,68 @@ def test_rate_curve_at_the_limit(cls, table):
         pick = curve.ranks[::max(1, len(curve.ranks) // 16)]
         tab = cg.rate_table(codec, *inds, d16, d8, [curve.ratio(K) for K in pick], per_image=True)
         assert torch.equal(curve.nbytes[:, torch.tensor(pick, device=DEV)], tab.nbytes.permute(1, 0, 2)), cls
+
+
+# ---------------------------------------------------------------------------- the thread steps of the curve launch
+STEP_SHAPES = [(8, 16), (3, 43)]            # n8 = 512: the largest image sorted by 256 threads; 516: the smallest sorted by 512
+
+
+@functools.lru_cache(maxsize=None)
+def _step_case(h16, w16):
+    inds, hinds = _heads_indices(2, h16, w16, 700 + w16)
+    e16, e8 = sr.special_maps(2, h16, w16, "mix", seed=w16, levels=12)
+    return inds, hinds, e16, e8
+
+
+@pytest.mark.parametrize("h16,w16", STEP_SHAPES)
+def test_rate_entry_points_at_the_thread_steps(h16, w16):
+    """B = 2 on either side of the step from 256 to 512 threads (16x16, 16x17 and 48x64 are above): the curve at every rank, the
+    budget route and a two-shape tiled call, all integers, all exact"""
+    _, codec, lens = _zipf()
+    inds, hinds, e16, e8 = _step_case(h16, w16)
+    d16, d8 = _t(e16), _t(e8)
+    B, n16 = 2, h16 * w16
+    # ---- the curve: every rank against the reference at explicit ranks, and the CPU oracle's router and sizes at every rank a
+    # ratio reaches
+    _assert_curve(codec, lens, inds, hinds, e16, e8, _every_rank, (h16, w16))
+    for coarse in (0.3, 0.0):
+        curve = cg.rate_curve(codec, *inds, d16, d8, coarse)
+        nb = curve.nbytes.cpu().numpy()
+        assert curve.ranks == list(range(round(4 * n16 * coarse), 4 * n16 + 1))
+        for K, (c, m) in zip(curve.ranks, curve.candidates):
+            omc, omm, omf, _, mode = orc.router(e16, e8, c, m, per_image=True, want_gate=False)
+            for b in range(B):
+                want = sr.stream_sizes(omc[b, 0] == 1, omm[b, 0] == 1, omf[b, 0] == 1, hinds[0][b], hinds[1][b], hinds[2][b], lens,
+                                       orc.mode_streams(mode))
+                assert nb[b, K].tolist() == want, (coarse, K, b, nb[b, K].tolist(), want)
+    # ---- the budget route: the router's masks and the merged indices at the rank it reports
+    for coarse in (0.3, 0.0):
+        Kt, mediums = rate.reachable_ranks_vec(n16, float(coarse))
+        ranks = Kt.tolist()
+        k_c, streams = sr.coarse_rank(n16, coarse), orc.mode_streams(0 if coarse > 0 else 1)
+        per = [sr.curve_at_ranks(e16[b], e8[b], hinds[0][b], hinds[1][b], hinds[2][b], lens, k_c, ranks, streams)[0] for b in range(B)]
+        S = [sum(sum(per[b][j]) for b in range(B)) for j in range(len(ranks))]
+        for budget in _budgets(S):
+            route = cg.route_to_bpp(codec, *inds, d16, d8, coarse, budget=torch.tensor([budget], dtype=torch.int64, device=DEV))
+            j = _assert_route(route, hinds, e16, e8, ranks, k_c, per, S, budget, codec, coarse, (h16, w16, coarse))
+            o = orc.router(e16, e8, coarse, float(mediums[j]), per_image=True, want_gate=False)
+            assert _masks_equal(route.masks, o[:3]) == [0, 0, 0], (coarse, budget, j)
+    # ---- one tile of each of the two shapes in one call, both of one image: every tile its own curve, the image their sum
+    for coarse in (0.3, 0.0):
+        groups, singles = [], []
+        for h, w in ((h16, w16), STEP_SHAPES[1 - STEP_SHAPES.index((h16, w16))]):
+            ti, _, t16, t8 = _step_case(h, w)
+            one, t16, t8 = tuple(t[:1] for t in ti), _t(t16[:1]), _t(t8[:1])
+            groups.append((*one, t16, t8, [0]))
+            singles.append(_curve_raw(codec, one, t16, t8, coarse)[0][0])
+        curve = cg.rate_curve_tiled(codec, groups, coarse, ends=False)
+        tile_nb = curve.tile_nbytes.cpu().numpy()
+        assert tile_nb.shape == (2, len(curve.candidates), 5) and curve.tile_shape == [0, 1] and len(curve.candidates) >= 16
+        fold = np.zeros(tile_nb.shape[1:], np.int64)
+        for s, single in enumerate(singles):
+            assert np.array_equal(tile_nb[s], single[curve.ranks[s].tolist()]), (coarse, s)
+            fold += tile_nb[s]
+        assert int(tile_nb.min()) >= 0 and np.array_equal(curve.nbytes.numpy()[0], fold)
 
 
 # ---------------------------------------------------------------------------- rate_curve_tiled
