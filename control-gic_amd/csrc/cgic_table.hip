@@ -464,12 +464,17 @@ extern "C" int cgic_table_create(const int64_t *freq, const int32_t *order, int 
     CGIC_REQUIRE(freq && out, CGIC_ERR_INVALID, "table_create: NULL argument");
     CGIC_REQUIRE(n >= 2 && n <= 65536, CGIC_ERR_INVALID, "table_create: n=%d out of range [2, 65536]", n);
     std::vector<char> seen((size_t)n, 0);
+    // no node of the tree exceeds the sum of the counts: the sum is bounded, not every count (65536 counts below 2^46 stay within
+    // it; so does a ladder of Fibonacci-like counts, whose code is 64 bits long with its largest count near 2^47)
+    const int64_t total_max = (int64_t)1 << 62;
+    int64_t total = 0;
     for (int i = 0; i < n; ++i) {
         int s = order ? order[i] : i;
         CGIC_REQUIRE(s >= 0 && s < n && !seen[s], CGIC_ERR_INVALID, "table_create: order is not a permutation");
         seen[s] = 1;
-        CGIC_REQUIRE(freq[s] >= 0 && freq[s] < ((int64_t)1 << 46), CGIC_ERR_INVALID,
-                     "table_create: freq[%d]=%lld outside [0, 2^46)", s, (long long)freq[s]);
+        CGIC_REQUIRE(freq[s] >= 0 && freq[s] < total_max - total, CGIC_ERR_INVALID,
+                     "table_create: freq[%d]=%lld is negative or takes the sum of the counts to 2^62", s, (long long)freq[s]);
+        total += freq[s];
     }
     Table *t = new (std::nothrow) Table();
     CGIC_REQUIRE(t, CGIC_ERR_NOMEM, "table_create: out of memory");

@@ -328,7 +328,8 @@ int cgic_router_f32(const float *e16, const float *e8, int64_t B, int64_t h16, i
  * CGIC/tools/indices_coding.py:10-17,46-75 (host side; CPython heapq
  * tie-breaking reproduced exactly).
  *
- *   freq  host [n] int64  int(value.item()) per symbol
+ *   freq  host [n] int64  int(value.item()) per symbol: none negative, their
+ *         sum below 2^62
  *   order host [n] int32 or NULL: order[i] = symbol pushed i-th = iteration
  *         order of the `frequency` mapping (NULL = 0,1,2,...).  NB the
  *         reference's mapping is an nn.ParameterDict built from a plain dict

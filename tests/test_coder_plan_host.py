@@ -65,6 +65,35 @@ PLANS += [
     # an empty batch asks for nothing, and is answered before the histogram's bound is looked at
     _case("0x64x64-hist-nsym8193", 0, 64, 64, dict(jobs=0, tickets=0, dyn_lds=0), hist=1, nsym=8193),
 ]
+# ---- a 64-bit code table (tests/test_long_codes.py): one row per form of the encoder, at the smallest grid (and batch) that reaches
+# it, then the other shapes that file runs.  A slot is 8 h w + 10 bytes, rounded up to 16
+LONG = dict(max_len=64)
+PLANS += [
+    # up to kLdsPosSmall positions: the small instantiation, the short jobs of an image in one workgroup
+    _case("form-lds-small-1x64x64-l64", 1, 64, 64, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 32784, 0), **LONG),
+    # up to kLdsPos positions: the same, the kLdsPos instantiation
+    _case("form-lds-1x64x96-l64", 1, 64, 96, _plan((1, 1, 1), 0, 0, 0, 1, 3, 0, 0, 49168, 0), **LONG),
+    # 8448 fine positions in 3 parts of 2816, each staged in 2 x 2816 + 64 bytes
+    _case("form-parts-1x64x132-l64", 1, 64, 132, _plan((1, 1, 3), 2816, 5696, 6, 0, 7, 0, 1, 67600, 152064), **LONG),
+    # 6 x 683 slots are beyond one ticket request: unsplit, all 8448 positions staged (2 x 8448 + 64 bytes)
+    _case("form-staged-683x64x132-l64", 683, 64, 132, _plan((1, 1, 1), 8448, 16960, 0, 0, 5, 0, 0, 67600), **LONG),
+    # 345 744 fine positions in 7 parts of 49 392: 98 784 bytes exceed the 96 KB stage: unsplit, round by round through the workspace
+    _case("form-global-1x588x588-l64", 1, 588, 588, _plan((1, 1, 1), 0, 0, 0, 0, 5, 0, 0, 2765968, 6223392), **LONG),
+    _case("3x64x64-l64", 3, 64, 64, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 32784, 0), **LONG),
+    _case("40x64x64-l64", 40, 64, 64, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 32784, 0), **LONG),
+    _case("1x4x4-l64", 1, 4, 4, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 144, 0), **LONG),
+    _case("1x8x12-l64", 1, 8, 12, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 784, 0), **LONG),
+    # 9216 fine positions in 3 parts of 3072
+    _case("1x96x96-l64", 1, 96, 96, _plan((1, 1, 3), 3072, 6208, 6, 0, 7, 0, 1, 73744, 165888), **LONG),
+    _case("12x96x96-l64", 12, 96, 96, _plan((1, 1, 3), 3072, 6208, 72, 0, 7, 0, 1, 73744, 1990656), **LONG),
+    _case("1x72x116-l64", 1, 72, 116, _plan((1, 1, 3), 2784, 5632, 6, 0, 7, 0, 1, 66832, 150336), **LONG),
+    _case("2x128x128-l64", 2, 128, 128, _plan((1, 1, 4), 4096, 8256, 12, 0, 8, 0, 1, 131088, 589824), **LONG),
+    # 65 bits and three-word codes change the slot alone (65 x 4096 / 8 + 10), 2560 symbols nothing
+    _case("1x64x64-l65", 1, 64, 64, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 33296, 0), max_len=65),
+    _case("3x32x48-l65", 3, 32, 48, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 12496, 0), max_len=65),
+    _case("3x64x64-l64-nsym2560", 3, 64, 64, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 32784, 0), nsym=2560, **LONG),
+    _case("3x32x48-l33-nsym96", 3, 32, 48, _plan((1, 1, 1), 0, 0, 0, 1, 3, 1, 0, 6352, 0), max_len=33, nsym=96),
+]
 REFUSALS = [
     _case("slot-one-below", 64, 64, 64, dict(err=ERR_CAPACITY, why="slot=10255, need a multiple of 16 >= 10256"), slot=10255),
     _case("slot-16-below", 64, 64, 64, dict(err=ERR_CAPACITY, why="slot=10240, need a multiple of 16 >= 10256"), slot=10240),

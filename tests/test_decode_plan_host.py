@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+import long_codes_ref as lc
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AUTO, LATENCY, THROUGHPUT = 0, 1, 2
 ERR_UNSUPPORTED, ERR_CAPACITY = -2, -5
@@ -76,6 +78,43 @@ CASES = [
     # a 64x64 grid's medium mask stream is staged as 32 + 2 words = 136 bytes
     _case("1x64x64-slot128", 1, 64, 64, AUTO, dict(err=ERR_CAPACITY, why="slot smaller than a mask stream"), slot=128),
     _case("1x64x64-slot144", 1, 64, 64, AUTO, _fused(20, 4, 16, 16, 1, 1, 0, 27632), slot=144),
+]
+
+
+# ---- code tables of 14 to 65 bits: every (B, h, w, longest code, decoder argument) that tests/test_long_codes.py runs, with the path
+# it must take (long_codes_ref.CODEC_CASES and FORM_CASES, worked out by hand there), so that "this case reaches the image decoder" is
+# a checked fact.  K follows the table; the slot is a 64-bit stream of the grid.
+_LONG_PATHS = {"image256": dict(decoder="image", ndec=1, image_threads=256), "image1024": dict(decoder="image", ndec=1, image_threads=1024),
+               "split4": dict(decoder="split", ndec=4, split_batch=1365), "split24": dict(decoder="split", ndec=24, split_batch=1365),
+               "serial": dict(decoder="serial", ndec=3)}
+
+
+def _long_code_rows():
+    rows = [(lc.case_id(K, L, B, h, w), K, L, B, h, w, paths) for K, L, B, h, w, paths in lc.CODEC_CASES]
+    rows += [(f"form-{form}-{lc.case_id(1024, 64, B, h, w)}", 1024, 64, B, h, w, paths) for form, B, h, w, paths in lc.FORM_CASES]
+    for name, K, L, B, h, w, paths in rows:
+        for mode, path in zip((AUTO, LATENCY, THROUGHPUT), paths):
+            # the fused launch: 4 decoder workgroups per image up to 64x64, 16 beyond
+            want = dict(decoder="fused", ndec=4 if h * w <= 64 * 64 else 16) if path == "fused" else _LONG_PATHS[path]
+            yield _case(f"{name}-{lc.DECODERS[mode]}", B, h, w, mode, want, K=K, max_len=L, slot=8 * h * w + 16 + 1024)
+
+
+CASES += list(_long_code_rows())
+CASES += [
+    # the plan's boundary between 64 bits and 65: the same shapes a bit apart
+    _case("1x64x64-max_len64", 1, 64, 64, AUTO, _fused(20, 4, 16, 16, 1, 1, 0, 27632), max_len=64),
+    _case("1x64x64-max_len65", 1, 64, 64, AUTO, dict(decoder="serial", merge="bands", ndec=3, **_merge(16, 16, 1, 1, 0, 27632)), max_len=65),
+    # 64 bits x 5376 symbols + 192 = 344 256 bits: a stage of 43 032 + 144 bytes and three chunk tables of 5379 + 8, each rounded up
+    # to 16, behind the 32 KB LUT
+    _case("40x64x64-max_len64-throughput", 40, 64, 64, THROUGHPUT, _image(256, 43184, 5392, 92128, "one_band", 8, 8, 1, 1, 0, 27632), max_len=64),
+    _case("40x64x64-max_len65-throughput", 40, 64, 64, THROUGHPUT, dict(decoder="serial", merge="one_band", ndec=3), max_len=65),
+    # the self-synchronising decoder's LDS at 64 bits: 21 symbols per coarse cell.  522 cells (72x116): 701 760 bits, a stage of
+    # 87 720 + 144 -> 87 872 bytes and chunk tables of 10 965 + 8 -> 10 976: 32 768 + 87 872 + 32 928 = 153 568 <= 153 600.
+    # 523 cells (4x2092, a prime): 703 104 bits, 88 032 + 3 x 11 008 + 32 768 = 153 824: the split decoder, as for 72x120
+    _case("1x72x116-max_len64-largest-image", 1, 72, 116, THROUGHPUT, dict(decoder="image", ndec=1, image_threads=1024, stage_cap=87872,
+                                                                         chunk_cap=10976, lds_ss=153568), max_len=64),
+    _case("1x4x2092-max_len64-next-cell", 1, 4, 2092, THROUGHPUT, dict(decoder="split", ndec=24, lds_ss=0), max_len=64),
+    _case("1x72x120-max_len64-next-grid", 1, 72, 120, THROUGHPUT, dict(decoder="split", ndec=24, lds_ss=0), max_len=64),
 ]
 FIELDS = ("B", "h", "w", "slot", "K", "has_zq", "max_len", "lut_bits", "mode", "cus", "share", "no_fuse", "lds_decoder")
 
