@@ -122,12 +122,15 @@ class CompressedBatch:
 
     @classmethod
     def from_host(cls, images, mode, h, w, slot, device):
-        """inverse of to_host(): images = list of {name: bytes}"""
+        """inverse of to_host(): images = list of {name: bytes}, each with every stream the mode writes (b"" = an empty file)"""
         B = len(images)
         data = torch.zeros((B, _lib.NUM_STREAMS, slot), dtype=torch.uint8)
         nbytes = torch.full((B, _lib.NUM_STREAMS), -1, dtype=torch.int32)
+        on = mode_streams(mode)
         for b, im in enumerate(images):
             for s, name in enumerate(STREAM_NAMES):
+                if on[s] and name not in im:              # the reference raises FileNotFoundError (model.py:270-275)
+                    raise ValueError(f"stream {name} of image {b} is missing: mode {int(mode)} writes it")
                 if name in im:
                     d = im[name]
                     if len(d) + 8 > slot:

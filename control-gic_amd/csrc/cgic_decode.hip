@@ -1084,7 +1084,7 @@ __device__ __forceinline__ void merge_body(const MergeArgs &a, const Blk blk, un
     float *zq = a.zq ? a.zq + b * 4 * n_f : nullptr;
     float *zq2 = a.zq2 ? a.zq2 + b * 4 * n_f : nullptr;
     uint32_t fcarry = fbase;
-    int bad_index = 0;
+    int bad_index = 0;            // an index outside the codebook, or overlapping masks
     // One thread per QUAD of four consecutive positions of a row (w % 4 == 0): they share their coarse cell and lie in two
     // medium cells, so a quad costs one coarse and two medium rank lookups instead of four of each, and every output is one
     // 16-byte store per plane (the per-position form issued 4-byte stores 8 bytes apart).
@@ -1101,6 +1101,8 @@ __device__ __forceinline__ void merge_body(const MergeArgs &a, const Blk blk, un
             bool bc, bma, bmb, dummy;
             bfa = fine_flag(y, 4 * xq, &bc, &bma);
             bfb = fine_flag(y, 4 * xq + 2, &dummy, &bmb);
+            // a cell both coarse and medium (the reference leaves -1 in the fine mask and in the sum there, :280): refused
+            bad_index |= (int)(mode == 0 && bc && (bma || bmb));
             int64_t vc = 0, va = 0, vb = 0;
             if (bc && use_c) vc = ds_c[(int64_t)pcb[j4 >> 5] + __popc(mcb[j4 >> 5] & ((1u << (j4 & 31)) - 1u)) - off_c];
             if (use_m) {

@@ -405,9 +405,27 @@ int cgic_decode_stream(const cgic_table *t, const uint8_t *in, int64_t nbytes, i
  *   codebook2 device [K, 4] + z_q2 device [B, 4, h, w] fp32: optional second gather of the same
  *           indices from another table -- post_quant_conv(codebook) gives post_quant_conv(quant)
  *           (CGIC.decode needs both, model.py:114-116) without a pass over the latent
- *   status  device [B] int32: 0, or CGIC_ERR_INVALID when a stream's symbol
- *           count does not match its mask / a mask stream has the wrong length
- *           / an index is outside the codebook (the reference raises there)
+ *   status  device [B] int32: 0, or CGIC_ERR_INVALID for an image whose streams
+ *           the reference would refuse: a stream's symbol count does not match
+ *           its mask (more symbols than the grid has cells included), a mask
+ *           stream is not exactly 2 + n/8 bytes with pad 8 - n%8 (an empty one
+ *           included), or -- only when z_q / z_q2 is asked for: the codebook is the
+ *           range the indices are held to -- an index is outside the codebook.
+ *           Stricter than the reference in three cases, all CGIC_ERR_INVALID: a
+ *           non-canonical mask header (pad + 8 and one more byte), mode 0 with a
+ *           cell both coarse and medium (the reference sums -1 there), and an index
+ *           stream of one symbol under a mask with another number of cells (the
+ *           reference broadcasts it).  The other images of the batch are exact.
+ *           What the reference accepts otherwise is accepted with its result: any
+ *           pad count 0..255, trailing bytes under the pad, trailing bits that
+ *           complete no codeword, an empty coarse / medium index file (all zeros).
+ *   nbytes  on the decode side: every stream must satisfy nbytes + 8 <= slot (a
+ *           longer one is a read outside the slot: the caller's error).  -1 on a
+ *           stream the mode writes: an index stream is read as an EMPTY FILE
+ *           (coarse / medium: all zeros; fine: refused where the mask has fine
+ *           cells), a mask stream is CGIC_ERR_INVALID in status.  The Python layer
+ *           does not get there: CompressedBatch.from_host and container.load raise
+ *           ValueError for an absent stream (the reference: FileNotFoundError).
  * ------------------------------------------------------------------------- */
 size_t cgic_compress_slot_bytes(const cgic_table *t, int64_t h, int64_t w);
 size_t cgic_compress_workspace_bytes(int64_t B, int64_t h, int64_t w);

@@ -683,6 +683,13 @@ int cgic_oracle_mode_streams(int mode)
  * them); n* are decoded counts, -1 = the stream file was empty (None).
  * Restates model.py:269-389.  Returns 0, or <0 if a count does not match its
  * mask (the reference raises a shape-mismatch RuntimeError there).
+ * Two things the reference does with malformed input are restated as they are
+ * (tests/golden/malformed.npz):
+ *  - t[t==1] = torch.tensor(decoded) broadcasts a list of ONE symbol over every
+ *    set cell (:287,291,292 and their twins in modes 1-3), whatever the mask's
+ *    count; the .view() of modes 4-6 does not;
+ *  - mode 0 with a cell both coarse and medium: ind_fine = 1 - m - c is -1
+ *    there (:280), the returned fine mask holds it and so does the sum (:293).
  */
 int cgic_oracle_merge(int mode, long h, long w,
                       const int32_t *mc_in, const int32_t *mm_in,
@@ -719,20 +726,21 @@ int cgic_oracle_merge(int mode, long h, long w,
     for (long i = 0; i < h4 * w4; ++i) ec += mc_out[i] == 1;
     for (long i = 0; i < h2 * w2; ++i) em += mm_out[i] == 1;
     for (long i = 0; i < h * w; ++i) ef += mf_out[i] == 1;
-    if (has_c && nc >= 0 && nc != ec) return -11;
-    if (has_m && nm >= 0 && nm != em) return -12;
-    if (has_f && (nf < 0 ? ef != 0 : nf != ef)) return -13;
+    int bc_c = nc == 1 && mode != 4, bc_m = nm == 1 && mode != 5, bc_f = nf == 1 && mode != 6;   /* one symbol: broadcast */
+    if (has_c && nc >= 0 && nc != ec && !bc_c) return -11;
+    if (has_m && nm >= 0 && nm != em && !bc_m) return -12;
+    if (has_f && (nf < 0 ? ef != 0 : (nf != ef && !bc_f))) return -13;
     long ic = 0, im = 0, jf = 0;
     int64_t *gc = (int64_t *)calloc((size_t)(h4 * w4), sizeof(int64_t));
     int64_t *gm = (int64_t *)calloc((size_t)(h2 * w2), sizeof(int64_t));
     if (has_c && nc >= 0)
-        for (long i = 0; i < h4 * w4; ++i) if (mc_out[i] == 1) gc[i] = sc[ic++];
+        for (long i = 0; i < h4 * w4; ++i) if (mc_out[i] == 1) gc[i] = sc[bc_c ? 0 : ic++];
     if (has_m && nm >= 0)
-        for (long i = 0; i < h2 * w2; ++i) if (mm_out[i] == 1) gm[i] = sm[im++];
+        for (long i = 0; i < h2 * w2; ++i) if (mm_out[i] == 1) gm[i] = sm[bc_m ? 0 : im++];
     for (long y = 0; y < h; ++y)
         for (long x = 0; x < w; ++x) {
-            int64_t v = 0;
-            if (has_f && nf >= 0 && mf_out[y * w + x] == 1) v = sf[jf++];
+            int64_t v = mode == 0 ? mf_out[y * w + x] : 0;                     /* ind_fine itself: -1 under an overlap */
+            if (mf_out[y * w + x] == 1) v = has_f && nf >= 0 ? sf[bc_f ? 0 : jf++] : 0;
             v += gm[(y / 2) * w2 + x / 2] + gc[(y / 4) * w4 + x / 4];          /* :293 */
             ind[y * w + x] = v;
         }

@@ -258,6 +258,8 @@ def decompress_image(streams, mode, h, w, htab):
     dec = [decode(htab, streams[STREAM_NAMES[i]]) if on[i] else None for i in range(3)]
     mcd = decode(btab, streams["mask_coarse"]) if on[3] else None
     mmd = decode(btab, streams["mask_medium"]) if on[4] else None
+    if (on[3] and mcd is None) or (on[4] and mmd is None):
+        raise RuntimeError("empty mask file")             # torch.tensor(None) raises (model.py:278-279)
     mc_in = np.ascontiguousarray(mcd, np.int32) if mcd is not None else np.zeros((h // 4) * (w // 4), np.int32)
     mm_in = np.ascontiguousarray(mmd, np.int32) if mmd is not None else np.zeros((h // 2) * (w // 2), np.int32)
     if mc_in.size != (h // 4) * (w // 4) or mm_in.size != (h // 2) * (w // 2):

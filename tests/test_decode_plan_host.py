@@ -116,6 +116,32 @@ CASES += [
     _case("1x4x2092-max_len64-next-cell", 1, 4, 2092, THROUGHPUT, dict(decoder="split", ndec=24, lds_ss=0), max_len=64),
     _case("1x72x120-max_len64-next-grid", 1, 72, 120, THROUGHPUT, dict(decoder="split", ndec=24, lds_ss=0), max_len=64),
 ]
+
+
+# ---- malformed streams: every (B, h, w, table, decoder argument) that tests/test_malformed_streams.py runs, with the path it is meant
+# to reach (malformed_ref.GPU_CASES), and the merge form where the case is there for it.  The slot is the library's for the table.
+def _malformed_rows():
+    import malformed_ref as mr
+    for table, B, h, w, paths in mr.GPU_CASES:
+        K, L = mr.table_shape(table)
+        for mode, path in zip((AUTO, LATENCY, THROUGHPUT), paths):
+            want = dict(decoder="fused", ndec=4 if h * w <= 64 * 64 else 16) if path == "fused" else dict(_LONG_PATHS[path])
+            # the symbols of a grid up to 64x96 are staged in LDS whole, those of 192x192 band by band; "throughput" merges a grid up
+            # to 64x64 in one band of 1024 threads
+            want["stage_sym"] = int(h * w <= 64 * 132)
+            if h * w == 192 * 192:
+                assert path != "image256"
+                want["band_syms"] = 2024
+            if path != "fused":
+                want["merge"] = "one_band" if mode == THROUGHPUT and h * w <= 64 * 64 else "bands"
+            yield _case(f"malformed-{mr.gpu_case_id(table, B, h, w)}-{lc.DECODERS[mode]}", B, h, w, mode, want, K=K, max_len=L,
+                        lut_bits=min(L, lc.LUT_BITS), slot=mr.slot_bytes(L, h, w))
+            if mode == AUTO:                  # the same call without z_q (the index-outside-the-codebook case runs both ways)
+                yield _case(f"malformed-{mr.gpu_case_id(table, B, h, w)}-auto-no_zq", B, h, w, mode, {k: v for k, v in want.items() if k != "band_syms"},
+                            K=0, has_zq=0, max_len=L, lut_bits=min(L, lc.LUT_BITS), slot=mr.slot_bytes(L, h, w))
+
+
+CASES += list(_malformed_rows())
 FIELDS = ("B", "h", "w", "slot", "K", "has_zq", "max_len", "lut_bits", "mode", "cus", "share", "no_fuse", "lds_decoder")
 
 

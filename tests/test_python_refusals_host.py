@@ -101,6 +101,11 @@ def _decompress_rows():
          f"decoder mode 'fast': expected one of {DECODERS}"),
         ("ops.decompress_streams: unknown decoder", lambda: op("fast"), ValueError, f"decoder 'fast': expected one of {DECODERS}"),
         ("ops.decompress_streams: CPU streams", lambda: op(device="cpu"), RuntimeError, CPU_TENSOR),
+        # mode 3 writes the coarse and the medium indices and the coarse mask: image 1 lacks one of them (the reference: FileNotFoundError)
+        ("CompressedBatch.from_host: a stream of the mode is missing",
+         lambda: cg.CompressedBatch.from_host([{"indices_coarse": b"", "indices_medium": b"", "mask_coarse": b""},
+                                               {"indices_coarse": b"", "mask_coarse": b"", "indices_fine": b""}], 3, H, W, 4096, "cuda"),
+         ValueError, "stream indices_medium of image 1 is missing: mode 3 writes it"),
     ]
 
 
