@@ -11,7 +11,9 @@
 //   2. the four waves exchange their 32 per-query maxima through LDS; every wave computes the same new maximum from the same four
 //      numbers, the weights p = exp2((s - m) * scale * log2 e) in fp32, and writes them, rounded once to the operand type, to the
 //      LDS tile P[query][key].  Tail keys get p = 0 by a select (not through exp), and are kept out of the maximum as -inf.
-//      v_max_f32 drops a NaN, so a NaN score arrives through exp2: the query becomes NaN, as in torch.
+//      v_max_f32 drops a NaN, so a NaN score arrives through exp2: the query becomes NaN, as in torch.  A -inf score weighs 0, also
+//      while the maximum itself is still -inf (a leading tile whose keys all score -inf: 0 is subtracted in place of the maximum);
+//      a query whose every key scores -inf ends as 0 / 0 = NaN, one with a +inf score as exp2(inf - inf) = NaN, both as in torch.
 //   3. wave w owns C / 4 channels of O^T[channel][query] += V[channel][128 keys] P^T (MFMA, A = v straight from memory -- a lane's
 //      keys of a channel are consecutive there --, B = P from LDS); the accumulator's column is again the query, so the rescale
 //      of step 2 is a per-lane multiply.
@@ -104,6 +106,18 @@ __device__ __forceinline__ typename T::frag lds_frag(const typename T::raw *p)
     else return *reinterpret_cast<const typename T::frag *>(p);                                   // (rows and offsets are multiples of 16 bytes)
 }
 
+// A weight, or a rescale factor of the accumulator, below 2^-64 of the row's largest weight is taken as exactly 0.  The row sum is at
+// least 1 and the accumulator's own roundings are 2^-24 of its largest term, so such a term is 40 binary orders below what fp32 keeps
+// unless one v is 2^40 times the terms that carry the result.  It must be an exact 0, not merely small: v_mfma_f32_32x32x16_{f16,bf16}
+// returns the predecessor of v * 1 when v is a power of two and its C input is any non-zero number of the opposite sign, however
+// small (1 + -2^-149 gives 1 - 2^-24), so a row whose weight is 1 on one key would miss v's own bits by an ulp.
+constexpr float kNegligible = -64.f;
+
+// exp2 of an exponent that is not below kNegligible (or is NaN): v_exp_f32 itself, which is what exp2f comes down to once its
+// rescaling of results below 2^-126 has nothing to do -- the same bits, and the select against kNegligible costs less than that
+static_assert(kNegligible > -126.f, "v_exp_f32 returns 0 for a denormal result; the select must keep such exponents from it");
+__device__ __forceinline__ float exp2_above_negligible(float x) { return __builtin_amdgcn_exp2f(x); }
+
 // row of the 32x32 result tile that register r of a lane in half h holds (its column is lane & 31)
 __device__ __forceinline__ int tile_row(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
 
@@ -180,12 +194,18 @@ __global__ __launch_bounds__(kAttnThreads) void attn_kernel(const typename T::ra
         __syncthreads();
         const float mn = fmaxf(fmaxf(m, fmaxf(stat[j], stat[32 + j])), fmaxf(stat[64 + j], stat[96 + j]));
         // (0 at the first tile, by a select: m is -inf there, and -inf * c2 is NaN when the scale is 0 or so small that c2 rounds to 0)
-        const float alpha = m == -INFINITY ? 0.f : exp2f((m - mn) * c2);
+        // (... and 0 where it is below 2^-64, like a weight below: see kNegligible)
+        const float ax = (m - mn) * c2;
+        const float alpha = m == -INFINITY || ax < kNegligible ? 0.f : exp2_above_negligible(ax);
+        // (the maximum is still -inf when every key so far scored -inf for this query: s - mn would be NaN.  Against 0 such a key
+        //  weighs exp2(-inf) = 0, as in the reference; a NaN score stays NaN, and so does -inf * c2 when the scale is 0)
+        const float sub = mn == -INFINITY ? 0.f : mn;
         float psum = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = tile_row(r, h);
-            const float p = kw + row < N ? exp2f((s[r] - mn) * c2) : 0.f;
+            const float x = (s[r] - sub) * c2;
+            const float p = kw + row < N && !(x < kNegligible) ? exp2_above_negligible(x) : 0.f;     // (a NaN exponent compares false and goes through exp2)
             psum += p;
             Ps[j * PROW + 32 * w + row] = T::down(p);
         }

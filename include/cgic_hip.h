@@ -716,6 +716,16 @@ int cgic_spatial_norm_one_launch(int in_dtype, int64_t B, int C, int64_t H, int6
  * (v_mfma_f32_32x32x2_f32), never as a half type; fp16 / bf16 inputs on v_mfma_f32_32x32x16_{f16,bf16}, the weights p rounded once
  * to the half type in front of the second product -- as torch's half bmm takes them -- while the row sum adds the unrounded p.
  * NaN: one in q[:, i] makes query i NaN, one in k the whole image, one in v[c, :] channel c -- the reference's pattern.
+ * Infinite scores (an Inf in q or k), as softmax over the whole row has them: a key whose score is -inf weighs 0, wherever it lies
+ * -- also when every key of the leading tiles scores -inf --, and the query is finite if any other key is; a query with a +inf
+ * score, with scores of both signs of inf, or whose every key scores -inf is NaN at every channel; with scale 0 an infinite score is
+ * inf * 0 = NaN.  Finite scores saturate nothing: the maximum is subtracted, so a common offset of thousands changes no weight.
+ * Infinite v: out[c, i] is v[c, :] weighed as IEEE sums do -- +Inf (-Inf) where channel c holds infinities of one sign at keys of
+ * non-zero weight, NaN where it holds both signs, or an infinity at a key whose weight is taken as 0 (0 * inf).
+ * A weight below 2^-64 of the row's largest is taken as exactly 0; a row whose other weights are all below that returns v's own
+ * column of the winning key bit for bit, in the fp32 out as in a half out.
+ * lse on such rows: where ln sum_j exp(scale * s_ij) and the row's softmax weights are finite -- v plays no part -- lse is that number
+ * (a -inf score adds 0 to the sum); on every other row it is non-finite: NaN for a NaN or +inf score, -inf where every key scores -inf.
  * Deterministic: an image's bits depend on its own q, k, v alone (not on B, not on scheduling); no atomics, no workgroup waits for
  * another.  out and lse must overlap no input and not each other (CGIC_ERR_INVALID); a pointer must be aligned to its own element;
  * 16-byte aligned v with N % 8 == 0 gets 16-byte loads, anything else element loads.  Every check precedes the one launch, so a

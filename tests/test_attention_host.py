@@ -5,7 +5,10 @@
   - cg.AttnBlock on CPU tensors takes torch's expression and returns the real encoder block's output bit for bit; adopt() keeps the
     parameter objects and the state_dict keys of the real classes;
   - install() swaps nothing by default and every AttnBlock-shaped module with patch_attention=True;
-  - the op's fake kernel gives shape and dtype; the raw call refuses CPU tensors and mismatched arguments before any pointer is taken.
+  - the op's fake kernel gives shape and dtype; the raw call refuses CPU tensors and mismatched arguments before any pointer is taken;
+  - the catalogue of infinite and saturated scores (attention_ref.SCORE_CASES): the restatement has the same NaN / +Inf / -Inf patterns
+    in fp32 as in float64, the ones spelled out by index; the kernel's tile loop in torch ops (attention_ref.tiled_model) meets every
+    pattern and bar of tests/test_attention_scores.py, and without the guard of a leading all -inf tile fails exactly cases a, c, g.
 """
 import inspect
 
@@ -197,3 +200,56 @@ def test_the_raw_call_refuses_before_it_takes_a_pointer():
             cg.attention(q, q, q, out_dtype=torch.float16)
         with pytest.raises(TypeError, match="result type"):
             cg.attention(q.half(), q.half(), q.half(), out_dtype=torch.bfloat16)
+
+
+# ---- infinite and saturated scores: the catalogue of tests/attention_ref.py without a device
+_score = {}
+_ids = [f"{name}-C{C}-{str(dt).split('.')[1]}" for name, C, dt in ref.SCORE_PARAMS]
+
+
+def score_case(name, C, dtype):
+    """(the built case, its references on the CPU): made once, shared, never changed"""
+    key = (name, C, dtype)
+    if key not in _score:
+        c = ref.build_case(name, C, dtype)
+        _score[key] = (c, ref.case_refs(c))
+    return _score[key]
+
+
+@pytest.mark.parametrize("name,C,dtype", ref.SCORE_PARAMS, ids=_ids)
+def test_float64_is_a_fair_reference_on_the_score_catalogue(name, C, dtype):
+    """the restatement in fp32 puts NaN, +Inf and -Inf where the restatement in float64 puts them, and both where the case spells
+    them out by index: on these inputs the patterns do not depend on the precision of the reference"""
+    c, r = score_case(name, C, dtype)
+    r32 = ref.restatement(c.q, c.k, c.v, c.scale, dtype=torch.float32)
+    assert ref.same_patterns(r32, r.r64)
+    assert ref.same_patterns(r.r64, c.expect) and ref.same_patterns(r32, c.expect)
+    assert bool(torch.isfinite(r.r64[1]).all())                                  # image 1 is clean
+    if name == "n":
+        print(f"one-hot rows: the largest runner-up weight in float64 is {r.runner_up:.3e}")
+        assert r.runner_up < 2.0 ** -60
+
+
+@pytest.mark.parametrize("name,C,dtype", ref.SCORE_PARAMS, ids=_ids)
+def test_the_tile_loop_with_the_guard_meets_every_pattern_and_bar(name, C, dtype):
+    """the kernel's algorithm (attention_ref.tiled_model, guard=True) passes what tests/test_attention_scores.py asks of the kernel:
+    the bars are conditions the algorithm can meet"""
+    c, r = score_case(name, C, dtype)
+    out, lse = ref.tiled_model(c.q, c.k, c.v, c.scale, guard=True)
+    ref.judge(c, r, out, lse, f"tile loop, {name} C{C} {dtype}")
+
+
+def test_without_the_guard_the_tile_loop_fails_exactly_the_leading_inf_tile_cases():
+    """guard=False is the kernel's arithmetic before the fix: exp2(-inf - -inf) in a leading tile whose scores are all -inf.  It must
+    fail the pattern check on cases a, c and g at every width and type, and on no other case: the catalogue catches this class of
+    error, and nothing else in it depends on the guard"""
+    failed, passed = set(), set()
+    for name, C, dtype in ref.SCORE_PARAMS:
+        c, r = score_case(name, C, dtype)
+        out, lse = ref.tiled_model(c.q, c.k, c.v, c.scale, guard=False)
+        ok = ref.same_patterns(out, c.expect)
+        if not ok:
+            nan = int(torch.isnan(out[0]).any(dim=0).sum())
+            print(f"{name} C{C} {dtype}: NaN at {nan} of {c.N} queries of image 0, the reference at {int(c.expect[0][0].any(dim=0).sum())}")
+        (passed if ok else failed).add(name)
+    assert failed == set(ref.LEADING_INF_TILE) and not (failed & passed)
