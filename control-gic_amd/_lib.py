@@ -171,6 +171,11 @@ PROTOTYPES = {
                                  _vp, _sz, _vp]),
     "cgic_spatial_norm_workspace_bytes": (_sz, [_int, _i64, _int, _i64, _i64, _int]),
     "cgic_spatial_norm_one_launch": (_int, [_int, _i64, _int, _i64, _i64, _int]),
+    "cgic_spatial_norm_train": (_int, [_vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                       _int, _vp, _vp, _sz, _vp]),
+    "cgic_spatial_norm_backward": (_int, [_vp, _int, _vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cgic_spatial_norm_backward_workspace_bytes": (_sz, [_int, _i64, _int, _i64, _i64, _int]),
     "cgic_attention": (_int, [_vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _i64, _i64, _f64, _vp, _int, _vp, _vp, _sz, _vp]),
     "cgic_attention_workspace_bytes": (_sz, [_int, _i64, _int, _i64]),
     "cgic_attention_supported": (_int, [_int, _int, _i64, _int, _i64]),

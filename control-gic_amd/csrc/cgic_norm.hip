@@ -25,6 +25,7 @@
 // are loaded once and serve every x of the thread that falls on that pixel.  The index divisions (by the row width and the two ratios) are multiplications by the plan's magic numbers.
 // Every element is read before it is written in both forms, so out may be f.
 #include "cgic_common.h"
+#include "cgic_norm_bwd_plan.h"
 #include "cgic_norm_plan.h"
 
 namespace cgic {
@@ -227,7 +228,7 @@ __device__ __forceinline__ void apply_units(const typename T::raw *src, void *ou
 
 // ---- one launch: one workgroup per span
 template <class T, bool HOUT, int U>
-__global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typename T::raw *f, Geom g, unsigned span_bytes16, void *out)
+__global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typename T::raw *f, Geom g, unsigned span_bytes16, void *out, float *stats)
 {
     using E = typename T::raw;
     extern __shared__ __attribute__((aligned(16))) unsigned char norm_lds[];
@@ -255,6 +256,7 @@ __global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typenam
     for (int k = 0; k < nw; ++k) { t1 += part[2 * k]; t2 += part[2 * k + 1]; }
     float mean, rstd;
     finish_stats(K, t1, t2, (double)span, g.eps, &mean, &rstd);
+    if (stats && threadIdx.x == 0) { stats[2 * spn] = mean; stats[2 * spn + 1] = rstd; }       // (the training forward)
     // apply from LDS: a wave takes one channel, or 256 units of one, at a time
     const int64_t b = spn / g.groups;
     const int grp = (int)(spn - b * g.groups);
@@ -306,7 +308,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_stats_kernel(const typename
 
 template <class T, bool HOUT, int U>
 __global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename T::raw *f, Geom g, const double *ws, int chunks, int64_t spans,
-                                                                  int64_t items, unsigned parts, void *out)
+                                                                  int64_t items, unsigned parts, void *out, float *stats)
 {
     const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_units = plane / U;
     const double n = (double)g.cpg * (double)plane;
@@ -322,6 +324,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename
         for (int k = 0; k < chunks; ++k) { t1 += p[2 * k]; t2 += p[2 * k + 1]; }
         float mean, rstd;
         finish_stats(ws[spans * chunks * 2 + spn], t1, t2, n, g.eps, &mean, &rstd);
+        if (stats && part == 0 && c % g.cpg == 0 && threadIdx.x == 0) { stats[2 * spn] = mean; stats[2 * spn + 1] = rstd; }
         const Chan w = load_chan(g, c);
         const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
         const unsigned first = part * (unsigned)kNormPartUnits;
@@ -332,7 +335,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename
 
 // ---- the launches: the plan's form and unit and the call's type pair pick the instantiation
 template <class T, bool HOUT, int U>
-static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, hipStream_t s)
+static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, float *stats, hipStream_t s)
 {
     using E = const typename T::raw *;
     if (p.form == 1) {
@@ -340,7 +343,7 @@ static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, hipS
         const int rc = ensure_lds_above_48k((const void *)kernel, p.lds_bytes);
         if (rc) return rc;
         const unsigned span_bytes16 = (unsigned)(p.lds_bytes - 2 * sizeof(double) * (size_t)(kNormOneThreads / kWave));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid_one), dim3(p.threads_one), p.lds_bytes, s, (E)c.f, g, span_bytes16, (void *)c.out);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid_one), dim3(p.threads_one), p.lds_bytes, s, (E)c.f, g, span_bytes16, (void *)c.out, stats);
         return launch_check("norm_one_kernel");
     }
     const unsigned units = (unsigned)(p.span / U);
@@ -349,19 +352,323 @@ static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, hipS
     int rc = launch_check("norm_stats_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL((norm_apply_kernel<T, HOUT, U>), dim3((unsigned)p.grid_apply), dim3(p.threads), 0, s, (E)c.f, g,
-                       (const double *)c.workspace, p.chunks, p.spans, c.B * c.C * p.parts, (unsigned)p.parts, (void *)c.out);
+                       (const double *)c.workspace, p.chunks, p.spans, c.B * c.C * p.parts, (unsigned)p.parts, (void *)c.out, stats);
     return launch_check("norm_apply_kernel");
 }
 
 template <class T, bool HOUT>
-static int launch_typed(const NormCall &c, const NormPlan &p, const Geom &g, hipStream_t s)
+static int launch_typed(const NormCall &c, const NormPlan &p, const Geom &g, float *stats, hipStream_t s)
 {
     if constexpr (sizeof(typename T::raw) == 2)
-        if (p.unit == 8) return launch_unit<T, HOUT, 8>(c, p, g, s);
+        if (p.unit == 8) return launch_unit<T, HOUT, 8>(c, p, g, stats, s);
     switch (p.unit) {
-    case 4: return launch_unit<T, HOUT, 4>(c, p, g, s);
-    case 2: return launch_unit<T, HOUT, 2>(c, p, g, s);
-    default: return launch_unit<T, HOUT, 1>(c, p, g, s);
+    case 4: return launch_unit<T, HOUT, 4>(c, p, g, stats, s);
+    case 2: return launch_unit<T, HOUT, 2>(c, p, g, stats, s);
+    default: return launch_unit<T, HOUT, 1>(c, p, g, stats, s);
+    }
+}
+
+// ================================================================================================================ the backward
+// With go the incoming gradient and mean, rstd the training forward's (stats), per element in fp32, v recomputed as the forward does:
+//     xhat = (x - mean) * rstd;  n = xhat * gamma[c] + beta[c];  y, b as above;  v = n * y + b
+//     gv = go, with swish go * (s * (1 + v * (1 - s))), s = 1 / (1 + exp(-v));     gn = gv * y;  gy = gv * n
+//     df = rstd * ((gamma[c] * gn - S1 / N) - xhat * (S2 / N)),   S1 = sum_c gamma[c] sum_p gn,  S2 = sum_c gamma[c] sum_p gn * xhat
+//     dbeta = sum gn, dgamma = sum gn * xhat, dby = sum gy, dbb = sum gv, dwy[k] = sum gy * z_k, dwb[k] = sum gv * z_k   (over b, p)
+//     dz_k(b, p) = sum_c wy[c,k] * gy + wb[c,k] * gv, folded through the nearest index into dzq
+// Every sum is accumulated in float64 in an order that cgic_norm_bwd_plan.h fixes (three launches ordered by the stream: reduce,
+// finish, apply; no atomics), so two calls give the same bits and an image's df and dzq do not depend on its batch.  A NaN in f
+// reaches every gradient it reaches in the reference: nothing here selects, clamps or skips by value.
+struct BwdGeom {
+    Geom g;
+    const float *stats;             // [B * groups][2] = (mean, rstd)
+    int chan_block, chan_blocks, tiles, need_dz, need_conv, need_df;
+    double *sums;                   // workspace: [B][C][tiles][12]
+    double *span;                   //            [B][C][2] = gamma_c * (sum gn, sum gn * xhat) of the plane
+    float *dz;                      //            [B][chan_blocks][4][H * W]
+};
+
+// U consecutive elements of go: one access, or two of 16 bytes (8 floats)
+template <class E, int U>
+__device__ __forceinline__ void load_go(const E *p, E (&v)[U])
+{
+    if constexpr (sizeof(E) * U == 32) {
+        E lo[U / 2], hi[U / 2];
+        load_n<E, U / 2>(p, lo);
+        load_n<E, U / 2>(p + U / 2, hi);
+#pragma unroll
+        for (int j = 0; j < U / 2; ++j) { v[j] = lo[j]; v[U / 2 + j] = hi[j]; }
+    } else {
+        load_n<E, U>(p, v);
+    }
+}
+
+// zq's four values at each of the U pixels of the unit at (y, x)
+template <int U>
+__device__ __forceinline__ void load_z(const Geom &g, const float *zq_b, unsigned y, unsigned x, float (&z)[kNormZq][U])
+{
+    const unsigned plane_q = (unsigned)g.hq * (unsigned)g.wq;
+    const unsigned sy = fdiv(y * (unsigned)g.ymul, g.mg_y, (unsigned)g.ydiv);
+    const float *zrow = zq_b + (size_t)sy * (unsigned)g.wq;
+    if (g.zq_vec) {
+#pragma unroll
+        for (int k = 0; k < kNormZq; ++k) {
+            float row[U];                           // (element by element into z: a block copy into a row of it would keep z in scratch)
+            load_zq<U>(zrow + (size_t)k * plane_q + x, row);
+#pragma unroll
+            for (int j = 0; j < U; ++j) z[k][j] = row[j];
+        }
+    } else {
+        const unsigned acc = x * (unsigned)g.xmul;
+        unsigned sx = fdiv(acc, g.mg_x, (unsigned)g.xdiv), rem = acc - sx * (unsigned)g.xdiv;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+#pragma unroll
+            for (int k = 0; k < kNormZq; ++k) z[k][j] = (j == 0 || rem == 0) ? zrow[(size_t)k * plane_q + sx] : z[k][j > 0 ? j - 1 : 0];
+            if (g.xdiv == 1) {
+                sx += (unsigned)g.xmul;
+            } else if (++rem == (unsigned)g.xdiv) {
+                rem = 0;
+                ++sx;
+            }
+        }
+    }
+}
+
+// the terms of one element
+struct Terms {
+    float xhat, n, y, gv;
+};
+__device__ __forceinline__ Terms bwd_terms(const Chan &w, int swish, float x, float mean, float rstd, float go, float z0, float z1, float z2, float z3)
+{
+    const float z[kNormZq] = {z0, z1, z2, z3};
+    float yv = w.by, bv = w.bb;
+#pragma unroll
+    for (int k = 0; k < kNormZq; ++k) {
+        yv = yv + w.wy[k] * z[k];
+        bv = bv + w.wb[k] * z[k];
+    }
+    Terms t;
+    t.xhat = (x - mean) * rstd;
+    t.n = t.xhat * w.gamma + w.beta;
+    t.y = yv;
+    t.gv = go;
+    if (swish) {
+        const float v = t.n * yv + bv;
+        const float sg = 1.0f / (1.0f + expf(-v));
+        t.gv = go * (sg * (1.0f + v * (1.0f - sg)));
+    }
+    return t;
+}
+
+// ---- reduce: workgroup (b, channel block, pixel tile); a thread keeps one unit of pixels and walks the block's channels
+template <class T, class G, int U>
+__global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_reduce_kernel(const typename T::raw *f, const typename G::raw *go, BwdGeom a)
+{
+    __shared__ double part[kNormBwdChanBlock][kNormBwdThreads / kWave][kNormBwdSums];
+    const Geom &g = a.g;
+    const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_units = plane / U;
+    const unsigned tile = blockIdx.x % (unsigned)a.tiles, rest = blockIdx.x / (unsigned)a.tiles;
+    const unsigned cb = rest % (unsigned)a.chan_blocks;
+    const int64_t b = rest / (unsigned)a.chan_blocks;
+    const unsigned u = tile * blockDim.x + threadIdx.x;
+    const bool live = u < plane_units;
+    const unsigned e = live ? u * U : 0u;
+    const unsigned y = fdiv(e, g.mg_w, (unsigned)g.W), x = e - y * (unsigned)g.W;
+    const int wave = (int)(threadIdx.x >> 6), lane = lane_id(), nw = (int)(blockDim.x >> 6);
+    float z[kNormZq][U];
+    load_z<U>(g, g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq, y, x, z);      // (a thread without a unit: the plane's first)
+    double dz[kNormZq][U];
+#pragma unroll
+    for (int k = 0; k < kNormZq; ++k)
+#pragma unroll
+        for (int j = 0; j < U; ++j) dz[k][j] = 0.0;
+    const int c0 = (int)cb * a.chan_block, c1 = c0 + a.chan_block < g.C ? c0 + a.chan_block : g.C;
+    const unsigned nsum = a.need_conv ? (unsigned)kNormBwdSums : 2u;       // sums per channel that are added, written and later read
+    for (int c = c0; c < c1; ++c) {
+        const Chan w = load_chan(g, c);
+        const int64_t spn = b * g.groups + c / g.cpg;
+        const float mean = a.stats[2 * spn], rstd = a.stats[2 * spn + 1];
+        double s[kNormBwdSums];
+#pragma unroll
+        for (int i = 0; i < kNormBwdSums; ++i) s[i] = 0.0;
+        if (live) {
+            const int64_t at = (b * g.C + c) * (int64_t)plane + e;
+            typename T::raw fv[U];
+            typename G::raw gov[U];
+            load_n<typename T::raw, U>(f + at, fv);
+            load_go<typename G::raw, U>(go + at, gov);
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
+                const float gn = t.gv * t.y, gy = t.gv * t.n;
+                s[0] += (double)gn;
+                s[1] += (double)(gn * t.xhat);
+                if (a.need_conv) {
+                    s[2] += (double)gy;
+                    s[3] += (double)t.gv;
+                }
+#pragma unroll
+                for (int k = 0; k < kNormZq; ++k) {
+                    if (a.need_conv) {
+                        s[4 + k] += (double)(gy * z[k][j]);
+                        s[8 + k] += (double)(t.gv * z[k][j]);
+                    }
+                    if (a.need_dz) dz[k][j] += (double)(w.wy[k] * gy + w.wb[k] * t.gv);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kNormBwdSums; ++i) {
+            if ((unsigned)i >= nsum) break;                   // (no conv gradient is wanted: the first two sums only)
+            const double t = wave_sum(s[i]);
+            if (lane == 0) part[c - c0][wave][i] = t;
+        }
+    }
+    __syncthreads();
+    // the waves in wave order: one thread per (channel, sum)
+    for (unsigned i = threadIdx.x; i < (unsigned)(c1 - c0) * nsum; i += blockDim.x) {
+        const unsigned cl = i / nsum, j = i - cl * nsum;
+        double t = 0.0;
+        for (int wv = 0; wv < nw; ++wv) t += part[cl][wv][j];
+        a.sums[(((b * g.C + c0 + (int)cl) * a.tiles + tile) * kNormBwdSums) + j] = t;
+    }
+    if (a.need_dz && live) {
+#pragma unroll
+        for (int k = 0; k < kNormZq; ++k) {
+            float o[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) o[j] = (float)dz[k][j];
+            store_out<F32, false, U>(a.dz, ((b * a.chan_blocks + cb) * kNormZq + k) * (int64_t)plane + e, o);
+        }
+    }
+}
+
+// ---- finish: the first `grid_sums` workgroups hold a thread per (channel, sum), the others a thread per element of dzq
+__global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_finish_kernel(BwdGeom a, int64_t B, unsigned grid_sums, float *dgamma, float *dbeta,
+                                                                          float *dwy, float *dby, float *dwb, float *dbb, float *dzq)
+{
+    const Geom &g = a.g;
+    if (blockIdx.x < grid_sums) {
+        const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= (unsigned)g.C * kNormBwdSums) return;
+        const unsigned c = i / kNormBwdSums, j = i - c * kNormBwdSums;
+        if (j >= 2 && !a.need_conv) return;         // (reduce did not write these)
+        const double gamma = (double)g.gamma[c];
+        double total = 0.0;
+        for (int64_t b = 0; b < B; ++b) {
+            const double *src = a.sums + (b * g.C + c) * a.tiles * kNormBwdSums + j;
+            double s = 0.0;
+            for (int t = 0; t < a.tiles; ++t) s += src[(int64_t)t * kNormBwdSums];
+            if (j < 2 && a.need_df) a.span[(b * g.C + c) * 2 + j] = gamma * s;
+            total += s;
+        }
+        float *dst = j == 0 ? dbeta : j == 1 ? dgamma : j == 2 ? dby : j == 3 ? dbb : j < 4 + kNormZq ? dwy : dwb;
+        if (dst) dst[j < 4 ? c : c * kNormZq + ((j - 4) & (kNormZq - 1))] = (float)total;
+        return;
+    }
+    const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_q = (unsigned)g.hq * (unsigned)g.wq;
+    const int64_t i = (int64_t)(blockIdx.x - grid_sums) * blockDim.x + threadIdx.x;
+    if (i >= B * kNormZq * (int64_t)plane_q) return;
+    const int64_t bk = i / plane_q;
+    const unsigned pix = (unsigned)(i - bk * plane_q), k = (unsigned)(bk & (kNormZq - 1));
+    const int64_t b = bk / kNormZq;
+    const unsigned sy = pix / (unsigned)g.wq, sx = pix - sy * (unsigned)g.wq;
+    // the feature pixels that read this element: a ydiv x xdiv block where the axis is up-sampled; one or none where it is sub-sampled
+    const bool hit = sy % (unsigned)g.ymul == 0 && sx % (unsigned)g.xmul == 0;
+    const unsigned y0 = g.ymul > 1 ? sy / (unsigned)g.ymul : sy * (unsigned)g.ydiv, x0 = g.xmul > 1 ? sx / (unsigned)g.xmul : sx * (unsigned)g.xdiv;
+    double t = 0.0;
+    if (hit)
+        for (int cb = 0; cb < a.chan_blocks; ++cb) {
+            const float *src = a.dz + ((b * a.chan_blocks + cb) * kNormZq + k) * (int64_t)plane;
+            for (unsigned dy = 0; dy < (unsigned)g.ydiv; ++dy)
+                for (unsigned dx = 0; dx < (unsigned)g.xdiv; ++dx) t += (double)src[(size_t)(y0 + dy) * (unsigned)g.W + x0 + dx];
+        }
+    dzq[i] = (float)t;
+}
+
+// ---- apply: the forward's grid; df of a unit is written after go's unit was read, so df may be go
+template <class T, class G, bool HOUT, int U>
+__global__ __launch_bounds__(kNormThreads) void norm_bwd_apply_kernel(const typename T::raw *f, const typename G::raw *go, BwdGeom a, int64_t items,
+                                                                      unsigned parts, void *df)
+{
+    const Geom &g = a.g;
+    const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_units = plane / U;
+    const double n = (double)g.cpg * (double)plane;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int64_t bc = it / parts;
+        const unsigned part = (unsigned)(it - bc * parts);
+        const int64_t b = bc / g.C;
+        const int c = (int)(bc - b * g.C), grp = c / g.cpg;
+        const int64_t spn = b * g.groups + grp;
+        // S1, S2: the group's channels in channel order (uniform)
+        const double *sp = a.span + (b * g.C + (int64_t)grp * g.cpg) * 2;
+        double s1 = 0.0, s2 = 0.0;
+        for (int cl = 0; cl < g.cpg; ++cl) { s1 += sp[2 * cl]; s2 += sp[2 * cl + 1]; }
+        const float m1 = (float)(s1 / n), m2 = (float)(s2 / n);
+        const float mean = a.stats[2 * spn], rstd = a.stats[2 * spn + 1];
+        const Chan w = load_chan(g, c);
+        const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
+        const unsigned first = part * (unsigned)kNormPartUnits;
+        const unsigned last = first + (unsigned)kNormPartUnits < plane_units ? first + (unsigned)kNormPartUnits : plane_units;
+        for (unsigned i = first + threadIdx.x; i < last; i += blockDim.x) {
+            const unsigned e = i * U;
+            const unsigned y = fdiv(e, g.mg_w, (unsigned)g.W), x = e - y * (unsigned)g.W;
+            float z[kNormZq][U];
+            load_z<U>(g, zq_b, y, x, z);
+            typename T::raw fv[U];
+            typename G::raw gov[U];
+            load_n<typename T::raw, U>(f + bc * (int64_t)plane + e, fv);
+            load_go<typename G::raw, U>(go + bc * (int64_t)plane + e, gov);
+            float o[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
+                const float gn = t.gv * t.y;
+                o[j] = rstd * ((w.gamma * gn - m1) - t.xhat * m2);
+                // a half df is the fp32 value rounded once more: the fp32 product has to exist.  Left to itself the compiler folds the
+                // multiplication into the conversion (v_fma_mixlo_f16: one rounding of the exact product), and where the fp32 value
+                // lies halfway between two halves the result is no longer .to(half) of the fp32 df
+                if constexpr (HOUT) asm volatile("" : "+v"(o[j]));
+            }
+            store_out<T, HOUT, U>(df, bc * (int64_t)plane + e, o);
+        }
+    }
+}
+
+template <class T, class G, int U>
+static int bwd_launch_unit(const NormBwdCall &c, const NormBwdPlan &p, const BwdGeom &a, hipStream_t s)
+{
+    using E = const typename T::raw *;
+    using EG = const typename G::raw *;
+    hipLaunchKernelGGL((norm_bwd_reduce_kernel<T, G, U>), dim3((unsigned)p.grid_reduce), dim3(p.threads_reduce), 0, s, (E)c.f, (EG)c.go, a);
+    int rc = launch_check("norm_bwd_reduce_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(norm_bwd_finish_kernel, dim3((unsigned)(p.grid_sums + p.grid_dzq)), dim3(kNormBwdThreads), 0, s, a, c.B, (unsigned)p.grid_sums,
+                       (float *)c.dgn_weight, (float *)c.dgn_bias, (float *)c.dwy, (float *)c.dby, (float *)c.dwb, (float *)c.dbb, (float *)c.dzq);
+    rc = launch_check("norm_bwd_finish_kernel");
+    if (rc || !p.grid_apply) return rc;
+    const int64_t items = c.B * c.C * p.parts;
+    if constexpr (sizeof(typename T::raw) == 2) {
+        if (c.df_dtype != CGIC_DT_F32) {
+            hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, true, U>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
+                               (unsigned)p.parts, (void *)c.df);
+            return launch_check("norm_bwd_apply_kernel");
+        }
+    }
+    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, false, U>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
+                       (unsigned)p.parts, (void *)c.df);
+    return launch_check("norm_bwd_apply_kernel");
+}
+
+template <class T, class G>
+static int bwd_launch_typed(const NormBwdCall &c, const NormBwdPlan &p, const BwdGeom &a, hipStream_t s)
+{
+    if constexpr (sizeof(typename T::raw) == 2)
+        if (p.unit == 8) return bwd_launch_unit<T, G, 8>(c, p, a, s);
+    switch (p.unit) {
+    case 4: return bwd_launch_unit<T, G, 4>(c, p, a, s);
+    case 2: return bwd_launch_unit<T, G, 2>(c, p, a, s);
+    default: return bwd_launch_unit<T, G, 1>(c, p, a, s);
     }
 }
 
@@ -370,12 +677,12 @@ static int launch_typed(const NormCall &c, const NormPlan &p, const Geom &g, hip
 
 using namespace cgic;
 
-extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
-                                 int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy, const float *by,
-                                 const float *wb, const float *bb, int swish, void *out, int out_dtype, void *workspace,
-                                 size_t workspace_bytes, cgic_stream_t stream)
+// the forward and the training forward (stats != NULL also writes the groups' mean and rstd): the same plan, the same kernels
+static int norm_forward(const char *name, bool train, const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq,
+                        int64_t hq, int64_t wq, int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy,
+                        const float *by, const float *wb, const float *bb, int swish, void *out, int out_dtype, float *stats, void *workspace,
+                        size_t workspace_bytes, cgic_stream_t stream)
 {
-    CGIC_NOT_IN_GROUP("cgic_spatial_norm");
     NormCall c{};
     c.in_dtype = in_dtype; c.out_dtype = out_dtype; c.B = B; c.C = C; c.H = H; c.W = W; c.hq = hq; c.wq = wq; c.groups = groups;
     c.f = (uintptr_t)f; c.zq = (uintptr_t)zq; c.gn_weight = (uintptr_t)gn_weight; c.gn_bias = (uintptr_t)gn_bias;
@@ -383,9 +690,9 @@ extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, 
     c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes;
     NormPlan p;
     const char *why = "";
-    const int rc = norm_plan(c, &p, &why);
+    const int rc = train ? norm_train_plan(c, (uintptr_t)stats, &p, &why) : norm_plan(c, &p, &why);
     CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
-    CGIC_REQUIRE(eps >= 0.0, CGIC_ERR_INVALID, "spatial_norm: eps %g", eps);
+    CGIC_REQUIRE(eps >= 0.0, CGIC_ERR_INVALID, "%s: eps %g", name, eps);
     if (p.form == 0) return CGIC_OK;
     norm::Geom g{};
     g.C = C; g.groups = groups; g.cpg = C / groups; g.H = (int)H; g.W = (int)W; g.hq = (int)hq; g.wq = (int)wq;
@@ -394,9 +701,72 @@ extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, 
     g.zq = zq; g.gamma = gn_weight; g.beta = gn_bias; g.wy = wy; g.by = by; g.wb = wb; g.bb = bb;
     const hipStream_t s = (hipStream_t)stream;
     const bool hout = out_dtype != CGIC_DT_F32;
-    if (in_dtype == CGIC_DT_F32) return norm::launch_typed<norm::F32, false>(c, p, g, s);
-    if (in_dtype == CGIC_DT_F16) return hout ? norm::launch_typed<norm::F16, true>(c, p, g, s) : norm::launch_typed<norm::F16, false>(c, p, g, s);
-    return hout ? norm::launch_typed<norm::BF16, true>(c, p, g, s) : norm::launch_typed<norm::BF16, false>(c, p, g, s);
+    if (in_dtype == CGIC_DT_F32) return norm::launch_typed<norm::F32, false>(c, p, g, stats, s);
+    if (in_dtype == CGIC_DT_F16) return hout ? norm::launch_typed<norm::F16, true>(c, p, g, stats, s) : norm::launch_typed<norm::F16, false>(c, p, g, stats, s);
+    return hout ? norm::launch_typed<norm::BF16, true>(c, p, g, stats, s) : norm::launch_typed<norm::BF16, false>(c, p, g, stats, s);
+}
+
+extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
+                                 int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy, const float *by,
+                                 const float *wb, const float *bb, int swish, void *out, int out_dtype, void *workspace,
+                                 size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_spatial_norm");
+    return norm_forward("spatial_norm", false, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish, out,
+                        out_dtype, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cgic_spatial_norm_train(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq,
+                                       int64_t wq, int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy,
+                                       const float *by, const float *wb, const float *bb, int swish, void *out, int out_dtype, float *stats,
+                                       void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_spatial_norm_train");
+    return norm_forward("spatial_norm_train", true, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish,
+                        out, out_dtype, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cgic_spatial_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W,
+                                          const float *zq, int64_t hq, int64_t wq, int groups, const float *stats, const float *gn_weight,
+                                          const float *gn_bias, const float *wy, const float *by, const float *wb, const float *bb, int swish,
+                                          void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
+                                          float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_spatial_norm_backward");
+    NormBwdCall c{};
+    c.in_dtype = in_dtype; c.go_dtype = go_dtype; c.df_dtype = df_dtype;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.hq = hq; c.wq = wq; c.groups = groups;
+    c.f = (uintptr_t)f; c.go = (uintptr_t)go; c.zq = (uintptr_t)zq; c.stats = (uintptr_t)stats; c.gn_weight = (uintptr_t)gn_weight;
+    c.gn_bias = (uintptr_t)gn_bias; c.wy = (uintptr_t)wy; c.by = (uintptr_t)by; c.wb = (uintptr_t)wb; c.bb = (uintptr_t)bb;
+    c.df = (uintptr_t)df; c.dzq = (uintptr_t)dzq; c.dgn_weight = (uintptr_t)dgn_weight; c.dgn_bias = (uintptr_t)dgn_bias;
+    c.dwy = (uintptr_t)dwy; c.dby = (uintptr_t)dby; c.dwb = (uintptr_t)dwb; c.dbb = (uintptr_t)dbb;
+    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes;
+    NormBwdPlan p;
+    const char *why = "";
+    const int rc = norm_bwd_plan(c, &p, &why);
+    CGIC_REQUIRE(rc == CGIC_OK, rc, "%s", why);
+    norm::BwdGeom a{};
+    norm::Geom &g = a.g;
+    g.C = C; g.groups = groups; g.cpg = C / groups; g.H = (int)H; g.W = (int)W; g.hq = (int)hq; g.wq = (int)wq;
+    g.ymul = p.ymul; g.ydiv = p.ydiv; g.xmul = p.xmul; g.xdiv = p.xdiv; g.mg_w = p.mg_w; g.mg_y = p.mg_y; g.mg_x = p.mg_x; g.zq_vec = p.zq_vec ? 1 : 0;
+    g.swish = swish ? 1 : 0;
+    g.zq = zq; g.gamma = gn_weight; g.beta = gn_bias; g.wy = wy; g.by = by; g.wb = wb; g.bb = bb;
+    a.stats = stats; a.chan_block = p.chan_block; a.chan_blocks = (int)p.chan_blocks; a.tiles = (int)p.tiles; a.need_dz = p.need_dz ? 1 : 0;
+    a.need_conv = p.need_conv ? 1 : 0; a.need_df = p.need_df ? 1 : 0;
+    unsigned char *ws = (unsigned char *)workspace;
+    a.sums = (double *)(ws + p.off_sums); a.span = (double *)(ws + p.off_span); a.dz = (float *)(ws + p.off_dz);
+    const hipStream_t s = (hipStream_t)stream;
+    const bool hgo = go_dtype != CGIC_DT_F32;
+    if (in_dtype == CGIC_DT_F32) return norm::bwd_launch_typed<norm::F32, norm::F32>(c, p, a, s);
+    if (in_dtype == CGIC_DT_F16) return hgo ? norm::bwd_launch_typed<norm::F16, norm::F16>(c, p, a, s) : norm::bwd_launch_typed<norm::F16, norm::F32>(c, p, a, s);
+    return hgo ? norm::bwd_launch_typed<norm::BF16, norm::BF16>(c, p, a, s) : norm::bwd_launch_typed<norm::BF16, norm::F32>(c, p, a, s);
+}
+
+extern "C" size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)
+{
+    NormBwdPlan p;
+    const char *why = "";
+    return norm_bwd_shape(in_dtype, B, C, H, W, groups, &p, &why) == CGIC_OK ? p.workspace_needed : 0;
 }
 
 extern "C" size_t cgic_spatial_norm_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)

@@ -1,0 +1,242 @@
+// cgic_norm_bwd_plan.h -- what one call of cgic_spatial_norm_train / cgic_spatial_norm_backward does, decided before anything is
+// enqueued: every check of the call, the unit, the layout of the partial sums in the workspace, the order in which they are added
+// and the three grids.  Plain C++17 like cgic_norm_plan.h (no HIP include, pointers are plain addresses): norm_bwd_plan() is a pure
+// function of a NormBwdCall (tests/host/norm_bwd_plan_main.cpp).
+//
+// The backward is three launches ordered by the stream; no workgroup waits for another and nothing is added atomically:
+//   reduce   grid (b, channel block, pixel tile).  A tile is `threads_reduce` units of `unit` consecutive pixels of a row; a thread
+//            keeps its unit and walks the block's `chan_block` channels.  Per channel the workgroup adds the twelve plane sums
+//            (lanes by shuffles, then the waves in wave order) and writes them to sums[b][c][tile][12] (float64); per pixel the
+//            thread adds the channels' dz_k in channel order and writes dz[b][block][k][pixel] (fp32).
+//   finish   thread (c, j) adds sums[b][c][0..tiles)[j] in tile order, writes gamma_c times the two sums that df needs to
+//            span[b][c][2] and adds the images in batch order into parameter gradient j of channel c; a thread per element of
+//            dzq adds its ydiv x xdiv pixels of every channel block in (block, row, column) order -- or writes 0 where a
+//            sub-sampled axis never reads that element.
+//   apply    the forward's apply grid: a workgroup adds span[b][c'][2] over the channels c' of its group in channel order (S1, S2),
+//            recomputes gn per element and writes df.
+// The channel block and the tile depend on (C, H, W, unit) and never on B, so an image's df and dzq do not depend on its batch.
+// The workspace is sized for the smallest unit, by the shape alone; every partial that is read was written by the same call.
+#pragma once
+#include "cgic_norm_plan.h"
+
+namespace cgic {
+
+constexpr int kNormBwdSums = 12;                    // sum gn, gn*xhat, gy, gv, four gy*z_k, four gv*z_k
+constexpr int kNormBwdThreads = 256;                // a reduce workgroup at most (64 or 128 where a plane has fewer units); finish
+constexpr int kNormBwdChanBlock = 32;               // channels a reduce workgroup walks, at most
+constexpr int kNormBwdMinChanBlock = 8;             // ... and at least, where the shape is small:
+constexpr int64_t kNormBwdBlocksPerImage = 64;      // the block halves while an image has fewer (block, 1024-pixel tile) pairs
+
+struct NormBwdCall {
+    int in_dtype, go_dtype, df_dtype;               // CGIC_DT_*
+    int64_t B, C, H, W, hq, wq, groups;
+    uintptr_t f, go, zq, stats, gn_weight, gn_bias, wy, by, wb, bb;         // the inputs
+    uintptr_t df, dzq, dgn_weight, dgn_bias, dwy, dby, dwb, dbb;            // the outputs: 0 = not wanted
+    uintptr_t workspace;
+    size_t workspace_bytes;
+};
+
+struct NormBwdPlan {
+    int unit;                       // consecutive pixels of a row per thread and access: 8 (halves only), 4, 2 or 1
+    int64_t span, spans;            // elements of a group; B * groups
+    int ymul, ydiv, xmul, xdiv;     // the nearest index, as in NormPlan
+    unsigned int mg_w, mg_y, mg_x;
+    bool zq_vec;
+    int chan_block;                 // channels per reduce workgroup
+    int64_t chan_blocks;            // ceil(C / chan_block)
+    int threads_reduce;             // 64, 128 or 256
+    int64_t tiles, tiles_max;       // pixel tiles of a plane at this unit; at unit 1 (the workspace's size)
+    int64_t grid_reduce;            // B * chan_blocks * tiles
+    int64_t grid_sums, grid_dzq;    // finish: workgroups of the (c, j) threads, then of the dzq threads (0: dzq not wanted)
+    int64_t grid_apply, parts;      // apply: as the forward's; 0: df not wanted
+    bool need_dz;                   // dzq is wanted: reduce writes dz, finish folds it
+    bool need_conv;                 // a gradient of conv_y / conv_b is wanted: without, reduce adds and writes only sum gn and sum gn * xhat
+    bool need_df;                   // df is wanted: finish writes span[b][c][2], apply runs
+    bool in_place;                  // df is go
+    size_t off_sums, off_span, off_dz;      // byte offsets into the workspace
+    size_t workspace_needed;
+    char why_text[224];
+};
+
+// the part that the shape alone decides: the checks of (dtype, B, C, H, W, groups), the channel block and the workspace
+// (cgic_spatial_norm_backward_workspace_bytes is this function)
+inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t groups, NormBwdPlan *p, const char **why)
+{
+    *p = NormBwdPlan{};
+    const auto refuse = [&](int code) { *why = p->why_text; return code; };
+    NormPlan fwd;
+    const char *fwd_why = "";
+    const int rc = norm_form(in_dtype, B, C, H, W, groups, &fwd, &fwd_why);
+    if (rc != CGIC_OK) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s", fwd_why);
+        return refuse(rc);
+    }
+    if (B == 0) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: an empty batch");
+        return refuse(CGIC_ERR_INVALID);
+    }
+    p->span = fwd.span;
+    p->spans = fwd.spans;
+    const int64_t plane = H * W;
+    int cb = kNormBwdChanBlock;
+    while (cb > kNormBwdMinChanBlock && ((C + cb - 1) / cb) * ((plane + 1023) / 1024) < kNormBwdBlocksPerImage) cb /= 2;
+    p->chan_block = cb;
+    p->chan_blocks = (C + cb - 1) / cb;
+    p->tiles_max = (plane + kNormBwdThreads - 1) / kNormBwdThreads;
+    if (B * p->chan_blocks * p->tiles_max >= ((int64_t)1 << 31) || B * C * kNormBwdSums >= ((int64_t)1 << 31)) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: [%lld,%lld,%lld,%lld] is beyond a grid of 2^31 workgroups",
+                 (long long)B, (long long)C, (long long)H, (long long)W);
+        return refuse(CGIC_ERR_UNSUPPORTED);
+    }
+    p->off_sums = 0;
+    p->off_span = p->off_sums + (size_t)(B * C * p->tiles_max) * kNormBwdSums * sizeof(double);
+    p->off_dz = p->off_span + (size_t)(B * C) * 2 * sizeof(double);
+    p->workspace_needed = p->off_dz + (size_t)(B * p->chan_blocks) * kNormZq * (size_t)plane * sizeof(float);
+    return CGIC_OK;
+}
+
+struct NormRegion {
+    uintptr_t addr;
+    int64_t bytes;
+    int align;
+};
+inline bool norm_regions_overlap(const NormRegion &a, const NormRegion &b)
+{
+    return a.addr && b.addr && a.addr < b.addr + (uintptr_t)b.bytes && b.addr < a.addr + (uintptr_t)a.bytes;
+}
+
+// CGIC_OK and the plan, or the error code of the call and *why
+inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
+{
+    const int rc = norm_bwd_shape(c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why);
+    if (rc != CGIC_OK) return rc;
+    const auto refuse = [&](int code) { *why = p->why_text; return code; };
+    // ---- the types: go and df are fp32 or the features' own type
+    const int both[2] = {c.go_dtype, c.df_dtype};
+    for (int i = 0; i < 2; ++i)
+        if (both[i] != CGIC_DT_F32 && both[i] != c.in_dtype) {
+            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: %s %d with in_dtype %d (CGIC_DT_F32 or the features' own type)",
+                     i ? "df_dtype" : "go_dtype", both[i], c.in_dtype);
+            return refuse(both[i] == CGIC_DT_F16 || both[i] == CGIC_DT_BF16 ? CGIC_ERR_UNSUPPORTED : CGIC_ERR_INVALID);
+        }
+    // ---- zq's grid
+    if (c.hq <= 0 || c.wq <= 0) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: zq grid %lldx%lld", (long long)c.hq, (long long)c.wq);
+        return refuse(CGIC_ERR_INVALID);
+    }
+    if (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || c.B * kNormZq * c.hq * c.wq >= ((int64_t)1 << 38) ||
+        !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv)) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)",
+                 (long long)c.hq, (long long)c.wq, (long long)c.H, (long long)c.W);
+        return refuse(CGIC_ERR_UNSUPPORTED);
+    }
+    // ---- the pointers: every input, the outputs that are wanted
+    const int ib = norm_dtype_bytes(c.in_dtype), gb = norm_dtype_bytes(c.go_dtype), db = norm_dtype_bytes(c.df_dtype);
+    const int64_t numel = c.B * c.C * c.H * c.W, nzq = c.B * kNormZq * c.hq * c.wq;
+    const int kIn = 10, kOut = 8;
+    const NormRegion r[kIn + kOut] = {
+        {c.f, numel * ib, ib}, {c.go, numel * gb, gb}, {c.zq, nzq * 4, 4}, {c.stats, p->spans * 8, 4}, {c.gn_weight, c.C * 4, 4},
+        {c.gn_bias, c.C * 4, 4}, {c.wy, c.C * kNormZq * 4, 4}, {c.by, c.C * 4, 4}, {c.wb, c.C * kNormZq * 4, 4}, {c.bb, c.C * 4, 4},
+        {c.df, numel * db, db}, {c.dzq, nzq * 4, 4}, {c.dgn_weight, c.C * 4, 4}, {c.dgn_bias, c.C * 4, 4}, {c.dwy, c.C * kNormZq * 4, 4},
+        {c.dby, c.C * 4, 4}, {c.dwb, c.C * kNormZq * 4, 4}, {c.dbb, c.C * 4, 4}};
+    for (int i = 0; i < kIn; ++i)
+        if (!r[i].addr) {
+            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: NULL input");
+            return refuse(CGIC_ERR_INVALID);
+        }
+    bool any = false;
+    for (int i = kIn; i < kIn + kOut; ++i) any = any || r[i].addr;
+    if (!any) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: no gradient is wanted (every output is NULL)");
+        return refuse(CGIC_ERR_INVALID);
+    }
+    for (int i = 0; i < kIn + kOut; ++i)
+        if (r[i].addr % (uintptr_t)r[i].align) {
+            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: a pointer is not aligned to its %d-byte element", r[i].align);
+            return refuse(CGIC_ERR_INVALID);
+        }
+    // ---- aliasing: an output overlaps nothing, except that df may be go itself when their types are equal (apply reads a unit of
+    // go before it writes that unit of df, and reduce and finish, which also read go, have finished by then)
+    p->in_place = c.df && c.df == c.go && c.df_dtype == c.go_dtype;
+    for (int o = kIn; o < kIn + kOut; ++o)
+        for (int i = 0; i < o; ++i) {
+            if (o == kIn && i == 1 && p->in_place) continue;
+            if (norm_regions_overlap(r[o], r[i])) {
+                snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: an output overlaps another tensor of the call (only df == go with equal types may)");
+                return refuse(CGIC_ERR_INVALID);
+            }
+        }
+    // ---- the workspace
+    if (!c.workspace || c.workspace_bytes < p->workspace_needed) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: workspace of %zu bytes, need %zu (cgic_spatial_norm_backward_workspace_bytes)",
+                 c.workspace ? c.workspace_bytes : (size_t)0, p->workspace_needed);
+        return refuse(CGIC_ERR_CAPACITY);
+    }
+    if (c.workspace % 16) {                         // (the dz partials are written 16 bytes at a time)
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: the workspace is not aligned to 16 bytes");
+        return refuse(CGIC_ERR_INVALID);
+    }
+    const NormRegion ws = {c.workspace, (int64_t)p->workspace_needed, 16};
+    for (int i = 0; i < kIn + kOut; ++i)
+        if (norm_regions_overlap(ws, r[i])) {
+            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: the workspace overlaps a tensor of the call");
+            return refuse(CGIC_ERR_INVALID);
+        }
+    // ---- the unit: 16 bytes of the feature type where the row width and the pointers of f, go and df allow, else fewer
+    int unit = 1;
+    for (int u = 16 / ib; u > 1; u >>= 1) {
+        const int gbytes = u * gb > 16 ? 16 : u * gb, dbytes = u * db > 16 ? 16 : u * db;
+        if (c.W % u == 0 && c.f % (uintptr_t)(u * ib) == 0 && c.go % (uintptr_t)gbytes == 0 && (!c.df || c.df % (uintptr_t)dbytes == 0)) {
+            unit = u;
+            break;
+        }
+    }
+    p->unit = unit;
+    p->mg_w = norm_magic(c.H * c.W, c.W);
+    p->mg_y = norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
+    p->mg_x = norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
+    p->zq_vec = p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
+    // ---- the grids
+    const int64_t plane_units = c.H * c.W / unit;
+    p->threads_reduce = plane_units <= 64 ? 64 : plane_units <= 128 ? 128 : kNormBwdThreads;
+    p->tiles = (plane_units + p->threads_reduce - 1) / p->threads_reduce;       // (<= tiles_max: at most ceil(H * W / 256), or 1)
+    p->grid_reduce = c.B * p->chan_blocks * p->tiles;
+    p->need_dz = c.dzq != 0;
+    p->need_conv = c.dwy || c.dby || c.dwb || c.dbb;
+    p->need_df = c.df != 0;
+    p->grid_sums = (c.C * kNormBwdSums + kNormBwdThreads - 1) / kNormBwdThreads;
+    p->grid_dzq = p->need_dz ? (nzq + kNormBwdThreads - 1) / kNormBwdThreads : 0;
+    if (c.df) {
+        p->parts = (plane_units + kNormPartUnits - 1) / kNormPartUnits;
+        const int64_t items = c.B * c.C * p->parts;
+        p->grid_apply = items > kNormApplyGridCap ? kNormApplyGridCap : items;
+    }
+    return CGIC_OK;
+}
+
+// the training forward: the forward's plan, and the statistics it also writes -- fp32 [B * groups][2] = (mean, rstd) -- must be a
+// tensor of its own
+inline int norm_train_plan(const NormCall &c, uintptr_t stats, NormPlan *p, const char **why)
+{
+    const int rc = norm_plan(c, p, why);
+    if (rc != CGIC_OK || p->form == 0) return rc;
+    const auto refuse = [&](int code) { *why = p->why_text; return code; };
+    if (!stats || stats % 4) {
+        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_train: stats is %s", stats ? "not aligned to its 4-byte element" : "NULL");
+        return refuse(CGIC_ERR_INVALID);
+    }
+    const int ib = norm_dtype_bytes(c.in_dtype), ob = norm_dtype_bytes(c.out_dtype);
+    const int64_t numel = c.B * c.C * c.H * c.W;
+    const NormRegion st = {stats, p->spans * 8, 4};
+    const NormRegion r[10] = {{c.f, numel * ib, ib}, {c.zq, c.B * kNormZq * c.hq * c.wq * 4, 4}, {c.gn_weight, c.C * 4, 4}, {c.gn_bias, c.C * 4, 4},
+                              {c.wy, c.C * kNormZq * 4, 4}, {c.by, c.C * 4, 4}, {c.wb, c.C * kNormZq * 4, 4}, {c.bb, c.C * 4, 4},
+                              {c.out, numel * ob, ob}, {p->workspace_needed ? c.workspace : 0, (int64_t)p->workspace_needed, 8}};
+    for (int i = 0; i < 10; ++i)
+        if (norm_regions_overlap(st, r[i])) {
+            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_train: stats overlaps another tensor of the call");
+            return refuse(CGIC_ERR_INVALID);
+        }
+    return CGIC_OK;
+}
+
+}  // namespace cgic

@@ -164,7 +164,7 @@ class AvgPool(torch.nn.Module):
         return torch.nn.functional.avg_pool2d(x, self.k, self.k, 0)
 
 
-def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False, patch_attention=False):
+def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False, patch_attention=False, norm_backward=False):
     """swap VectorQuantize2 / Entropy / router target / compress of a reference CGIC instance in place.
     patch_pools: the decoder's two average pools in front of its masked blends (decoder.avgpool_layer1 / _layer2,
     decoder.py:304-305,366-367) become control_gic_amd.model.AvgPool -- they are modules, so they can be swapped.  The three
@@ -178,7 +178,10 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
     reaches `model.quantize` as an ordinary tensor is quantised as it is.
     patch_norms: every module with the shape of the reference's SpatialNorm (decoder.py:34-53: norm_layer, 1x1 conv_y / conv_b,
     add_conv) becomes control_gic_amd.norm.SpatialNorm on the same parameters (csrc/cgic_norm.hip under no_grad; torch's expression
-    when a gradient is needed).  Off by default, unlike patch_pools: the pools are bit-identical to torch, a normalisation agrees
+    when a gradient is needed -- or, with norm_backward=True, the library's training forward and backward kernels there too:
+    SpatialNorm.backward_kernel, one kernel family forward and backward that keeps only f and two floats per group.  Forward +
+    backward of the norm alone, measured over the decoder's shapes at B = 8 and 1, fp32 and autocast-fp16, one layer and a stack of
+    eight: 1.1x to 4.5x faster than torch's path and 2.5x to 8.4x less peak memory, no shape slower; profiles/spatial_norm_backward.md).  Off by default, unlike patch_pools: the pools are bit-identical to torch, a normalisation agrees
     with torch's only within rounding, and the default install() keeps producing exactly what it produced before.
     patch_attention: every module with the shape of the reference's AttnBlock (decoder.py:161-213, vqvae_blocks.py:140-192:
     in_channels, norm, 1x1 q / k / v / proj_out) becomes control_gic_amd.attention.AttnBlock on the same parameters: under no_grad
@@ -213,7 +216,7 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
     if patch_attention:
         _patch_attention(model)
     if patch_norms:
-        _norm.patch_norms(model)
+        _norm.patch_norms(model, backward_kernel=norm_backward)
     model.compress = types.MethodType(compress, model)
     model.compress_batch = types.MethodType(compress_batch, model)
     model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)

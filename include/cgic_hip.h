@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 18
+#define CGIC_ABI_VERSION 19
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -695,6 +695,40 @@ int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, 
                       size_t workspace_bytes, cgic_stream_t stream);
 size_t cgic_spatial_norm_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
 int cgic_spatial_norm_one_launch(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
+
+/* ---------------------------------------------------------------------------
+ * SpatialNorm for training (ABI 19): the forward that keeps the groups' statistics, and the backward.
+ *
+ * cgic_spatial_norm_train is cgic_spatial_norm (same arguments, same checks, same kernels, the same bits in `out`) that also writes
+ *   stats      device fp32 [B * groups][2] = (mean, rstd) of each group, as the forward rounded them; a tensor of its own.
+ *
+ * cgic_spatial_norm_backward, with go the gradient of the forward's result:
+ *   f, zq, the six parameters, groups, swish: what the forward was given; stats: what it wrote.
+ *   go         device [B, C, H, W] of go_dtype: CGIC_DT_F32, or in_dtype
+ *   df         device [B, C, H, W] of df_dtype: CGIC_DT_F32, or in_dtype (the fp32 value rounded once).  May be go itself when the
+ *              types are equal; an output overlaps nothing else.
+ *   dzq        device fp32 [B, 4, hq, wq]; an element that a sub-sampled axis never reads gets exactly 0
+ *   dgn_weight, dgn_bias, dby, dbb   device fp32 [C];   dwy, dwb   device fp32 [C, 4]
+ *   Every output may be NULL: it is not computed (without dzq no dz partials; without dwy, dby, dwb and dbb two plane sums per
+ *   channel instead of twelve; without df no apply launch).  At least one is wanted.
+ *   workspace  device, cgic_spatial_norm_backward_workspace_bytes(...) bytes (a function of the shape alone), 16-byte aligned.  It
+ *              need not be zeroed: the call writes every partial it reads.
+ * Values: per element in fp32 with the forward's mean and rstd, the pre-activation v recomputed, not stored; every sum in float64.
+ * Three launches ordered by the stream (cgic_norm_bwd_plan.h), no atomics, no host synchronisation, no allocation: two calls give
+ * the same bits, df and dzq of an image do not depend on its batch, and the chain can be captured in a graph.  A NaN in f makes the
+ * gradients NaN where the reference's are; +-Inf in f or go is not specified (torch's own GroupNorm backward uses another algebra
+ * there).  Every check precedes the first launch; not available inside a launch group.
+ * ------------------------------------------------------------------------- */
+int cgic_spatial_norm_train(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
+                            int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy, const float *by,
+                            const float *wb, const float *bb, int swish, void *out, int out_dtype, float *stats, void *workspace,
+                            size_t workspace_bytes, cgic_stream_t stream);
+int cgic_spatial_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W,
+                               const float *zq, int64_t hq, int64_t wq, int groups, const float *stats, const float *gn_weight,
+                               const float *gn_bias, const float *wy, const float *by, const float *wb, const float *bb, int swish,
+                               void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
+                               float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream);
+size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
 
 /* ---------------------------------------------------------------------------
  * AttnBlock's attention (ABI 18) -- CGIC/modules/vqvae/decoder.py:189-213, vqvae_blocks.py:168-193:
