@@ -179,6 +179,10 @@ PROTOTYPES = {
     "cgic_attention": (_int, [_vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _i64, _i64, _f64, _vp, _int, _vp, _vp, _sz, _vp]),
     "cgic_attention_workspace_bytes": (_sz, [_int, _i64, _int, _i64]),
     "cgic_attention_supported": (_int, [_int, _int, _i64, _int, _i64]),
+    "cgic_attention_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _i64, _i64, _i64, _f64, _vp, _vp, _vp, _int, _vp,
+                                       _sz, _vp]),
+    "cgic_attention_backward_workspace_bytes": (_sz, [_int, _i64, _int, _i64]),
+    "cgic_attention_backward_supported": (_int, [_int, _int, _i64, _int, _i64]),
     "cgic_embedding_gather_f32": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp]),
     "cgic_rate_table_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int]),
     "cgic_rate_table": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, C.POINTER(_f64), C.POINTER(_f64), _int, _px, _vp, _vp,

@@ -164,7 +164,8 @@ class AvgPool(torch.nn.Module):
         return torch.nn.functional.avg_pool2d(x, self.k, self.k, 0)
 
 
-def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False, patch_attention=False, norm_backward=False):
+def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False, patch_attention=False, norm_backward=False,
+            attention_backward=False):
     """swap VectorQuantize2 / Entropy / router target / compress of a reference CGIC instance in place.
     patch_pools: the decoder's two average pools in front of its masked blends (decoder.avgpool_layer1 / _layer2,
     decoder.py:304-305,366-367) become control_gic_amd.model.AvgPool -- they are modules, so they can be swapped.  The three
@@ -187,7 +188,15 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
     in_channels, norm, 1x1 q / k / v / proj_out) becomes control_gic_amd.attention.AttnBlock on the same parameters: under no_grad
     its softmax(q^T k) v runs in csrc/cgic_attn.hip and no [B,N,N] matrix is written; torch's expression when a gradient is needed
     or the width is not built.  Off by default for the reason patch_norms is.  With patch_norms as well, the block's norm is the
-    fused SpatialNorm."""
+    fused SpatialNorm.
+    attention_backward (with patch_attention): AttnBlock.backward_kernel -- an attention that needs a gradient runs the same forward
+    kernel and, in the backward pass, csrc/cgic_attn_bwd.hip, so that training keeps q, k, v, out and one float per token in place of
+    torch's [B,N,N] softmax and its half copy.  Forward + backward of the attention alone, measured: at [2,512,4096] in bf16 a peak
+    of 32 MiB against 720 MiB for 3.5x the time (3.31 ms against 0.94 ms), at the 36 864 tokens of a 768x768 tile 144 MiB against
+    28 GiB for 2.7x the time; fp32 3x to 90x less memory for 8x the time; no shape is faster (profiles/attention_backward.md).  Off by
+    default, also where patch_attention is on: the gradients agree with torch's only within rounding, and the switch buys memory,
+    not time -- set it where the attention blocks' activations limit the batch or the tile.  Without patch_attention there is no
+    block to set it on and the call raises (norm_backward without patch_norms is ignored, as it always was: that behaviour is kept)."""
     old = model.quantize
     dev = old.embedding.weight.device
     q = VectorQuantize2(old.n_e, old.e_dim, beta=old.beta, legacy=getattr(old, "legacy", True))
@@ -214,7 +223,9 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
             if isinstance(m, torch.nn.AvgPool2d) and m.kernel_size in (k, (k, k)) and m.stride in (k, (k, k)) and m.padding in (0, (0, 0)):
                 setattr(dec, name, AvgPool(k))
     if patch_attention:
-        _patch_attention(model)
+        _patch_attention(model, backward_kernel=attention_backward)
+    elif attention_backward:
+        raise ValueError("install: attention_backward=True sets AttnBlock.backward_kernel on the blocks that patch_attention=True swaps in; without it there are none")
     if patch_norms:
         _norm.patch_norms(model, backward_kernel=norm_backward)
     model.compress = types.MethodType(compress, model)

@@ -17,6 +17,7 @@ functions the module classes use (each entry point of libcgic_hip.so is bound on
     blob, total = torch.ops.cgic.container_pack(data, nbytes, mode, 256, 256, 0)                  # the batch as a container file, on the device
     new_f  = torch.ops.cgic.spatial_norm(f, zq, gn_w, gn_b, wy, by, wb, bb, 32, 1e-6, False, False) # the decoder's SpatialNorm (decoder.py:34-53); defined in norm.py, next to its module
     h_     = torch.ops.cgic.attention(q, k, v, int(C) ** -0.5, False)                            # AttnBlock's softmax(q^T k) v without the [B,N,N] matrix; defined in attention.py, next to its module
+    h_, lse = torch.ops.cgic.attention_train(q, k, v, int(C) ** -0.5)                             # the same, differentiable: its backward is csrc/cgic_attn_bwd.hip, no [B,N,N] matrix there either
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 19
+#define CGIC_ABI_VERSION 20
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -743,7 +743,7 @@ size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C
  *              uniform weights: out is the mean of v, lse is ln N
  *   out        device [B, C, N] dense of out_dtype: in_dtype, or CGIC_DT_F32.  A half out is the fp32 result rounded once to
  *              nearest-even.
- *   lse        device fp32 [B, N], or NULL: ln sum_j exp(scale * s_ij) (for a backward pass to come), as max * scale + ln(row sum) in
+ *   lse        device fp32 [B, N], or NULL: ln sum_j exp(scale * s_ij) (cgic_attention_backward reads it), as max * scale + ln(row sum) in
  *              float64 from the fp32 maximum and row sum, rounded once
  *   workspace  cgic_attention_workspace_bytes(...) bytes; that is 0 for every shape (keys are never split over workgroups), NULL is fine
  * Values: the scores, the running maximum, the row sum and the accumulator are fp32.  fp32 inputs are multiplied as fp32
@@ -772,6 +772,45 @@ int cgic_attention(const void *q, const void *k, const void *v, int in_dtype, in
                    size_t workspace_bytes, cgic_stream_t stream);
 size_t cgic_attention_workspace_bytes(int in_dtype, int64_t B, int C, int64_t N);
 int cgic_attention_supported(int in_dtype, int out_dtype, int64_t B, int C, int64_t N);
+
+/* ---------------------------------------------------------------------------
+ * The attention's backward pass (ABI 20), again with no tokens x tokens tensor in memory (csrc/cgic_attn_bwd.hip; every check and the
+ * geometry of the launches: csrc/cgic_attn_bwd_plan.h).  With s_ij = scale * sum_c q[c,i] k[c,j] and go the gradient of the forward's out:
+ *     P_ij = exp(s_ij - lse_i)    delta_i = sum_c go[c,i] out[c,i]    dP_ij = sum_c go[c,i] v[c,j]    dS_ij = P_ij (dP_ij - delta_i)
+ *     dv[c,j] = sum_i go[c,i] P_ij      dq[c,i] = scale sum_j dS_ij k[c,j]      dk[c,j] = scale sum_i dS_ij q[c,i]
+ *   q, k, v, C, N, scale, the three batch strides: what cgic_attention was given (views of one [B, 3C, N] tensor are read where they lie)
+ *   go         device, [C, N] per image of in_dtype, image b go_batch_stride ELEMENTS behind the pointer (>= C * N; the four batch
+ *              strides are at most 2^59 / B elements: CGIC_ERR_INVALID beyond, so that no extent of the aliasing check can wrap)
+ *   out        device [B, C, N] dense of in_dtype: what the forward returned with out_dtype = in_dtype
+ *   lse        device fp32 [B, N]: what the forward wrote
+ *   dq, dk, dv device [B, C, N] dense of grad_dtype: CGIC_DT_F32, or in_dtype (the fp32 value rounded once to nearest-even).  Each may be
+ *              NULL: it is neither computed nor written (without dq no query-owning launch; without dk and dv no key-owning launch,
+ *              with one of them half of its products; without dq and dk no delta).  All three NULL: nothing is done, CGIC_OK.
+ *   workspace  device, cgic_attention_backward_workspace_bytes(...) bytes -- delta: 4 bytes per token and image, rounded up to 16; a
+ *              function of the shape alone --, 16-byte aligned.  It need not be zeroed: the call writes every element it reads.
+ * Up to three launches ordered by the stream: delta; a launch whose workgroups own 32 queries and walk the keys (dq); one whose
+ * workgroups own 32 keys and walk the queries (dk, dv).  P and dS are recomputed per tile on the chip and all sums are kept in
+ * registers.  No atomics, no workgroup waits for another, every sum in a fixed order, no host synchronisation, no allocation: two
+ * calls give the same bits, an image's gradients do not depend on its batch, and the chain can be captured in a graph.
+ * Values: scores and dP in fp32 from the exactly upcast inputs (fp32 inputs on v_mfma_f32_32x32x2_f32, never through a half type;
+ * fp16 / bf16 on v_mfma_f32_32x32x16_{f16,bf16}); P = exp2((s * scale - lse) * log2 e) in fp32, exactly 0 below 2^-64; tail keys and
+ * queries 0 by a select; P and dS rounded once to the operand type in front of the second products; delta fp32; scale applied once,
+ * in fp32, to the finished sums.  With scale 0, dq and dk are exact zeros.
+ * NaN: one in go[c0, i0] reaches dq[:, i0], all of dk and dv[c0, :] of its image; one in q[c0, i0] dq[:, i0] and all of dk and dv; one in
+ * k all three; one in v all of dq and dk and nothing of dv -- as float64 autograd of the reference's expression, and never another
+ * image.  +-Inf in an input, and rows whose lse is not finite, are not specified.
+ * An output must overlap no input, no other output and not the workspace (CGIC_ERR_INVALID); a pointer must be aligned to its own
+ * element; rows that begin 16-byte aligned (N % 8 == 0, aligned pointer and stride) get 16-byte loads.  Every check precedes the
+ * first launch, so a refused call enqueues nothing; not available inside a launch group.
+ * cgic_attention_backward_supported: 1 if the call is built for these types and this shape, 0 if not, CGIC_ERR_INVALID for arguments
+ * that are wrong in themselves.
+ * ------------------------------------------------------------------------- */
+int cgic_attention_backward(const void *go, const void *q, const void *k, const void *v, const void *out, const float *lse, int in_dtype,
+                            int64_t B, int C, int64_t N, int64_t go_batch_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                            int64_t v_batch_stride, double scale, void *dq, void *dk, void *dv, int grad_dtype, void *workspace,
+                            size_t workspace_bytes, cgic_stream_t stream);
+size_t cgic_attention_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t N);
+int cgic_attention_backward_supported(int in_dtype, int grad_dtype, int64_t B, int C, int64_t N);
 
 /* embedding gather on its own (model.py:121,391-392): out[b, c, p] = codebook[ind[b, p], c] */
 int cgic_embedding_gather_f32(const int64_t *ind, int64_t B, int64_t hw, const float *codebook, int K,
