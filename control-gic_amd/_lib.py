@@ -176,6 +176,10 @@ PROTOTYPES = {
     "cgic_spatial_norm_backward": (_int, [_vp, _int, _vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cgic_spatial_norm_backward_workspace_bytes": (_sz, [_int, _i64, _int, _i64, _i64, _int]),
+    "cgic_group_norm": (_int, [_vp, _int, _i64, _int, _i64, _i64, _int, _f64, _vp, _vp, _int, _vp, _int, _vp, _sz, _vp]),
+    "cgic_group_norm_train": (_int, [_vp, _int, _i64, _int, _i64, _i64, _int, _f64, _vp, _vp, _int, _vp, _int, _vp, _vp, _sz, _vp]),
+    "cgic_group_norm_backward": (_int, [_vp, _int, _vp, _int, _i64, _int, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    "cgic_group_norm_backward_workspace_bytes": (_sz, [_int, _i64, _int, _i64, _i64, _int]),
     "cgic_attention": (_int, [_vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _i64, _i64, _f64, _vp, _int, _vp, _vp, _sz, _vp]),
     "cgic_attention_workspace_bytes": (_sz, [_int, _i64, _int, _i64]),
     "cgic_attention_supported": (_int, [_int, _int, _i64, _int, _i64]),

@@ -24,6 +24,12 @@
 // its pixels of each zq channel as 16-byte vectors, all issued before the first is used; otherwise the four zq values of a pixel
 // are loaded once and serve every x of the thread that falls on that pixel.  The index divisions (by the row width and the two ratios) are multiplications by the plan's magic numbers.
 // Every element is read before it is written in both forms, so out may be f.
+//
+// The encoder's plain GroupNorm (vqvae_blocks.py:34, and the swish of ResnetBlock / the norm_out heads behind it) is the same kernel
+// family instantiated with MOD = false (cgic_group_norm, _train, _backward): the same statistics, per element
+//     v = ((x - mean) * rstd) * gamma[c] + beta[c];    with swish  v / (1 + exp(-v))
+// No zq pointer reaches those instantiations and no y / b value is loaded or multiplied; norm_stats_kernel never saw zq and is
+// shared.  On finite inputs the result is bit for bit the modulated one at wy = wb = 0, by = 1, bb = 0 (n * 1 + 0 is exact).
 #include "cgic_common.h"
 #include "cgic_norm_bwd_plan.h"
 #include "cgic_norm_plan.h"
@@ -226,8 +232,40 @@ __device__ __forceinline__ void apply_units(const typename T::raw *src, void *ou
     }
 }
 
-// ---- one launch: one workgroup per span
+// the same units of the plain GroupNorm: no zq, v = n
 template <class T, bool HOUT, int U>
+__device__ __forceinline__ void apply_units_plain(const typename T::raw *src, void *out, int64_t out_plane, unsigned first, unsigned end,
+                                                  unsigned step, int swish, float gamma, float beta, float mean, float rstd)
+{
+    for (unsigned i = first; i < end; i += step) {
+        const unsigned e = i * U;
+        typename T::raw v[U];
+        load_n<typename T::raw, U>(src + e, v);
+        float o[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            float val = ((T::up(v[j]) - mean) * rstd) * gamma + beta;
+            if (swish) val = val / (1.0f + expf(-val));
+            o[j] = val;
+        }
+        store_out<T, HOUT, U>(out, out_plane + e, o);
+    }
+}
+// channel c of image b: MOD the modulated layer (the twelve parameters, zq), else the plain one (gamma and beta alone)
+template <class T, bool HOUT, int U, bool MOD>
+__device__ __forceinline__ void apply_channel(const typename T::raw *src, void *out, int64_t out_plane, unsigned first, unsigned end, unsigned step,
+                                              const Geom &g, int64_t b, int c, float mean, float rstd)
+{
+    if constexpr (MOD) {
+        const Chan w = load_chan(g, c);
+        apply_units<T, HOUT, U>(src, out, out_plane, first, end, step, g, g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq, w, mean, rstd);
+    } else {
+        apply_units_plain<T, HOUT, U>(src, out, out_plane, first, end, step, g.swish, g.gamma[c], g.beta[c], mean, rstd);
+    }
+}
+
+// ---- one launch: one workgroup per span
+template <class T, bool HOUT, int U, bool MOD>
 __global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typename T::raw *f, Geom g, unsigned span_bytes16, void *out, float *stats)
 {
     using E = typename T::raw;
@@ -260,15 +298,13 @@ __global__ __launch_bounds__(kNormOneThreads) void norm_one_kernel(const typenam
     // apply from LDS: a wave takes one channel, or 256 units of one, at a time
     const int64_t b = spn / g.groups;
     const int grp = (int)(spn - b * g.groups);
-    const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
     const unsigned plane_units = plane / U, seg_units = 4 * kWave;
     const unsigned segs = (plane_units + seg_units - 1) / seg_units, items = (unsigned)g.cpg * segs;
     for (unsigned it = (unsigned)wave; it < items; it += (unsigned)nw) {
         const unsigned cl = it / segs, sg = it - cl * segs;
-        const Chan w = load_chan(g, grp * g.cpg + (int)cl);
         const unsigned first = sg * seg_units, last = first + seg_units < plane_units ? first + seg_units : plane_units;
-        apply_units<T, HOUT, U>(sp + (size_t)cl * plane, out, spn * (int64_t)span + (int64_t)cl * plane, first + (unsigned)lane, last, kWave,
-                                g, zq_b, w, mean, rstd);
+        apply_channel<T, HOUT, U, MOD>(sp + (size_t)cl * plane, out, spn * (int64_t)span + (int64_t)cl * plane, first + (unsigned)lane, last, kWave,
+                                       g, b, grp * g.cpg + (int)cl, mean, rstd);
     }
 }
 
@@ -306,7 +342,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_stats_kernel(const typename
     }
 }
 
-template <class T, bool HOUT, int U>
+template <class T, bool HOUT, int U, bool MOD>
 __global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename T::raw *f, Geom g, const double *ws, int chunks, int64_t spans,
                                                                   int64_t items, unsigned parts, void *out, float *stats)
 {
@@ -325,21 +361,19 @@ __global__ __launch_bounds__(kNormThreads) void norm_apply_kernel(const typename
         float mean, rstd;
         finish_stats(ws[spans * chunks * 2 + spn], t1, t2, n, g.eps, &mean, &rstd);
         if (stats && part == 0 && c % g.cpg == 0 && threadIdx.x == 0) { stats[2 * spn] = mean; stats[2 * spn + 1] = rstd; }
-        const Chan w = load_chan(g, c);
-        const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
         const unsigned first = part * (unsigned)kNormPartUnits;
         const unsigned last = first + (unsigned)kNormPartUnits < plane_units ? first + (unsigned)kNormPartUnits : plane_units;
-        apply_units<T, HOUT, U>(f + bc * (int64_t)plane, out, bc * (int64_t)plane, first + threadIdx.x, last, blockDim.x, g, zq_b, w, mean, rstd);
+        apply_channel<T, HOUT, U, MOD>(f + bc * (int64_t)plane, out, bc * (int64_t)plane, first + threadIdx.x, last, blockDim.x, g, b, c, mean, rstd);
     }
 }
 
 // ---- the launches: the plan's form and unit and the call's type pair pick the instantiation
-template <class T, bool HOUT, int U>
+template <class T, bool HOUT, int U, bool MOD>
 static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, float *stats, hipStream_t s)
 {
     using E = const typename T::raw *;
     if (p.form == 1) {
-        const auto kernel = norm_one_kernel<T, HOUT, U>;
+        const auto kernel = norm_one_kernel<T, HOUT, U, MOD>;
         const int rc = ensure_lds_above_48k((const void *)kernel, p.lds_bytes);
         if (rc) return rc;
         const unsigned span_bytes16 = (unsigned)(p.lds_bytes - 2 * sizeof(double) * (size_t)(kNormOneThreads / kWave));
@@ -351,21 +385,31 @@ static int launch_unit(const NormCall &c, const NormPlan &p, const Geom &g, floa
                        (unsigned)p.chunk_units, p.spans, (double *)c.workspace);
     int rc = launch_check("norm_stats_kernel");
     if (rc) return rc;
-    hipLaunchKernelGGL((norm_apply_kernel<T, HOUT, U>), dim3((unsigned)p.grid_apply), dim3(p.threads), 0, s, (E)c.f, g,
+    hipLaunchKernelGGL((norm_apply_kernel<T, HOUT, U, MOD>), dim3((unsigned)p.grid_apply), dim3(p.threads), 0, s, (E)c.f, g,
                        (const double *)c.workspace, p.chunks, p.spans, c.B * c.C * p.parts, (unsigned)p.parts, (void *)c.out, stats);
     return launch_check("norm_apply_kernel");
 }
 
-template <class T, bool HOUT>
+template <class T, bool HOUT, bool MOD>
 static int launch_typed(const NormCall &c, const NormPlan &p, const Geom &g, float *stats, hipStream_t s)
 {
     if constexpr (sizeof(typename T::raw) == 2)
-        if (p.unit == 8) return launch_unit<T, HOUT, 8>(c, p, g, stats, s);
+        if (p.unit == 8) return launch_unit<T, HOUT, 8, MOD>(c, p, g, stats, s);
     switch (p.unit) {
-    case 4: return launch_unit<T, HOUT, 4>(c, p, g, stats, s);
-    case 2: return launch_unit<T, HOUT, 2>(c, p, g, stats, s);
-    default: return launch_unit<T, HOUT, 1>(c, p, g, stats, s);
+    case 4: return launch_unit<T, HOUT, 4, MOD>(c, p, g, stats, s);
+    case 2: return launch_unit<T, HOUT, 2, MOD>(c, p, g, stats, s);
+    default: return launch_unit<T, HOUT, 1, MOD>(c, p, g, stats, s);
     }
+}
+
+// the call's type pair
+template <bool MOD>
+static int launch_call(const NormCall &c, const NormPlan &p, const Geom &g, float *stats, hipStream_t s)
+{
+    const bool hout = c.out_dtype != CGIC_DT_F32;
+    if (c.in_dtype == CGIC_DT_F32) return launch_typed<F32, false, MOD>(c, p, g, stats, s);
+    if (c.in_dtype == CGIC_DT_F16) return hout ? launch_typed<F16, true, MOD>(c, p, g, stats, s) : launch_typed<F16, false, MOD>(c, p, g, stats, s);
+    return hout ? launch_typed<BF16, true, MOD>(c, p, g, stats, s) : launch_typed<BF16, false, MOD>(c, p, g, stats, s);
 }
 
 // ================================================================================================================ the backward
@@ -460,11 +504,29 @@ __device__ __forceinline__ Terms bwd_terms(const Chan &w, int swish, float x, fl
     return t;
 }
 
-// ---- reduce: workgroup (b, channel block, pixel tile); a thread keeps one unit of pixels and walks the block's channels
-template <class T, class G, int U>
+// the plain GroupNorm's: v = n, so y = 1 and gn = gv (one multiplication less, the same bits as the modulated terms at y = 1, b = 0)
+__device__ __forceinline__ Terms bwd_terms_plain(float gamma, float beta, int swish, float x, float mean, float rstd, float go)
+{
+    Terms t;
+    t.xhat = (x - mean) * rstd;
+    t.n = t.xhat * gamma + beta;
+    t.y = 1.0f;
+    t.gv = go;
+    if (swish) {
+        const float v = t.n;
+        const float sg = 1.0f / (1.0f + expf(-v));
+        t.gv = go * (sg * (1.0f + v * (1.0f - sg)));
+    }
+    return t;
+}
+
+// ---- reduce: workgroup (b, channel block, pixel tile); a thread keeps one unit of pixels and walks the block's channels.
+// MOD: the modulated layer.  Without it (the plain GroupNorm) a channel has two plane sums, nothing of zq is read and no dz written
+template <class T, class G, int U, bool MOD>
 __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_reduce_kernel(const typename T::raw *f, const typename G::raw *go, BwdGeom a)
 {
-    __shared__ double part[kNormBwdChanBlock][kNormBwdThreads / kWave][kNormBwdSums];
+    constexpr int NS = MOD ? kNormBwdSums : 2;      // sums per (channel, tile) in the workspace
+    __shared__ double part[kNormBwdChanBlock][kNormBwdThreads / kWave][NS];
     const Geom &g = a.g;
     const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_units = plane / U;
     const unsigned tile = blockIdx.x % (unsigned)a.tiles, rest = blockIdx.x / (unsigned)a.tiles;
@@ -476,49 +538,68 @@ __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_reduce_kernel(const 
     const unsigned y = fdiv(e, g.mg_w, (unsigned)g.W), x = e - y * (unsigned)g.W;
     const int wave = (int)(threadIdx.x >> 6), lane = lane_id(), nw = (int)(blockDim.x >> 6);
     float z[kNormZq][U];
-    load_z<U>(g, g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq, y, x, z);      // (a thread without a unit: the plane's first)
     double dz[kNormZq][U];
+    if constexpr (MOD) {
+        load_z<U>(g, g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq, y, x, z);      // (a thread without a unit: the plane's first)
 #pragma unroll
-    for (int k = 0; k < kNormZq; ++k)
+        for (int k = 0; k < kNormZq; ++k)
 #pragma unroll
-        for (int j = 0; j < U; ++j) dz[k][j] = 0.0;
+            for (int j = 0; j < U; ++j) dz[k][j] = 0.0;
+    }
     const int c0 = (int)cb * a.chan_block, c1 = c0 + a.chan_block < g.C ? c0 + a.chan_block : g.C;
-    const unsigned nsum = a.need_conv ? (unsigned)kNormBwdSums : 2u;       // sums per channel that are added, written and later read
+    const unsigned nsum = MOD && a.need_conv ? (unsigned)kNormBwdSums : 2u;       // sums per channel that are added, written and later read
     for (int c = c0; c < c1; ++c) {
-        const Chan w = load_chan(g, c);
         const int64_t spn = b * g.groups + c / g.cpg;
         const float mean = a.stats[2 * spn], rstd = a.stats[2 * spn + 1];
-        double s[kNormBwdSums];
+        double s[NS];
 #pragma unroll
-        for (int i = 0; i < kNormBwdSums; ++i) s[i] = 0.0;
-        if (live) {
-            const int64_t at = (b * g.C + c) * (int64_t)plane + e;
-            typename T::raw fv[U];
-            typename G::raw gov[U];
-            load_n<typename T::raw, U>(f + at, fv);
-            load_go<typename G::raw, U>(go + at, gov);
+        for (int i = 0; i < NS; ++i) s[i] = 0.0;
+        if constexpr (!MOD) {
+            const float gamma = g.gamma[c], beta = g.beta[c];
+            if (live) {
+                const int64_t at = (b * g.C + c) * (int64_t)plane + e;
+                typename T::raw fv[U];
+                typename G::raw gov[U];
+                load_n<typename T::raw, U>(f + at, fv);
+                load_go<typename G::raw, U>(go + at, gov);
 #pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
-                const float gn = t.gv * t.y, gy = t.gv * t.n;
-                s[0] += (double)gn;
-                s[1] += (double)(gn * t.xhat);
-                if (a.need_conv) {
-                    s[2] += (double)gy;
-                    s[3] += (double)t.gv;
+                for (int j = 0; j < U; ++j) {
+                    const Terms t = bwd_terms_plain(gamma, beta, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]));
+                    s[0] += (double)t.gv;
+                    s[1] += (double)(t.gv * t.xhat);
                 }
+            }
+        } else {
+            const Chan w = load_chan(g, c);
+            if (live) {
+                const int64_t at = (b * g.C + c) * (int64_t)plane + e;
+                typename T::raw fv[U];
+                typename G::raw gov[U];
+                load_n<typename T::raw, U>(f + at, fv);
+                load_go<typename G::raw, U>(go + at, gov);
 #pragma unroll
-                for (int k = 0; k < kNormZq; ++k) {
+                for (int j = 0; j < U; ++j) {
+                    const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
+                    const float gn = t.gv * t.y, gy = t.gv * t.n;
+                    s[0] += (double)gn;
+                    s[1] += (double)(gn * t.xhat);
                     if (a.need_conv) {
-                        s[4 + k] += (double)(gy * z[k][j]);
-                        s[8 + k] += (double)(t.gv * z[k][j]);
+                        s[2] += (double)gy;
+                        s[3] += (double)t.gv;
                     }
-                    if (a.need_dz) dz[k][j] += (double)(w.wy[k] * gy + w.wb[k] * t.gv);
+#pragma unroll
+                    for (int k = 0; k < kNormZq; ++k) {
+                        if (a.need_conv) {
+                            s[4 + k] += (double)(gy * z[k][j]);
+                            s[8 + k] += (double)(t.gv * z[k][j]);
+                        }
+                        if (a.need_dz) dz[k][j] += (double)(w.wy[k] * gy + w.wb[k] * t.gv);
+                    }
                 }
             }
         }
 #pragma unroll
-        for (int i = 0; i < kNormBwdSums; ++i) {
+        for (int i = 0; i < NS; ++i) {
             if ((unsigned)i >= nsum) break;                   // (no conv gradient is wanted: the first two sums only)
             const double t = wave_sum(s[i]);
             if (lane == 0) part[c - c0][wave][i] = t;
@@ -530,35 +611,39 @@ __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_reduce_kernel(const 
         const unsigned cl = i / nsum, j = i - cl * nsum;
         double t = 0.0;
         for (int wv = 0; wv < nw; ++wv) t += part[cl][wv][j];
-        a.sums[(((b * g.C + c0 + (int)cl) * a.tiles + tile) * kNormBwdSums) + j] = t;
+        a.sums[(((b * g.C + c0 + (int)cl) * a.tiles + tile) * NS) + j] = t;
     }
-    if (a.need_dz && live) {
+    if constexpr (MOD) {
+        if (a.need_dz && live) {
 #pragma unroll
-        for (int k = 0; k < kNormZq; ++k) {
-            float o[U];
+            for (int k = 0; k < kNormZq; ++k) {
+                float o[U];
 #pragma unroll
-            for (int j = 0; j < U; ++j) o[j] = (float)dz[k][j];
-            store_out<F32, false, U>(a.dz, ((b * a.chan_blocks + cb) * kNormZq + k) * (int64_t)plane + e, o);
+                for (int j = 0; j < U; ++j) o[j] = (float)dz[k][j];
+                store_out<F32, false, U>(a.dz, ((b * a.chan_blocks + cb) * kNormZq + k) * (int64_t)plane + e, o);
+            }
         }
     }
 }
 
 // ---- finish: the first `grid_sums` workgroups hold a thread per (channel, sum), the others a thread per element of dzq
+template <bool MOD>
 __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_finish_kernel(BwdGeom a, int64_t B, unsigned grid_sums, float *dgamma, float *dbeta,
                                                                           float *dwy, float *dby, float *dwb, float *dbb, float *dzq)
 {
+    constexpr unsigned NS = MOD ? kNormBwdSums : 2;
     const Geom &g = a.g;
-    if (blockIdx.x < grid_sums) {
+    if (!MOD || blockIdx.x < grid_sums) {           // (the plain GroupNorm has no dzq: every workgroup is one of these)
         const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-        if (i >= (unsigned)g.C * kNormBwdSums) return;
-        const unsigned c = i / kNormBwdSums, j = i - c * kNormBwdSums;
+        if (i >= (unsigned)g.C * NS) return;
+        const unsigned c = i / NS, j = i - c * NS;
         if (j >= 2 && !a.need_conv) return;         // (reduce did not write these)
         const double gamma = (double)g.gamma[c];
         double total = 0.0;
         for (int64_t b = 0; b < B; ++b) {
-            const double *src = a.sums + (b * g.C + c) * a.tiles * kNormBwdSums + j;
+            const double *src = a.sums + (b * g.C + c) * a.tiles * NS + j;
             double s = 0.0;
-            for (int t = 0; t < a.tiles; ++t) s += src[(int64_t)t * kNormBwdSums];
+            for (int t = 0; t < a.tiles; ++t) s += src[(int64_t)t * NS];
             if (j < 2 && a.need_df) a.span[(b * g.C + c) * 2 + j] = gamma * s;
             total += s;
         }
@@ -566,6 +651,7 @@ __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_finish_kernel(BwdGeo
         if (dst) dst[j < 4 ? c : c * kNormZq + ((j - 4) & (kNormZq - 1))] = (float)total;
         return;
     }
+    if constexpr (!MOD) return;
     const unsigned plane = (unsigned)g.H * (unsigned)g.W, plane_q = (unsigned)g.hq * (unsigned)g.wq;
     const int64_t i = (int64_t)(blockIdx.x - grid_sums) * blockDim.x + threadIdx.x;
     if (i >= B * kNormZq * (int64_t)plane_q) return;
@@ -587,7 +673,7 @@ __global__ __launch_bounds__(kNormBwdThreads) void norm_bwd_finish_kernel(BwdGeo
 }
 
 // ---- apply: the forward's grid; df of a unit is written after go's unit was read, so df may be go
-template <class T, class G, bool HOUT, int U>
+template <class T, class G, bool HOUT, int U, bool MOD>
 __global__ __launch_bounds__(kNormThreads) void norm_bwd_apply_kernel(const typename T::raw *f, const typename G::raw *go, BwdGeom a, int64_t items,
                                                                       unsigned parts, void *df)
 {
@@ -606,70 +692,99 @@ __global__ __launch_bounds__(kNormThreads) void norm_bwd_apply_kernel(const type
         for (int cl = 0; cl < g.cpg; ++cl) { s1 += sp[2 * cl]; s2 += sp[2 * cl + 1]; }
         const float m1 = (float)(s1 / n), m2 = (float)(s2 / n);
         const float mean = a.stats[2 * spn], rstd = a.stats[2 * spn + 1];
-        const Chan w = load_chan(g, c);
-        const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
         const unsigned first = part * (unsigned)kNormPartUnits;
         const unsigned last = first + (unsigned)kNormPartUnits < plane_units ? first + (unsigned)kNormPartUnits : plane_units;
-        for (unsigned i = first + threadIdx.x; i < last; i += blockDim.x) {
-            const unsigned e = i * U;
-            const unsigned y = fdiv(e, g.mg_w, (unsigned)g.W), x = e - y * (unsigned)g.W;
-            float z[kNormZq][U];
-            load_z<U>(g, zq_b, y, x, z);
-            typename T::raw fv[U];
-            typename G::raw gov[U];
-            load_n<typename T::raw, U>(f + bc * (int64_t)plane + e, fv);
-            load_go<typename G::raw, U>(go + bc * (int64_t)plane + e, gov);
-            float o[U];
+        if constexpr (!MOD) {
+            const float gamma = g.gamma[c], beta = g.beta[c];
+            for (unsigned i = first + threadIdx.x; i < last; i += blockDim.x) {
+                const unsigned e = i * U;
+                typename T::raw fv[U];
+                typename G::raw gov[U];
+                load_n<typename T::raw, U>(f + bc * (int64_t)plane + e, fv);
+                load_go<typename G::raw, U>(go + bc * (int64_t)plane + e, gov);
+                float o[U];
 #pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
-                const float gn = t.gv * t.y;
-                o[j] = rstd * ((w.gamma * gn - m1) - t.xhat * m2);
-                // a half df is the fp32 value rounded once more: the fp32 product has to exist.  Left to itself the compiler folds the
-                // multiplication into the conversion (v_fma_mixlo_f16: one rounding of the exact product), and where the fp32 value
-                // lies halfway between two halves the result is no longer .to(half) of the fp32 df
-                if constexpr (HOUT) asm volatile("" : "+v"(o[j]));
+                for (int j = 0; j < U; ++j) {
+                    const Terms t = bwd_terms_plain(gamma, beta, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]));
+                    o[j] = rstd * ((gamma * t.gv - m1) - t.xhat * m2);
+                    if constexpr (HOUT) asm volatile("" : "+v"(o[j]));          // (as below: the fp32 product has to exist)
+                }
+                store_out<T, HOUT, U>(df, bc * (int64_t)plane + e, o);
             }
-            store_out<T, HOUT, U>(df, bc * (int64_t)plane + e, o);
+        } else {
+            const Chan w = load_chan(g, c);
+            const float *zq_b = g.zq + (size_t)b * kNormZq * (unsigned)g.hq * (unsigned)g.wq;
+            for (unsigned i = first + threadIdx.x; i < last; i += blockDim.x) {
+                const unsigned e = i * U;
+                const unsigned y = fdiv(e, g.mg_w, (unsigned)g.W), x = e - y * (unsigned)g.W;
+                float z[kNormZq][U];
+                load_z<U>(g, zq_b, y, x, z);
+                typename T::raw fv[U];
+                typename G::raw gov[U];
+                load_n<typename T::raw, U>(f + bc * (int64_t)plane + e, fv);
+                load_go<typename G::raw, U>(go + bc * (int64_t)plane + e, gov);
+                float o[U];
+#pragma unroll
+                for (int j = 0; j < U; ++j) {
+                    const Terms t = bwd_terms(w, g.swish, T::up(fv[j]), mean, rstd, G::up(gov[j]), z[0][j], z[1][j], z[2][j], z[3][j]);
+                    const float gn = t.gv * t.y;
+                    o[j] = rstd * ((w.gamma * gn - m1) - t.xhat * m2);
+                    // a half df is the fp32 value rounded once more: the fp32 product has to exist.  Left to itself the compiler folds the
+                    // multiplication into the conversion (v_fma_mixlo_f16: one rounding of the exact product), and where the fp32 value
+                    // lies halfway between two halves the result is no longer .to(half) of the fp32 df
+                    if constexpr (HOUT) asm volatile("" : "+v"(o[j]));
+                }
+                store_out<T, HOUT, U>(df, bc * (int64_t)plane + e, o);
+            }
         }
     }
 }
 
-template <class T, class G, int U>
+template <class T, class G, int U, bool MOD>
 static int bwd_launch_unit(const NormBwdCall &c, const NormBwdPlan &p, const BwdGeom &a, hipStream_t s)
 {
     using E = const typename T::raw *;
     using EG = const typename G::raw *;
-    hipLaunchKernelGGL((norm_bwd_reduce_kernel<T, G, U>), dim3((unsigned)p.grid_reduce), dim3(p.threads_reduce), 0, s, (E)c.f, (EG)c.go, a);
+    hipLaunchKernelGGL((norm_bwd_reduce_kernel<T, G, U, MOD>), dim3((unsigned)p.grid_reduce), dim3(p.threads_reduce), 0, s, (E)c.f, (EG)c.go, a);
     int rc = launch_check("norm_bwd_reduce_kernel");
     if (rc) return rc;
-    hipLaunchKernelGGL(norm_bwd_finish_kernel, dim3((unsigned)(p.grid_sums + p.grid_dzq)), dim3(kNormBwdThreads), 0, s, a, c.B, (unsigned)p.grid_sums,
+    hipLaunchKernelGGL(norm_bwd_finish_kernel<MOD>, dim3((unsigned)(p.grid_sums + p.grid_dzq)), dim3(kNormBwdThreads), 0, s, a, c.B, (unsigned)p.grid_sums,
                        (float *)c.dgn_weight, (float *)c.dgn_bias, (float *)c.dwy, (float *)c.dby, (float *)c.dwb, (float *)c.dbb, (float *)c.dzq);
     rc = launch_check("norm_bwd_finish_kernel");
     if (rc || !p.grid_apply) return rc;
     const int64_t items = c.B * c.C * p.parts;
     if constexpr (sizeof(typename T::raw) == 2) {
         if (c.df_dtype != CGIC_DT_F32) {
-            hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, true, U>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
+            hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, true, U, MOD>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
                                (unsigned)p.parts, (void *)c.df);
             return launch_check("norm_bwd_apply_kernel");
         }
     }
-    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, false, U>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
+    hipLaunchKernelGGL((norm_bwd_apply_kernel<T, G, false, U, MOD>), dim3((unsigned)p.grid_apply), dim3(kNormThreads), 0, s, (E)c.f, (EG)c.go, a, items,
                        (unsigned)p.parts, (void *)c.df);
     return launch_check("norm_bwd_apply_kernel");
 }
 
-template <class T, class G>
+template <class T, class G, bool MOD>
 static int bwd_launch_typed(const NormBwdCall &c, const NormBwdPlan &p, const BwdGeom &a, hipStream_t s)
 {
     if constexpr (sizeof(typename T::raw) == 2)
-        if (p.unit == 8) return bwd_launch_unit<T, G, 8>(c, p, a, s);
+        if (p.unit == 8) return bwd_launch_unit<T, G, 8, MOD>(c, p, a, s);
     switch (p.unit) {
-    case 4: return bwd_launch_unit<T, G, 4>(c, p, a, s);
-    case 2: return bwd_launch_unit<T, G, 2>(c, p, a, s);
-    default: return bwd_launch_unit<T, G, 1>(c, p, a, s);
+    case 4: return bwd_launch_unit<T, G, 4, MOD>(c, p, a, s);
+    case 2: return bwd_launch_unit<T, G, 2, MOD>(c, p, a, s);
+    default: return bwd_launch_unit<T, G, 1, MOD>(c, p, a, s);
     }
+}
+
+// the call's types of f and go
+template <bool MOD>
+static int bwd_launch_call(const NormBwdCall &c, const NormBwdPlan &p, const BwdGeom &a, hipStream_t s)
+{
+    const bool hgo = c.go_dtype != CGIC_DT_F32;
+    if (c.in_dtype == CGIC_DT_F32) return bwd_launch_typed<F32, F32, MOD>(c, p, a, s);
+    if (c.in_dtype == CGIC_DT_F16) return hgo ? bwd_launch_typed<F16, F16, MOD>(c, p, a, s) : bwd_launch_typed<F16, F32, MOD>(c, p, a, s);
+    return hgo ? bwd_launch_typed<BF16, BF16, MOD>(c, p, a, s) : bwd_launch_typed<BF16, F32, MOD>(c, p, a, s);
 }
 
 }  // namespace norm
@@ -678,7 +793,7 @@ static int bwd_launch_typed(const NormBwdCall &c, const NormBwdPlan &p, const Bw
 using namespace cgic;
 
 // the forward and the training forward (stats != NULL also writes the groups' mean and rstd): the same plan, the same kernels
-static int norm_forward(const char *name, bool train, const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq,
+static int norm_forward(const char *name, bool plain, bool train, const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq,
                         int64_t hq, int64_t wq, int groups, double eps, const float *gn_weight, const float *gn_bias, const float *wy,
                         const float *by, const float *wb, const float *bb, int swish, void *out, int out_dtype, float *stats, void *workspace,
                         size_t workspace_bytes, cgic_stream_t stream)
@@ -687,7 +802,7 @@ static int norm_forward(const char *name, bool train, const void *f, int in_dtyp
     c.in_dtype = in_dtype; c.out_dtype = out_dtype; c.B = B; c.C = C; c.H = H; c.W = W; c.hq = hq; c.wq = wq; c.groups = groups;
     c.f = (uintptr_t)f; c.zq = (uintptr_t)zq; c.gn_weight = (uintptr_t)gn_weight; c.gn_bias = (uintptr_t)gn_bias;
     c.wy = (uintptr_t)wy; c.by = (uintptr_t)by; c.wb = (uintptr_t)wb; c.bb = (uintptr_t)bb; c.out = (uintptr_t)out;
-    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes;
+    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes; c.plain = plain;
     NormPlan p;
     const char *why = "";
     const int rc = train ? norm_train_plan(c, (uintptr_t)stats, &p, &why) : norm_plan(c, &p, &why);
@@ -700,10 +815,7 @@ static int norm_forward(const char *name, bool train, const void *f, int in_dtyp
     g.swish = swish ? 1 : 0; g.eps = eps;
     g.zq = zq; g.gamma = gn_weight; g.beta = gn_bias; g.wy = wy; g.by = by; g.wb = wb; g.bb = bb;
     const hipStream_t s = (hipStream_t)stream;
-    const bool hout = out_dtype != CGIC_DT_F32;
-    if (in_dtype == CGIC_DT_F32) return norm::launch_typed<norm::F32, false>(c, p, g, stats, s);
-    if (in_dtype == CGIC_DT_F16) return hout ? norm::launch_typed<norm::F16, true>(c, p, g, stats, s) : norm::launch_typed<norm::F16, false>(c, p, g, stats, s);
-    return hout ? norm::launch_typed<norm::BF16, true>(c, p, g, stats, s) : norm::launch_typed<norm::BF16, false>(c, p, g, stats, s);
+    return plain ? norm::launch_call<false>(c, p, g, stats, s) : norm::launch_call<true>(c, p, g, stats, s);
 }
 
 extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, const float *zq, int64_t hq, int64_t wq,
@@ -712,7 +824,7 @@ extern "C" int cgic_spatial_norm(const void *f, int in_dtype, int64_t B, int C, 
                                  size_t workspace_bytes, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_spatial_norm");
-    return norm_forward("spatial_norm", false, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish, out,
+    return norm_forward("spatial_norm", false, false, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish, out,
                         out_dtype, nullptr, workspace, workspace_bytes, stream);
 }
 
@@ -722,17 +834,35 @@ extern "C" int cgic_spatial_norm_train(const void *f, int in_dtype, int64_t B, i
                                        void *workspace, size_t workspace_bytes, cgic_stream_t stream)
 {
     CGIC_NOT_IN_GROUP("cgic_spatial_norm_train");
-    return norm_forward("spatial_norm_train", true, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish,
+    return norm_forward("spatial_norm_train", false, true, f, in_dtype, B, C, H, W, zq, hq, wq, groups, eps, gn_weight, gn_bias, wy, by, wb, bb, swish,
                         out, out_dtype, stats, workspace, workspace_bytes, stream);
 }
 
-extern "C" int cgic_spatial_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W,
-                                          const float *zq, int64_t hq, int64_t wq, int groups, const float *stats, const float *gn_weight,
-                                          const float *gn_bias, const float *wy, const float *by, const float *wb, const float *bb, int swish,
-                                          void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
-                                          float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+// the plain GroupNorm's calls: no zq, no conv_y / conv_b -- the same plans with the flag set, the kernels' other instantiation
+extern "C" int cgic_group_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups, double eps, const float *gn_weight,
+                               const float *gn_bias, int swish, void *out, int out_dtype, void *workspace, size_t workspace_bytes,
+                               cgic_stream_t stream)
 {
-    CGIC_NOT_IN_GROUP("cgic_spatial_norm_backward");
+    CGIC_NOT_IN_GROUP("cgic_group_norm");
+    return norm_forward("group_norm", true, false, f, in_dtype, B, C, H, W, nullptr, 0, 0, groups, eps, gn_weight, gn_bias, nullptr, nullptr, nullptr,
+                        nullptr, swish, out, out_dtype, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cgic_group_norm_train(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups, double eps,
+                                     const float *gn_weight, const float *gn_bias, int swish, void *out, int out_dtype, float *stats,
+                                     void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_group_norm_train");
+    return norm_forward("group_norm_train", true, true, f, in_dtype, B, C, H, W, nullptr, 0, 0, groups, eps, gn_weight, gn_bias, nullptr, nullptr,
+                        nullptr, nullptr, swish, out, out_dtype, stats, workspace, workspace_bytes, stream);
+}
+
+static int norm_backward(bool plain, const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W,
+                         const float *zq, int64_t hq, int64_t wq, int groups, const float *stats, const float *gn_weight,
+                         const float *gn_bias, const float *wy, const float *by, const float *wb, const float *bb, int swish,
+                         void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
+                         float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
     NormBwdCall c{};
     c.in_dtype = in_dtype; c.go_dtype = go_dtype; c.df_dtype = df_dtype;
     c.B = B; c.C = C; c.H = H; c.W = W; c.hq = hq; c.wq = wq; c.groups = groups;
@@ -740,7 +870,7 @@ extern "C" int cgic_spatial_norm_backward(const void *f, int in_dtype, const voi
     c.gn_bias = (uintptr_t)gn_bias; c.wy = (uintptr_t)wy; c.by = (uintptr_t)by; c.wb = (uintptr_t)wb; c.bb = (uintptr_t)bb;
     c.df = (uintptr_t)df; c.dzq = (uintptr_t)dzq; c.dgn_weight = (uintptr_t)dgn_weight; c.dgn_bias = (uintptr_t)dgn_bias;
     c.dwy = (uintptr_t)dwy; c.dby = (uintptr_t)dby; c.dwb = (uintptr_t)dwb; c.dbb = (uintptr_t)dbb;
-    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes;
+    c.workspace = (uintptr_t)workspace; c.workspace_bytes = workspace_bytes; c.plain = plain;
     NormBwdPlan p;
     const char *why = "";
     const int rc = norm_bwd_plan(c, &p, &why);
@@ -756,10 +886,27 @@ extern "C" int cgic_spatial_norm_backward(const void *f, int in_dtype, const voi
     unsigned char *ws = (unsigned char *)workspace;
     a.sums = (double *)(ws + p.off_sums); a.span = (double *)(ws + p.off_span); a.dz = (float *)(ws + p.off_dz);
     const hipStream_t s = (hipStream_t)stream;
-    const bool hgo = go_dtype != CGIC_DT_F32;
-    if (in_dtype == CGIC_DT_F32) return norm::bwd_launch_typed<norm::F32, norm::F32>(c, p, a, s);
-    if (in_dtype == CGIC_DT_F16) return hgo ? norm::bwd_launch_typed<norm::F16, norm::F16>(c, p, a, s) : norm::bwd_launch_typed<norm::F16, norm::F32>(c, p, a, s);
-    return hgo ? norm::bwd_launch_typed<norm::BF16, norm::BF16>(c, p, a, s) : norm::bwd_launch_typed<norm::BF16, norm::F32>(c, p, a, s);
+    return plain ? norm::bwd_launch_call<false>(c, p, a, s) : norm::bwd_launch_call<true>(c, p, a, s);
+}
+
+extern "C" int cgic_spatial_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W,
+                                          const float *zq, int64_t hq, int64_t wq, int groups, const float *stats, const float *gn_weight,
+                                          const float *gn_bias, const float *wy, const float *by, const float *wb, const float *bb, int swish,
+                                          void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
+                                          float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_spatial_norm_backward");
+    return norm_backward(false, f, in_dtype, go, go_dtype, B, C, H, W, zq, hq, wq, groups, stats, gn_weight, gn_bias, wy, by, wb, bb, swish, df, df_dtype,
+                         dzq, dgn_weight, dgn_bias, dwy, dby, dwb, dbb, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cgic_group_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W, int groups,
+                                        const float *stats, const float *gn_weight, const float *gn_bias, int swish, void *df, int df_dtype,
+                                        float *dgn_weight, float *dgn_bias, void *workspace, size_t workspace_bytes, cgic_stream_t stream)
+{
+    CGIC_NOT_IN_GROUP("cgic_group_norm_backward");
+    return norm_backward(true, f, in_dtype, go, go_dtype, B, C, H, W, nullptr, 0, 0, groups, stats, gn_weight, gn_bias, nullptr, nullptr, nullptr, nullptr,
+                         swish, df, df_dtype, nullptr, dgn_weight, dgn_bias, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)
@@ -767,6 +914,13 @@ extern "C" size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64
     NormBwdPlan p;
     const char *why = "";
     return norm_bwd_shape(in_dtype, B, C, H, W, groups, &p, &why) == CGIC_OK ? p.workspace_needed : 0;
+}
+
+extern "C" size_t cgic_group_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)
+{
+    NormBwdPlan p;
+    const char *why = "";
+    return norm_bwd_shape(in_dtype, B, C, H, W, groups, &p, &why, true) == CGIC_OK ? p.workspace_needed : 0;
 }
 
 extern "C" size_t cgic_spatial_norm_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups)

@@ -16,6 +16,8 @@
 //            recomputes gn per element and writes df.
 // The channel block and the tile depend on (C, H, W, unit) and never on B, so an image's df and dzq do not depend on its batch.
 // The workspace is sized for the smallest unit, by the shape alone; every partial that is read was written by the same call.
+// NormBwdCall::plain (value-initialised: false) plans cgic_group_norm_backward: two plane sums per channel (sums[b][c][tile][2]), no
+// dz, no dzq threads in finish; zq, conv_y, conv_b and their gradients are not looked at, every other check is the same.
 #pragma once
 #include "cgic_norm_plan.h"
 
@@ -34,6 +36,7 @@ struct NormBwdCall {
     uintptr_t df, dzq, dgn_weight, dgn_bias, dwy, dby, dwb, dbb;            // the outputs: 0 = not wanted
     uintptr_t workspace;
     size_t workspace_bytes;
+    bool plain;                     // cgic_group_norm_backward: no zq, no conv_y / conv_b, none of their gradients (those fields are not looked at)
 };
 
 struct NormBwdPlan {
@@ -53,17 +56,24 @@ struct NormBwdPlan {
     bool need_conv;                 // a gradient of conv_y / conv_b is wanted: without, reduce adds and writes only sum gn and sum gn * xhat
     bool need_df;                   // df is wanted: finish writes span[b][c][2], apply runs
     bool in_place;                  // df is go
+    int sums;                       // plane sums per channel and tile in the workspace: kNormBwdSums, or 2 for the plain call
     size_t off_sums, off_span, off_dz;      // byte offsets into the workspace
     size_t workspace_needed;
     char why_text[224];
 };
 
 // the part that the shape alone decides: the checks of (dtype, B, C, H, W, groups), the channel block and the workspace
-// (cgic_spatial_norm_backward_workspace_bytes is this function)
-inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t groups, NormBwdPlan *p, const char **why)
+// (cgic_spatial_norm_backward_workspace_bytes is this function; with `plain`, cgic_group_norm_backward_workspace_bytes: two sums
+// per channel and tile instead of twelve, no dz partials)
+inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t groups, NormBwdPlan *p, const char **why,
+                          bool plain = false)
 {
     *p = NormBwdPlan{};
-    const auto refuse = [&](int code) { *why = p->why_text; return code; };
+    const auto refuse = [&](int code) {
+        if (plain) norm_as_group(p->why_text);
+        *why = p->why_text;
+        return code;
+    };
     NormPlan fwd;
     const char *fwd_why = "";
     const int rc = norm_form(in_dtype, B, C, H, W, groups, &fwd, &fwd_why);
@@ -88,10 +98,11 @@ inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t
                  (long long)B, (long long)C, (long long)H, (long long)W);
         return refuse(CGIC_ERR_UNSUPPORTED);
     }
+    p->sums = plain ? 2 : kNormBwdSums;
     p->off_sums = 0;
-    p->off_span = p->off_sums + (size_t)(B * C * p->tiles_max) * kNormBwdSums * sizeof(double);
+    p->off_span = p->off_sums + (size_t)(B * C * p->tiles_max) * (size_t)p->sums * sizeof(double);
     p->off_dz = p->off_span + (size_t)(B * C) * 2 * sizeof(double);
-    p->workspace_needed = p->off_dz + (size_t)(B * p->chan_blocks) * kNormZq * (size_t)plane * sizeof(float);
+    p->workspace_needed = p->off_dz + (plain ? (size_t)0 : (size_t)(B * p->chan_blocks) * kNormZq * (size_t)plane * sizeof(float));
     return CGIC_OK;
 }
 
@@ -108,51 +119,57 @@ inline bool norm_regions_overlap(const NormRegion &a, const NormRegion &b)
 // CGIC_OK and the plan, or the error code of the call and *why
 inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
 {
-    const int rc = norm_bwd_shape(c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why);
+    const int rc = norm_bwd_shape(c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why, c.plain);
     if (rc != CGIC_OK) return rc;
+    const char *nm = c.plain ? "group_norm_backward" : "spatial_norm_backward";
     const auto refuse = [&](int code) { *why = p->why_text; return code; };
     // ---- the types: go and df are fp32 or the features' own type
     const int both[2] = {c.go_dtype, c.df_dtype};
     for (int i = 0; i < 2; ++i)
         if (both[i] != CGIC_DT_F32 && both[i] != c.in_dtype) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: %s %d with in_dtype %d (CGIC_DT_F32 or the features' own type)",
+            snprintf(p->why_text, sizeof(p->why_text), "%s: %s %d with in_dtype %d (CGIC_DT_F32 or the features' own type)", nm,
                      i ? "df_dtype" : "go_dtype", both[i], c.in_dtype);
             return refuse(both[i] == CGIC_DT_F16 || both[i] == CGIC_DT_BF16 ? CGIC_ERR_UNSUPPORTED : CGIC_ERR_INVALID);
         }
     // ---- zq's grid
-    if (c.hq <= 0 || c.wq <= 0) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: zq grid %lldx%lld", (long long)c.hq, (long long)c.wq);
+    p->ymul = p->ydiv = p->xmul = p->xdiv = 1;     // (what the plain call, which has no zq, keeps)
+    if (!c.plain && (c.hq <= 0 || c.wq <= 0)) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s: zq grid %lldx%lld", nm, (long long)c.hq, (long long)c.wq);
         return refuse(CGIC_ERR_INVALID);
     }
-    if (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || c.B * kNormZq * c.hq * c.wq >= ((int64_t)1 << 38) ||
-        !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv)) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)",
+    if (!c.plain && (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || c.B * kNormZq * c.hq * c.wq >= ((int64_t)1 << 38) ||
+        !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv))) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)", nm,
                  (long long)c.hq, (long long)c.wq, (long long)c.H, (long long)c.W);
         return refuse(CGIC_ERR_UNSUPPORTED);
     }
     // ---- the pointers: every input, the outputs that are wanted
     const int ib = norm_dtype_bytes(c.in_dtype), gb = norm_dtype_bytes(c.go_dtype), db = norm_dtype_bytes(c.df_dtype);
-    const int64_t numel = c.B * c.C * c.H * c.W, nzq = c.B * kNormZq * c.hq * c.wq;
+    const int64_t numel = c.B * c.C * c.H * c.W, nzq = c.plain ? 0 : c.B * kNormZq * c.hq * c.wq;
     const int kIn = 10, kOut = 8;
-    const NormRegion r[kIn + kOut] = {
+    NormRegion r[kIn + kOut] = {
         {c.f, numel * ib, ib}, {c.go, numel * gb, gb}, {c.zq, nzq * 4, 4}, {c.stats, p->spans * 8, 4}, {c.gn_weight, c.C * 4, 4},
         {c.gn_bias, c.C * 4, 4}, {c.wy, c.C * kNormZq * 4, 4}, {c.by, c.C * 4, 4}, {c.wb, c.C * kNormZq * 4, 4}, {c.bb, c.C * 4, 4},
         {c.df, numel * db, db}, {c.dzq, nzq * 4, 4}, {c.dgn_weight, c.C * 4, 4}, {c.dgn_bias, c.C * 4, 4}, {c.dwy, c.C * kNormZq * 4, 4},
         {c.dby, c.C * 4, 4}, {c.dwb, c.C * kNormZq * 4, 4}, {c.dbb, c.C * 4, 4}};
+    // the plain call: zq, the conv parameters and their gradients do not exist (address 0 overlaps nothing and is aligned)
+    const auto absent = [&](int i) { return c.plain && (i == 2 || (i >= 6 && i < kIn) || i == kIn + 1 || i >= kIn + 4); };
+    for (int i = 0; i < kIn + kOut; ++i)
+        if (absent(i)) r[i].addr = 0;
     for (int i = 0; i < kIn; ++i)
-        if (!r[i].addr) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: NULL input");
+        if (!r[i].addr && !absent(i)) {
+            snprintf(p->why_text, sizeof(p->why_text), "%s: NULL input", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     bool any = false;
     for (int i = kIn; i < kIn + kOut; ++i) any = any || r[i].addr;
     if (!any) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: no gradient is wanted (every output is NULL)");
+        snprintf(p->why_text, sizeof(p->why_text), "%s: no gradient is wanted (every output is NULL)", nm);
         return refuse(CGIC_ERR_INVALID);
     }
     for (int i = 0; i < kIn + kOut; ++i)
         if (r[i].addr % (uintptr_t)r[i].align) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: a pointer is not aligned to its %d-byte element", r[i].align);
+            snprintf(p->why_text, sizeof(p->why_text), "%s: a pointer is not aligned to its %d-byte element", nm, r[i].align);
             return refuse(CGIC_ERR_INVALID);
         }
     // ---- aliasing: an output overlaps nothing, except that df may be go itself when their types are equal (apply reads a unit of
@@ -162,24 +179,24 @@ inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
         for (int i = 0; i < o; ++i) {
             if (o == kIn && i == 1 && p->in_place) continue;
             if (norm_regions_overlap(r[o], r[i])) {
-                snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: an output overlaps another tensor of the call (only df == go with equal types may)");
+                snprintf(p->why_text, sizeof(p->why_text), "%s: an output overlaps another tensor of the call (only df == go with equal types may)", nm);
                 return refuse(CGIC_ERR_INVALID);
             }
         }
     // ---- the workspace
     if (!c.workspace || c.workspace_bytes < p->workspace_needed) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: workspace of %zu bytes, need %zu (cgic_spatial_norm_backward_workspace_bytes)",
-                 c.workspace ? c.workspace_bytes : (size_t)0, p->workspace_needed);
+        snprintf(p->why_text, sizeof(p->why_text), "%s: workspace of %zu bytes, need %zu (cgic_%s_workspace_bytes)", nm,
+                 c.workspace ? c.workspace_bytes : (size_t)0, p->workspace_needed, nm);
         return refuse(CGIC_ERR_CAPACITY);
     }
     if (c.workspace % 16) {                         // (the dz partials are written 16 bytes at a time)
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: the workspace is not aligned to 16 bytes");
+        snprintf(p->why_text, sizeof(p->why_text), "%s: the workspace is not aligned to 16 bytes", nm);
         return refuse(CGIC_ERR_INVALID);
     }
     const NormRegion ws = {c.workspace, (int64_t)p->workspace_needed, 16};
     for (int i = 0; i < kIn + kOut; ++i)
         if (norm_regions_overlap(ws, r[i])) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: the workspace overlaps a tensor of the call");
+            snprintf(p->why_text, sizeof(p->why_text), "%s: the workspace overlaps a tensor of the call", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     // ---- the unit: 16 bytes of the feature type where the row width and the pointers of f, go and df allow, else fewer
@@ -193,18 +210,18 @@ inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
     }
     p->unit = unit;
     p->mg_w = norm_magic(c.H * c.W, c.W);
-    p->mg_y = norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
-    p->mg_x = norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
-    p->zq_vec = p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
+    p->mg_y = c.plain ? 0u : norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
+    p->mg_x = c.plain ? 0u : norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
+    p->zq_vec = !c.plain && p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
     // ---- the grids
     const int64_t plane_units = c.H * c.W / unit;
     p->threads_reduce = plane_units <= 64 ? 64 : plane_units <= 128 ? 128 : kNormBwdThreads;
     p->tiles = (plane_units + p->threads_reduce - 1) / p->threads_reduce;       // (<= tiles_max: at most ceil(H * W / 256), or 1)
     p->grid_reduce = c.B * p->chan_blocks * p->tiles;
-    p->need_dz = c.dzq != 0;
-    p->need_conv = c.dwy || c.dby || c.dwb || c.dbb;
+    p->need_dz = r[kIn + 1].addr != 0;
+    p->need_conv = r[kIn + 4].addr || r[kIn + 5].addr || r[kIn + 6].addr || r[kIn + 7].addr;
     p->need_df = c.df != 0;
-    p->grid_sums = (c.C * kNormBwdSums + kNormBwdThreads - 1) / kNormBwdThreads;
+    p->grid_sums = (c.C * p->sums + kNormBwdThreads - 1) / kNormBwdThreads;
     p->grid_dzq = p->need_dz ? (nzq + kNormBwdThreads - 1) / kNormBwdThreads : 0;
     if (c.df) {
         p->parts = (plane_units + kNormPartUnits - 1) / kNormPartUnits;
@@ -220,20 +237,22 @@ inline int norm_train_plan(const NormCall &c, uintptr_t stats, NormPlan *p, cons
 {
     const int rc = norm_plan(c, p, why);
     if (rc != CGIC_OK || p->form == 0) return rc;
+    const char *nm = c.plain ? "group_norm_train" : "spatial_norm_train";
+    const auto gone = [&](uintptr_t a) { return c.plain ? (uintptr_t)0 : a; };      // (the plain call has no zq and no conv parameters)
     const auto refuse = [&](int code) { *why = p->why_text; return code; };
     if (!stats || stats % 4) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_train: stats is %s", stats ? "not aligned to its 4-byte element" : "NULL");
+        snprintf(p->why_text, sizeof(p->why_text), "%s: stats is %s", nm, stats ? "not aligned to its 4-byte element" : "NULL");
         return refuse(CGIC_ERR_INVALID);
     }
     const int ib = norm_dtype_bytes(c.in_dtype), ob = norm_dtype_bytes(c.out_dtype);
     const int64_t numel = c.B * c.C * c.H * c.W;
     const NormRegion st = {stats, p->spans * 8, 4};
-    const NormRegion r[10] = {{c.f, numel * ib, ib}, {c.zq, c.B * kNormZq * c.hq * c.wq * 4, 4}, {c.gn_weight, c.C * 4, 4}, {c.gn_bias, c.C * 4, 4},
-                              {c.wy, c.C * kNormZq * 4, 4}, {c.by, c.C * 4, 4}, {c.wb, c.C * kNormZq * 4, 4}, {c.bb, c.C * 4, 4},
-                              {c.out, numel * ob, ob}, {p->workspace_needed ? c.workspace : 0, (int64_t)p->workspace_needed, 8}};
+    const NormRegion r[10] = {{c.f, numel * ib, ib}, {gone(c.zq), c.B * kNormZq * c.hq * c.wq * 4, 4}, {c.gn_weight, c.C * 4, 4}, {c.gn_bias, c.C * 4, 4},
+                              {gone(c.wy), c.C * kNormZq * 4, 4}, {gone(c.by), c.C * 4, 4}, {gone(c.wb), c.C * kNormZq * 4, 4},
+                              {gone(c.bb), c.C * 4, 4}, {c.out, numel * ob, ob}, {p->workspace_needed ? c.workspace : 0, (int64_t)p->workspace_needed, 8}};
     for (int i = 0; i < 10; ++i)
         if (norm_regions_overlap(st, r[i])) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_train: stats overlaps another tensor of the call");
+            snprintf(p->why_text, sizeof(p->why_text), "%s: stats overlaps another tensor of the call", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     return CGIC_OK;

@@ -14,10 +14,13 @@
 //                 the caller's workspace (and the span's first element, K, once per span) -- and norm_apply_kernel, element-wise, whose workgroups add their span's `chunks`
 //                 partials in chunk order.  Ordered by the stream; no workgroup waits for another.
 // The chunk count depends on the shape alone (not on the pointers), so the workspace can be sized without them.
+// NormCall::plain (value-initialised: false, the modulated call) plans cgic_group_norm: no zq grid is checked, the pointers of zq,
+// conv_y and conv_b are neither required nor overlap-tested, every other check is the same under the name group_norm.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/cgic_hip.h"
 
@@ -45,6 +48,7 @@ struct NormCall {
     uintptr_t f, zq, gn_weight, gn_bias, wy, by, wb, bb, out;
     uintptr_t workspace;
     size_t workspace_bytes;
+    bool plain;                     // cgic_group_norm: no zq and no conv_y / conv_b (hq, wq and their five pointers are not looked at)
 };
 
 struct NormPlan {
@@ -110,6 +114,14 @@ inline int norm_form(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, i
     return CGIC_OK;
 }
 
+// a refusal of the shape part reads "spatial_norm...": the same text under the plain call's name, "group_norm..."
+inline void norm_as_group(char *text)
+{
+    if (strncmp(text, "spatial", 7)) return;
+    memcpy(text, "group", 5);
+    memmove(text + 5, text + 7, strlen(text + 7) + 1);
+}
+
 // the nearest index of one axis (torch's "nearest" at an integer ratio): up-sampling src = dst / (n / nq), sub-sampling
 // src = dst * (nq / n); any other ratio is not built
 inline bool norm_ratio(int64_t n, int64_t nq, int *mul, int *div)
@@ -132,21 +144,26 @@ inline unsigned int norm_magic(int64_t nmax, int64_t d)
 inline int norm_plan(const NormCall &c, NormPlan *p, const char **why)
 {
     const int rc = norm_form(c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why);
-    if (rc != CGIC_OK) return rc;
+    if (rc != CGIC_OK) {
+        if (c.plain) norm_as_group(p->why_text);
+        return rc;
+    }
+    const char *nm = c.plain ? "group_norm" : "spatial_norm";
     const auto refuse = [&](int code) { *why = p->why_text; return code; };
     // ---- the type pair: F32 -> F32; F16 | BF16 -> F32 | the same
     if (c.out_dtype != CGIC_DT_F32 && c.out_dtype != c.in_dtype) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: out_dtype %d with in_dtype %d (CGIC_DT_F32 or the features' own type)",
+        snprintf(p->why_text, sizeof(p->why_text), "%s: out_dtype %d with in_dtype %d (CGIC_DT_F32 or the features' own type)", nm,
                  c.out_dtype, c.in_dtype);
         return refuse(c.out_dtype == CGIC_DT_F16 || c.out_dtype == CGIC_DT_BF16 ? CGIC_ERR_UNSUPPORTED : CGIC_ERR_INVALID);
     }
-    // ---- zq's grid
-    if (c.hq <= 0 || c.wq <= 0) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: zq grid %lldx%lld", (long long)c.hq, (long long)c.wq);
+    // ---- zq's grid (the plain call has none: every index ratio stays 1)
+    p->ymul = p->ydiv = p->xmul = p->xdiv = 1;
+    if (!c.plain && (c.hq <= 0 || c.wq <= 0)) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s: zq grid %lldx%lld", nm, (long long)c.hq, (long long)c.wq);
         return refuse(CGIC_ERR_INVALID);
     }
-    if (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv)) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)",
+    if (!c.plain && (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv))) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)", nm,
                  (long long)c.hq, (long long)c.wq, (long long)c.H, (long long)c.W);
         return refuse(CGIC_ERR_UNSUPPORTED);
     }
@@ -154,15 +171,16 @@ inline int norm_plan(const NormCall &c, NormPlan *p, const char **why)
     // ---- the pointers
     const int ib = norm_dtype_bytes(c.in_dtype), ob = norm_dtype_bytes(c.out_dtype);
     const uintptr_t all[9] = {c.f, c.zq, c.gn_weight, c.gn_bias, c.wy, c.by, c.wb, c.bb, c.out};
+    const auto absent = [&](int i) { return c.plain && (i == 1 || (i >= 4 && i < 8)); };     // zq, wy, by, wb, bb of the plain call
     for (int i = 0; i < 9; ++i)
-        if (!all[i]) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: NULL tensor");
+        if (!all[i] && !absent(i)) {
+            snprintf(p->why_text, sizeof(p->why_text), "%s: NULL tensor", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     for (int i = 0; i < 9; ++i) {
         const int eb = i == 0 ? ib : i == 8 ? ob : 4;
-        if (all[i] % (uintptr_t)eb) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: a pointer is not aligned to its %d-byte element", eb);
+        if (!absent(i) && all[i] % (uintptr_t)eb) {
+            snprintf(p->why_text, sizeof(p->why_text), "%s: a pointer is not aligned to its %d-byte element", nm, eb);
             return refuse(CGIC_ERR_INVALID);
         }
     }
@@ -175,26 +193,26 @@ inline int norm_plan(const NormCall &c, NormPlan *p, const char **why)
         {c.f, numel * ib}, {c.zq, c.B * kNormZq * c.hq * c.wq * 4}, {c.gn_weight, c.C * 4}, {c.gn_bias, c.C * 4},
         {c.wy, c.C * kNormZq * 4}, {c.by, c.C * 4}, {c.wb, c.C * kNormZq * 4}, {c.bb, c.C * 4}};
     for (int i = (p->in_place ? 1 : 0); i < 8; ++i)
-        if (c.out < in[i].addr + (uintptr_t)in[i].bytes && in[i].addr < out_end) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: out overlaps an input (only out == f with equal types, the in-place form, may)");
+        if (!absent(i) && c.out < in[i].addr + (uintptr_t)in[i].bytes && in[i].addr < out_end) {
+            snprintf(p->why_text, sizeof(p->why_text), "%s: out overlaps an input (only out == f with equal types, the in-place form, may)", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     // ---- the workspace of the two-launch form
     if (p->workspace_needed) {
         if (!c.workspace || c.workspace_bytes < p->workspace_needed) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: workspace of %zu bytes, need %zu (cgic_spatial_norm_workspace_bytes)",
+            snprintf(p->why_text, sizeof(p->why_text), "%s: workspace of %zu bytes, need %zu (cgic_spatial_norm_workspace_bytes)", nm,
                      c.workspace ? c.workspace_bytes : (size_t)0, p->workspace_needed);
             return refuse(CGIC_ERR_CAPACITY);
         }
         if (c.workspace % 8) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: the workspace is not aligned to 8 bytes");
+            snprintf(p->why_text, sizeof(p->why_text), "%s: the workspace is not aligned to 8 bytes", nm);
             return refuse(CGIC_ERR_INVALID);
         }
         const uintptr_t ws_end = c.workspace + (uintptr_t)p->workspace_needed;
         bool clash = c.workspace < out_end && c.out < ws_end;
-        for (int i = 0; i < 8; ++i) clash = clash || (c.workspace < in[i].addr + (uintptr_t)in[i].bytes && in[i].addr < ws_end);
+        for (int i = 0; i < 8; ++i) clash = clash || (!absent(i) && c.workspace < in[i].addr + (uintptr_t)in[i].bytes && in[i].addr < ws_end);
         if (clash) {
-            snprintf(p->why_text, sizeof(p->why_text), "spatial_norm: the workspace overlaps a tensor of the call");
+            snprintf(p->why_text, sizeof(p->why_text), "%s: the workspace overlaps a tensor of the call", nm);
             return refuse(CGIC_ERR_INVALID);
         }
     }
@@ -207,9 +225,9 @@ inline int norm_plan(const NormCall &c, NormPlan *p, const char **why)
     }
     p->unit = unit;
     p->mg_w = norm_magic(c.H * c.W, c.W);
-    p->mg_y = norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
-    p->mg_x = norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
-    p->zq_vec = p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
+    p->mg_y = c.plain ? 0u : norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
+    p->mg_x = c.plain ? 0u : norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
+    p->zq_vec = !c.plain && p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
     const int64_t units = p->span / unit;           // (W % unit == 0, and the span is whole rows)
     if (p->form == 1) {
         p->grid_one = p->spans;

@@ -15,6 +15,7 @@ from . import merge as _merge
 from . import norm as _norm
 from .attention import patch_attention as _patch_attention      # (the package exports the FUNCTION attention under the module's name)
 from . import rate as _rate
+from . import resblock as _resblock
 from .codec import GrainCodec
 from .entropy import Entropy
 from .indices_coding import HuffmanCoding
@@ -165,7 +166,7 @@ class AvgPool(torch.nn.Module):
 
 
 def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_norms=False, patch_attention=False, norm_backward=False,
-            attention_backward=False):
+            attention_backward=False, patch_group_norms=False, patch_resblocks=False):
     """swap VectorQuantize2 / Entropy / router target / compress of a reference CGIC instance in place.
     patch_pools: the decoder's two average pools in front of its masked blends (decoder.avgpool_layer1 / _layer2,
     decoder.py:304-305,366-367) become control_gic_amd.model.AvgPool -- they are modules, so they can be swapped.  The three
@@ -196,7 +197,23 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
     28 GiB for 2.7x the time; fp32 3x to 90x less memory for 8x the time; no shape is faster (profiles/attention_backward.md).  Off by
     default, also where patch_attention is on: the gradients agree with torch's only within rounding, and the switch buys memory,
     not time -- set it where the attention blocks' activations limit the batch or the tile.  Without patch_attention there is no
-    block to set it on and the call raises (norm_backward without patch_norms is ignored, as it always was: that behaviour is kept)."""
+    block to set it on and the call raises (norm_backward without patch_norms is ignored, as it always was: that behaviour is kept).
+    patch_group_norms: every affine torch.nn.GroupNorm that is not the norm_layer of a SpatialNorm-shaped module -- the encoder's
+    Normalize (vqvae_blocks.py:34) in its ResnetBlocks, AttnBlocks and norm_out heads -- becomes control_gic_amd.norm.GroupNorm, a
+    subclass on the same parameters: the same kernel family without zq under no_grad, F.group_norm when a gradient is needed or, with
+    norm_backward=True, the library's training forward and backward kernels (GroupNorm.backward_kernel on the norms swapped in here).
+    patch_resblocks: every module with the shape of the reference's ResnetBlock (vqvae_blocks.py:78-137, decoder.py:99-158: norm1,
+    conv1, norm2, dropout, conv2, in_channels, out_channels, use_conv_shortcut) becomes control_gic_amd.resblock.ResnetBlock on the
+    same submodules, which passes swish=True to its norms where they are the library's (patch_group_norms / patch_norms) so that the
+    swish runs inside the norm kernel, and under autocast takes the half type straight from the kernel.  The encoder's three
+    norm_out + nonlinearity pairs are inline in Encoder.forward: INTEGRATION.md section 3f shows the one-line edit.  Both are off by
+    default for the reason patch_norms is, and install() with neither produces exactly the module tree it produced before.  Measured
+    against torch's group_norm + swish over the encoder's shapes at B = 8 and 1 (profiles/group_norm.md): 2.6x to 7.3x faster at the
+    256x256 and 128x128 levels, forward and forward + backward, with 2x to 6.4x less peak memory.  SLOWER than torch's path where the
+    features are small, beyond the run-to-run spread: forward in fp32 at [8,512,16,16] (0.84x) and at B = 1 from 64x64 down (0.70x to
+    0.85x); forward + backward of a single layer at B = 8 from 64x64 down and at B = 1 from 128x128 down (0.58x to 0.88x) -- a call of
+    the kernel route costs about 0.03 ms forward and 0.10 to 0.14 ms forward + backward in Python and launches, torch's two small
+    kernels 0.02 to 0.03 ms.  Under autocast the forward is never slower."""
     old = model.quantize
     dev = old.embedding.weight.device
     q = VectorQuantize2(old.n_e, old.e_dim, beta=old.beta, legacy=getattr(old, "legacy", True))
@@ -228,6 +245,10 @@ def install(model, per_image=False, fuse_convs=True, patch_pools=True, patch_nor
         raise ValueError("install: attention_backward=True sets AttnBlock.backward_kernel on the blocks that patch_attention=True swaps in; without it there are none")
     if patch_norms:
         _norm.patch_norms(model, backward_kernel=norm_backward)
+    if patch_group_norms:
+        _norm.patch_group_norms(model, backward_kernel=norm_backward)
+    if patch_resblocks:
+        _resblock.patch_resblocks(model)
     model.compress = types.MethodType(compress, model)
     model.compress_batch = types.MethodType(compress_batch, model)
     model.compress_to_bpp = types.MethodType(_rate.compress_to_bpp, model)

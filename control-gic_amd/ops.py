@@ -16,6 +16,7 @@ functions the module classes use (each entry point of libcgic_hip.so is bound on
     pmap   = torch.ops.cgic.partition_map(x, mc, mm, mf, False)                                   # the grain grid drawn into the batch (draw.py:78-119)
     blob, total = torch.ops.cgic.container_pack(data, nbytes, mode, 256, 256, 0)                  # the batch as a container file, on the device
     new_f  = torch.ops.cgic.spatial_norm(f, zq, gn_w, gn_b, wy, by, wb, bb, 32, 1e-6, False, False) # the decoder's SpatialNorm (decoder.py:34-53); defined in norm.py, next to its module
+    h      = torch.ops.cgic.group_norm(f, gn_w, gn_b, 32, 1e-6, True, False)                      # the encoder's GroupNorm (+ swish) on the same kernels without zq; norm.py (group_norm_train: differentiable)
     h_     = torch.ops.cgic.attention(q, k, v, int(C) ** -0.5, False)                            # AttnBlock's softmax(q^T k) v without the [B,N,N] matrix; defined in attention.py, next to its module
     h_, lse = torch.ops.cgic.attention_train(q, k, v, int(C) ** -0.5)                             # the same, differentiable: its backward is csrc/cgic_attn_bwd.hip, no [B,N,N] matrix there either
 

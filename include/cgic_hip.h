@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 20
+#define CGIC_ABI_VERSION 21
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -729,6 +729,32 @@ int cgic_spatial_norm_backward(const void *f, int in_dtype, const void *go, int 
                                void *df, int df_dtype, float *dzq, float *dgn_weight, float *dgn_bias, float *dwy, float *dby,
                                float *dwb, float *dbb, void *workspace, size_t workspace_bytes, cgic_stream_t stream);
 size_t cgic_spatial_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
+
+/* ---------------------------------------------------------------------------
+ * The encoder's GroupNorm (ABI 21) -- CGIC/modules/vqvae/vqvae_blocks.py:34, GroupNorm(groups, eps, affine), and on request the swish
+ * that ResnetBlock and the norm_out heads put behind it: the kernels above instantiated without zq (no zq, y or b value is loaded
+ * or multiplied), for inference and for training.
+ *   f, groups, eps, gn_weight, gn_bias, swish, out, workspace: as cgic_spatial_norm's; the workspace is sized by
+ *   cgic_spatial_norm_workspace_bytes and the form answered by cgic_spatial_norm_one_launch (both depend on the shape alone).
+ * Values: the same statistics; per element in fp32, without contraction: v = ((x - mean) * rstd) * gamma + beta, with swish
+ * v / (1 + exp(-v)).  On finite inputs this is bit for bit cgic_spatial_norm with wy = wb = 0, by = 1, bb = 0.
+ * cgic_group_norm_train also writes stats [B * groups][2] = (mean, rstd); its out is cgic_group_norm's bit for bit.
+ * cgic_group_norm_backward: df, dgn_weight (sum go' * xhat) and dgn_bias (sum go'), each optional (NULL), at least one wanted; go' is
+ * go, with swish go times the swish's derivative at the recomputed v.  The same three launches (reduce, finish, apply) with two
+ * float64 plane sums per channel; no atomics; df may be go itself when the types are equal.  workspace:
+ * cgic_group_norm_backward_workspace_bytes(...) bytes, 16-byte aligned, need not be zeroed.
+ * Every check precedes the first launch (the same refusals as the modulated calls, under the names group_norm, group_norm_train
+ * and group_norm_backward); not available inside a launch group.
+ * ------------------------------------------------------------------------- */
+int cgic_group_norm(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups, double eps, const float *gn_weight,
+                    const float *gn_bias, int swish, void *out, int out_dtype, void *workspace, size_t workspace_bytes, cgic_stream_t stream);
+int cgic_group_norm_train(const void *f, int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups, double eps, const float *gn_weight,
+                          const float *gn_bias, int swish, void *out, int out_dtype, float *stats, void *workspace, size_t workspace_bytes,
+                          cgic_stream_t stream);
+int cgic_group_norm_backward(const void *f, int in_dtype, const void *go, int go_dtype, int64_t B, int C, int64_t H, int64_t W, int groups,
+                             const float *stats, const float *gn_weight, const float *gn_bias, int swish, void *df, int df_dtype,
+                             float *dgn_weight, float *dgn_bias, void *workspace, size_t workspace_bytes, cgic_stream_t stream);
+size_t cgic_group_norm_backward_workspace_bytes(int in_dtype, int64_t B, int C, int64_t H, int64_t W, int groups);
 
 /* ---------------------------------------------------------------------------
  * AttnBlock's attention (ABI 18) -- CGIC/modules/vqvae/decoder.py:189-213, vqvae_blocks.py:168-193:
