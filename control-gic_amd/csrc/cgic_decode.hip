@@ -887,15 +887,14 @@ __device__ __forceinline__ void merge_body(const MergeArgs &a, const Blk blk, un
     __syncthreads();
     CGIC_STAMP(11);
 
-    // a mask stream must be exactly 1 + n/8 + 1 bytes with pad = 8 - n%8 (mask_coding.py:19-26)
-    if (tid == 0) {
-        if (send_mc && (s_hdr[0] != 2 + (n_c >> 3) || (int)(rawc[0] & 0xFF) != 8 - (int)(n_c & 7))) s_status = CGIC_ERR_INVALID;
-        if (send_mm && (s_hdr[1] != 2 + (n_m >> 3) || (int)(rawm[0] & 0xFF) != 8 - (int)(n_m & 7))) s_status = CGIC_ERR_INVALID;
-    }
-    __syncthreads();
-    if (s_status) {
+    // a mask stream must be exactly 1 + n/8 + 1 bytes with pad = 8 - n%8 (mask_coding.py:19-26).  Every thread reads the two
+    // lengths and the two header bytes behind the barrier that follows the loads (round 7: thread 0 alone + a second barrier before)
+    bool hdr_bad = false;
+    if (send_mc && (s_hdr[0] != 2 + (n_c >> 3) || (int)(rawc[0] & 0xFF) != 8 - (int)(n_c & 7))) hdr_bad = true;
+    if (send_mm && (s_hdr[1] != 2 + (n_m >> 3) || (int)(rawm[0] & 0xFF) != 8 - (int)(n_m & 7))) hdr_bad = true;
+    if (hdr_bad) {                                        // (the same LDS words in every thread: workgroup-uniform)
         if (WAIT) wait_decoded(done, need, total);        // (the decoder's first workgroup initialises status[b])
-        if (tid == 0 && a.status) atomicMin(&a.status[b], s_status);
+        if (tid == 0 && a.status) atomicMin(&a.status[b], CGIC_ERR_INVALID);
         return;
     }
     // MSB-first stream bytes (after the header byte) -> LSB-first bit words
@@ -1019,7 +1018,7 @@ __device__ __forceinline__ void merge_body(const MergeArgs &a, const Blk blk, un
     };
     // fine symbols consumed by the rows above this band (exact for any mask bits)
     uint32_t fbase = 0;
-    {
+    if (r0 > 0) {                       // (the first band -- every workgroup of the one-band launch -- has no rows above: two barriers less)
         // the flag is constant over a 2x2 medium cell: walk the medium cells of the rows above (rows by wave, columns by
         // lane, no divisions) and count 4 per cell.  (The per-position loop cost the LAST band of a 768x768 tile 70 trips of
         // ~40 instructions -- the merge launch took twice as long as its first band.)

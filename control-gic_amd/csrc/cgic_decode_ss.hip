@@ -254,7 +254,9 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
     __shared__ int s_scan[kDecWaves + 1];
-    __shared__ int s_base[4];
+    __shared__ int s_at[2][2];          // streams 1 and 2: the wave that owns the first chunk, the codewords before it inside that wave
+    __shared__ int s_capped[2];         // a wave ran out of sweeps, by parity of the round it happened in (never cleared: it ends the loop)
+    __shared__ int s_sweeps;            // the most walks after the first that a wave made
     __shared__ MeFn s_fn[kDecWaves];
     uint32_t *lut = sm;                                             // [1 << lut_bits]
     uint8_t *stage = reinterpret_cast<uint8_t *>(lut + (1 << a.tab.lut_bits));
@@ -266,30 +268,27 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
     int nb[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) nb[s] = (a.stream_mask >> s & 1) ? a.nbytes[b * CGIC_NUM_STREAMS + s] : -2;
-    const int pad[3] = {in0[0], in0[a.slot], in0[2 * a.slot]};      // (slot memory is always readable)
-    {   // LUT -> LDS: eight 16-byte loads in flight per thread (a plain strided loop pays one memory round trip per trip:
-        // 32 trips of a 256-thread workgroup = 25 us)
-        const uint4 *gl = reinterpret_cast<const uint4 *>(a.tab.lut);
-        uint4 *dl = reinterpret_cast<uint4 *>(lut);
-        const int n4 = (1 << a.tab.lut_bits) >> 2;
-        // every code fits the LUT window (ss_walk's predicated loop): "no such prefix" (length 0) is staged as length 255, which
-        // ends a walk without a test of its own
-        const bool mark = a.tab.max_len <= a.tab.lut_bits;
-        auto fix = [mark](uint32_t e) { return mark && (e & 0xFFu) == 0u ? e | 0xFFu : e; };
-        if (n4 == 0 && tid < (1 << a.tab.lut_bits)) lut[tid] = fix(a.tab.lut[tid]);      // (a table of two symbols: a 2-entry LUT)
-        for (int base = 0; base < n4; base += 8 * T) {
-            uint4 v[8];
+    // (slot memory is always readable.)  The pad count is byte 0 of the slot, fetched as the slot's first aligned word: a scalar load,
+    // which is not counted with the vector loads of the LUT that follow and so is waited for without them
+    auto pad_of = [&](int s) { return (int)(*reinterpret_cast<const uint32_t *>(in0 + s * a.slot) & 0xFFu); };
+    const int pad[3] = {pad_of(0), pad_of(1), pad_of(2)};
+    // Setup in ONE memory round trip (round 7): the first eight LUT loads of every thread are issued, the stream layout is computed
+    // from the byte counts and pad bytes (requested before them) while they fly, the stream loads follow at once, and only then is
+    // anything waited for and written to LDS.  (Before: LUT loads -> wait -> LDS, layout, stream loads -> wait -> LDS.)
+    // LUT -> LDS: eight 16-byte loads in flight per thread (a plain strided loop pays one memory round trip per trip:
+    // 32 trips of a 256-thread workgroup = 25 us)
+    const uint4 *gl = reinterpret_cast<const uint4 *>(a.tab.lut);
+    uint4 *dl = reinterpret_cast<uint4 *>(lut);
+    const int n4 = (1 << a.tab.lut_bits) >> 2;
+    // every code fits the LUT window (ss_walk's predicated loop): "no such prefix" (length 0) is staged as length 255, which
+    // ends a walk without a test of its own
+    const bool mark = a.tab.max_len <= a.tab.lut_bits;
+    auto fix = [mark](uint32_t e) { return mark && (e & 0xFFu) == 0u ? e | 0xFFu : e; };
+    uint4 v0[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int i = base + k * T + tid;
-                v[k] = i < n4 ? gl[i] : uint4{0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int i = base + k * T + tid;
-                if (i < n4) dl[i] = uint4{fix(v[k].x), fix(v[k].y), fix(v[k].z), fix(v[k].w)};
-            }
-        }
+    for (int k = 0; k < 8; ++k) {
+        const int i = k * T + tid;
+        v0[k] = i < n4 ? gl[i] : uint4{0u, 0u, 0u, 0u};
     }
     const int64_t n_c = (a.h >> 2) * (a.w >> 2), n_m = (a.h >> 1) * (a.w >> 1), n_f = a.h * a.w;
     const int cap[3] = {(int)n_c, (int)n_m, (int)n_f};
@@ -316,18 +315,46 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
             if (nb[s] <= 0) a.dcount[b * 3 + s] = nb[s] == 0 ? -1 : -2;             // empty file (None) / not sent
             else if (!fits) a.dcount[b * 3 + s] = -3;
         }
+        s_capped[0] = 0; s_capped[1] = 0; s_sweeps = 0;
     }
     if (!fits) return;
     CGIC_STAMP3(1);
-    // stage the stream bytes (16-byte copies; the tail beyond the stream is never interpreted: every walk checks `rem`)
+    // the stream bytes (16-byte copies; the tail beyond the stream is never interpreted: every walk checks `rem`): every thread's
+    // first copy of each stream joins the LUT loads in flight
+    const int slot4 = (int)(a.slot >> 4);                           // stay inside the slot
+    uint4 u0[3];
+    int words[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-        if (!L.nbits[s]) continue;
-        const int words = ((((L.nbits[s] + 7) >> 3) + 1 + 24 + 15) & ~15) >> 4;
+        words[s] = L.nbits[s] ? ((((L.nbits[s] + 7) >> 3) + 1 + 24 + 15) & ~15) >> 4 : 0;
+        const uint4 *g = reinterpret_cast<const uint4 *>(in0 + s * a.slot);
+        u0[s] = tid < words[s] && tid < slot4 ? g[tid] : uint4{0u, 0u, 0u, 0u};
+    }
+    if (n4 == 0 && tid < (1 << a.tab.lut_bits)) lut[tid] = fix(a.tab.lut[tid]);      // (a table of two symbols: a 2-entry LUT)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int i = k * T + tid;
+        if (i < n4) dl[i] = uint4{fix(v0[k].x), fix(v0[k].y), fix(v0[k].z), fix(v0[k].w)};
+    }
+    for (int base = 8 * T; base < n4; base += 8 * T) {              // (a LUT of more than 32 entries per thread)
+        uint4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = base + k * T + tid;
+            v[k] = i < n4 ? gl[i] : uint4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = base + k * T + tid;
+            if (i < n4) dl[i] = uint4{fix(v[k].x), fix(v[k].y), fix(v[k].z), fix(v[k].w)};
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
         const uint4 *g = reinterpret_cast<const uint4 *>(in0 + s * a.slot);
         uint4 *d = reinterpret_cast<uint4 *>(stage + L.off[s]);
-        const int lim = (int)(a.slot >> 4);                         // stay inside the slot
-        for (int i = tid; i < words; i += T) d[i] = i < lim ? g[i] : uint4{0u, 0u, 0u, 0u};
+        if (tid < words[s]) d[tid] = u0[s];
+        for (int i = tid + T; i < words[s]; i += T) d[i] = i < slot4 ? g[i] : uint4{0u, 0u, 0u, 0u};
     }
     __syncthreads();
     CGIC_STAMP3(2);
@@ -343,40 +370,88 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
     // re-synchronise -- one 13-bit codeword repeated: one sweep per chunk, 207 sweeps, 852 us -- is cut off after kSsMaxSweeps
     // and finished by the all-entries pass, whose running time does not depend on the data (56 us for that batch).
     bool stuck = false;
-    {
-        int prev = 0;
-        for (int g = g0; g < g1; ++g) {
-            // the guess: the smallest offset in the residue class the code lengths allow (0 when their gcd is 1); inside the
-            // lane's own run the predecessor is known
-            int e = prev;
-            if (is_first(g)) e = 0;
-            else if (g == g0) {
-                const int sg = (g >= L.c[1]) + (g >= L.c[2]);
-                const int chg = g - sel3(sg, L.c[0], L.c[1], L.c[2]);
-                const int m = (64 * chg) % a.tab.len_gcd;
-                e = m ? a.tab.len_gcd - m : 0;
-            }
-            int n;
-            prev = ss_walk<false>(a.tab, lut, stage, L, g, e, &n, nop);
-            ent[g] = (uint8_t)e; ext[g] = (uint8_t)prev; cnt[g] = (uint8_t)n;
+    // R == 1 (at most one chunk per lane: every image up to 256x256 at the usual ratios): the lane's chunk lives in registers --
+    // entry e1, exit x1, count n1 -- and a wave's 64 chunks are consecutive, so each wave runs the fix point ON ITS OWN (round 7).
+    // The predecessor's exit comes by a lane shift; only lane 0 looks into LDS, where the last lane of the wave before publishes
+    // its exit whenever it changes; a wave-wide ballot ends the wave's loop.  The workgroup meets when a wave is locally stable:
+    // if no wave published anything since the last meeting, every wave was stable against inputs that did not move, which is the
+    // fix point (unique, so the order of the walks does not matter).  Before, every sweep of every wave ended at a workgroup
+    // barrier and cost the slowest lane of the slowest wave plus an LDS round trip of three bytes per chunk.
+    const bool own = g0 < g1;
+    int e1 = 0, x1 = kSsEnd, n1 = 0;
+    if (R == 1) {
+        const bool first = own && is_first(g0);
+        volatile uint8_t *vext = ext;
+        if (own && !first) {                 // the guess: the smallest offset in the residue class the code lengths allow (0 when their gcd is 1)
+            const int sg = (g0 >= L.c[1]) + (g0 >= L.c[2]);
+            const int chg = g0 - sel3(sg, L.c[0], L.c[1], L.c[2]);
+            const int m = (64 * chg) % a.tab.len_gcd;
+            e1 = m ? a.tab.len_gcd - m : 0;
         }
-    }
-    __syncthreads();
-    CGIC_STAMP3(3);
-    for (;;) {
-        ++dbg_sweeps;
-        int changed = 0;
-        for (int g = g0; g < g1; ++g) {
-            const int e = is_first(g) ? 0 : ext[g - 1];
-            if (e != ent[g]) {
+        if (own) x1 = ss_walk<false>(a.tab, lut, stage, L, g0, e1, &n1, nop);
+        int pub = x1;                        // (last lane of a wave) what the next wave sees
+        if (lane == kWave - 1 && own) vext[g0] = (uint8_t)x1;
+        __syncthreads();
+        CGIC_STAMP3(3);
+        // kSsMaxSweeps bounds the walks of a lane over ALL rounds, as it bounded the sweeps: a stream that never re-synchronises
+        // reaches the all-entries pass after the same work
+        int walks = 0;
+        for (int round = 0;; ++round) {
+            int changed = 0;
+            bool need;
+            for (;;) {
+                int pe = __shfl_up(x1, 1, kWave);
+                if (lane == 0 && own && g0 > 0) pe = vext[g0 - 1];
+                if (first) pe = 0;
+                need = own && pe != e1;
+                if (__builtin_amdgcn_ballot_w64(need) == 0) break;                 // locally stable
+                if (all_entries && walks >= kSsMaxSweeps) break;                   // (wave-uniform) out of sweeps: `need` stays set
+                if (need) { x1 = ss_walk<false>(a.tab, lut, stage, L, g0, pe, &n1, nop); e1 = pe; }
+                ++walks;
+                if (lane == kWave - 1 && x1 != pub) { vext[g0] = (uint8_t)x1; pub = x1; changed = 1; }
+            }
+            // (the flag of round r is read after the barrier of round r and next written in round r + 2, behind the barrier of r + 1)
+            if (need) s_capped[round & 1] = 1;
+            if (!__syncthreads_or(changed | (int)need)) break;
+            if (s_capped[round & 1]) { stuck = true; break; }
+        }
+        if (lane == 0) atomicMax(&s_sweeps, walks + 1);        // (+ the check that found nothing to do: a sweep of the barrier loop)
+    } else {                                // several chunks per lane: one workgroup barrier per sweep, entry / exit / count in LDS
+        {
+            int prev = 0;
+            for (int g = g0; g < g1; ++g) {
+                // the guess: the smallest offset in the residue class the code lengths allow (0 when their gcd is 1); inside the
+                // lane's own run the predecessor is known
+                int e = prev;
+                if (is_first(g)) e = 0;
+                else if (g == g0) {
+                    const int sg = (g >= L.c[1]) + (g >= L.c[2]);
+                    const int chg = g - sel3(sg, L.c[0], L.c[1], L.c[2]);
+                    const int m = (64 * chg) % a.tab.len_gcd;
+                    e = m ? a.tab.len_gcd - m : 0;
+                }
                 int n;
-                const int x = ss_walk<false>(a.tab, lut, stage, L, g, e, &n, nop);
-                ent[g] = (uint8_t)e; ext[g] = (uint8_t)x; cnt[g] = (uint8_t)n;
-                changed = 1;
+                prev = ss_walk<false>(a.tab, lut, stage, L, g, e, &n, nop);
+                ent[g] = (uint8_t)e; ext[g] = (uint8_t)prev; cnt[g] = (uint8_t)n;
             }
         }
-        if (!__syncthreads_or(changed)) break;
-        if (all_entries && dbg_sweeps >= kSsMaxSweeps) { stuck = true; break; }
+        __syncthreads();
+        CGIC_STAMP3(3);
+        for (;;) {
+            ++dbg_sweeps;
+            int changed = 0;
+            for (int g = g0; g < g1; ++g) {
+                const int e = is_first(g) ? 0 : ext[g - 1];
+                if (e != ent[g]) {
+                    int n;
+                    const int x = ss_walk<false>(a.tab, lut, stage, L, g, e, &n, nop);
+                    ent[g] = (uint8_t)e; ext[g] = (uint8_t)x; cnt[g] = (uint8_t)n;
+                    changed = 1;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;
+            if (all_entries && dbg_sweeps >= kSsMaxSweeps) { stuck = true; break; }
+        }
     }
     if (stuck) {
         // ---- every entry offset at once; the chunks' entry -> exit functions composed by a scan
@@ -400,8 +475,8 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
         if (R == 1) {
             if (g0 < g1) {
                 const unsigned long long cw = e < 8 ? c_lo : c_hi;
-                ent[g0] = (uint8_t)(e == kMeEnd ? kSsEnd : (int)e);
-                cnt[g0] = e == kMeEnd ? (uint8_t)0 : (uint8_t)((cw >> (8 * (e & 7))) & 0xFFull);
+                e1 = e == kMeEnd ? kSsEnd : (int)e;
+                n1 = e == kMeEnd ? 0 : (int)((cw >> (8 * (e & 7))) & 0xFFull);
             }
         } else {
             int en = e == kMeEnd ? kSsEnd : (int)e;
@@ -417,6 +492,33 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
         __syncthreads();
     }
     CGIC_STAMP3(4);
+    // output positions: exclusive prefix of the counts over the chunks, restarted at every stream.  ONE barrier (round 7): every
+    // wave leaves its total, the lane that owns a stream's first chunk leaves where that chunk is (its wave, the count before it
+    // inside the wave), and behind the barrier every thread adds up the few wave totals it needs itself -- its own wave's base and
+    // the bases of streams 1 and 2.  (Before: a scan of the totals by wave 0 and a pass for the stream bases, three barriers.)
+    int mine = n1;
+    if (R != 1) for (int g = g0; g < g1; ++g) mine += cnt[g];
+    const int inc = (int)wave_inclusive_scan_u32((unsigned int)mine);        // (counts: DPP adds, no LDS-crossbar round trips)
+    if (lane == kWave - 1) s_scan[wave] = inc;
+    {
+        int r = inc - mine;
+        for (int g = g0; g < g1; ++g) {
+            if (g == L.c[1]) { s_at[0][0] = wave; s_at[0][1] = r; }
+            if (g == L.c[2]) { s_at[1][0] = wave; s_at[1][1] = r; }
+            r += R == 1 ? n1 : (int)cnt[g];
+        }
+    }
+    __syncthreads();
+    const int w1 = L.c[1] < C ? s_at[0][0] : nw, w2 = L.c[2] < C ? s_at[1][0] : nw;       // (a stream without chunks starts at the total)
+    int run = inc - mine, total = 0, base1 = L.c[1] < C ? s_at[0][1] : 0, base2 = L.c[2] < C ? s_at[1][1] : 0;
+    for (int k = 0; k < nw; ++k) {
+        const int t = s_scan[k];
+        run += k < wave ? t : 0;
+        base1 += k < w1 ? t : 0;
+        base2 += k < w2 ? t : 0;
+        total += t;
+    }
+    if (R == 1) dbg_sweeps = s_sweeps;              // (out of sweeps: kSsMaxSweeps walks + the all-entries pass, as the barrier loop counts)
     if (a.stats && tid == 0) {
         atomicAdd(&a.stats[0], (unsigned int)dbg_sweeps);
         atomicAdd(&a.stats[1], 1u);
@@ -425,50 +527,21 @@ __device__ __forceinline__ void decode_image_body(const DecodeArgs &a, const int
 #ifdef CGIC_PHASE_CLOCKS
     if (blk.x == 0 && tid == 0) g_phase_clk[9] = dbg_sweeps;
 #endif
-    // output positions: exclusive prefix of the counts over the chunks, restarted at every stream
-    int mine = 0;
-    for (int g = g0; g < g1; ++g) mine += cnt[g];
-    int inc = wave_inclusive_scan(mine);
-    if (lane == kWave - 1) s_scan[wave] = inc;
-    __syncthreads();
-    if (wave == 0) {
-        const int v = lane < nw ? s_scan[lane] : 0;
-        const int vi = wave_inclusive_scan(v);
-        if (lane < nw) s_scan[lane] = vi - v;
-        if (lane == nw - 1) s_scan[kDecWaves] = vi;
-    }
-    __syncthreads();
-    int run = s_scan[wave] + inc - mine;
-    const int total = s_scan[kDecWaves];
-    {
-        int r = run;
-        for (int g = g0; g < g1; ++g) {
-            if (g == L.c[1]) s_base[1] = r;
-            if (g == L.c[2]) s_base[2] = r;
-            r += cnt[g];
-        }
-        if (tid == 0) {
-            s_base[0] = 0; s_base[3] = total;
-            if (L.c[2] == C) s_base[2] = total;
-            if (L.c[1] == C) s_base[1] = total;
-        }
-    }
-    __syncthreads();
     CGIC_STAMP3(5);
     uint16_t *dst = a.dsym + b * (n_c + n_m + n_f);
     for (int g = g0; g < g1; ++g) {
         const int s = (g >= L.c[1]) + (g >= L.c[2]);
-        const int at = run - s_base[s];
+        const int at = run - sel3(s, 0, base1, base2);
         const int cap_s = sel3(s, cap[0], cap[1], cap[2]);
         uint16_t *dst_s = dst + sel3(s, 0, (int)n_c, (int)(n_c + n_m)) + at;
         int n;
-        ss_walk<true>(a.tab, lut, stage, L, g, (int)ent[g], &n,
+        ss_walk<true>(a.tab, lut, stage, L, g, R == 1 ? e1 : (int)ent[g], &n,
                       [&](int, int k, int sym) { if (at + k < cap_s) dst_s[k] = (uint16_t)sym; });
         run += n;
     }
     CGIC_STAMP3(6);
     if (tid < 3 && sel3(tid, nb[0], nb[1], nb[2]) > 0) {
-        const int n = s_base[tid + 1] - s_base[tid];
+        const int n = sel3(tid, base1, base2, total) - sel3(tid, 0, base1, base2);
         a.dcount[b * 3 + tid] = n > sel3(tid, cap[0], cap[1], cap[2]) ? -3 : n;
     }
 }
