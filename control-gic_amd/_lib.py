@@ -90,6 +90,11 @@ class RateTile(C.Structure):
                 ("off_c", _i64), ("off_m", _i64), ("off_f", _i64), ("off_e16", _i64), ("off_e8", _i64)]
 
 
+class EmaEntry(C.Structure):
+    """struct cgic_ema_entry (include/cgic_hip.h): one (shadow, param) tensor pair of cgic_ema_plan_create"""
+    _fields_ = [("shadow", _vp), ("param", _vp), ("n", _i64)]
+
+
 # name -> (restype, argtypes); every function include/cgic_hip.h declares
 PROTOTYPES = {
     "cgic_last_error": (C.c_char_p, []),
@@ -204,6 +209,11 @@ PROTOTYPES = {
     "cgic_container_workspace_bytes": (_sz, [_i64]),
     "cgic_container_pack": (_int, [C.POINTER(ContainerGroup), _int, C.POINTER(ContainerEntry), _i64, _vp, _i64, _vp, _vp, _vp]),
     "cgic_container_unpack": (_int, [_vp, _vp, _i64, C.POINTER(ContainerGroup), _int, C.POINTER(ContainerEntry), _i64, _vp, _vp]),
+    "cgic_ema_plan_create": (_int, [C.POINTER(EmaEntry), _int, C.POINTER(_vp)]),
+    "cgic_ema_plan_destroy": (None, [_vp]),
+    "cgic_ema_plan_info": (_int, [_vp, C.POINTER(_i64)]),
+    "cgic_ema_update": (_int, [_vp, _vp, _vp, _vp]),
+    "cgic_ema_copy": (_int, [_vp, _int, _vp, _vp]),
 }
 
 _lib = None

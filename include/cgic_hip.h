@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 21
+#define CGIC_ABI_VERSION 22
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -1115,6 +1115,55 @@ int cgic_container_pack(const cgic_container_group *groups, int G, const cgic_co
                         int64_t capacity, int64_t *total, void *workspace, cgic_stream_t stream);
 int cgic_container_unpack(const uint8_t *host_blob, const uint8_t *blob, int64_t bytes, const cgic_container_group *groups, int G,
                           const cgic_container_entry *entries, int64_t E, void *workspace, cgic_stream_t stream);
+
+/* LitEma (ABI 22): the exponential moving average of a model's parameters -- CGIC/models/ema.py:25-76, called five times after every
+ * optimiser step (CGIC/models/model.py:147-153) -- over ALL tensors of a module in one launch.  The reference runs
+ * shadow.sub_(one_minus_decay * (shadow - param)) per tensor (three launches, two temporaries) and reads num_updates on the host.
+ *
+ * A plan is built once from the list of tensor pairs and holds, in device memory, the work list of the launches: a table of entries
+ * (shadow, param, n, offset in a stash) and a table of chunks (entry, offset, length) -- a tensor is cut into chunks of a fixed
+ * number of elements (the last one shorter; a smaller tensor is one chunk; an empty one none) --, and one float, omd.
+ *
+ *   entries  host [n]: shadow, param device fp32 [n_i], 4-byte aligned (NULL allowed where n_i == 0), n_i >= 0.  The pairs must not
+ *            overlap one another (shadow == param of one pair is harmless)
+ * cgic_ema_plan_create checks every entry, computes the tables on the host and uploads them in one allocation on the current device,
+ * SYNCHRONOUSLY: not for use while a stream is capturing.  CGIC_ERR_INVALID: n < 0, entries NULL with n > 0, an n_i < 0, a NULL
+ * address with n_i > 0, an address that is not 4-byte aligned, more chunks than an int32 index can hold.  CGIC_ERR_NOMEM: no host memory for
+ * the tables; CGIC_ERR_HIP: the allocation or the upload failed.  cgic_ema_plan_destroy frees
+ * it (NULL: a no-op); the caller makes sure no launch that uses it is still in flight.
+ * cgic_ema_plan_info: out host int64 [8] = { entries, elements, chunks, elements of a full chunk, chunks whose shadow AND param are
+ * 16-byte aligned (they move 16 bytes per lane and access in the update and in direction 0; the others 4), workgroups of a launch,
+ * elements of the stash of cgic_ema_copy, chunks whose param is 16-byte aligned (the same for directions 1 and 2) }.
+ *
+ * cgic_ema_update: for every element  shadow = shadow - (omd * (shadow - param)), three separately rounded fp32 operations (no
+ * fused multiply-add), with omd computed on the device by a one-thread launch in front of it:
+ *   decay        device float [1]
+ *   num_updates  device int32 [1] or NULL.  If given and >= 0 it is incremented ONCE (by that one thread; wrapping like an int32
+ *                tensor) and decay' = cand < decay ? cand : decay with cand = (float)(1 + n) / (float)(10 + n) of the incremented n,
+ *                the additions wrapping in int32, the division in fp32 -- Python's min(self.decay, ...) of ema.py:30 (a NaN decay
+ *                stays NaN); otherwise decay' = decay.   omd = 1.0f - decay'
+ * Exactly two launches ordered by the stream (one when the plan has no chunk: the counter still moves), no allocation, no copy, no
+ * synchronisation, no atomics: it may be captured into a graph and replayed.  The plan's omd is written by every call: calls on ONE
+ * plan must be ordered by their streams (two streams may not run the same plan at once).
+ *
+ * cgic_ema_copy, bit for bit, one launch:   direction 0   param = shadow            (LitEma.copy_to)
+ *                                           direction 1   stash = param             (LitEma.store)
+ *                                           direction 2   param = stash             (LitEma.restore)
+ *   stash   device fp32 [info[6]], 16-byte aligned, for directions 1 and 2 (ignored for 0): ONE buffer for all tensors; tensor i lives
+ *           at the offset the plan gave it (the element counts before it, each rounded up to a multiple of 4).  Directions 1 and 2
+ *           never touch shadow.
+ * Every host argument is checked before anything is enqueued.  None of the five is available inside a launch group. */
+typedef struct cgic_ema_entry {
+    float *shadow;
+    float *param;
+    int64_t n;
+} cgic_ema_entry;
+typedef struct cgic_ema_plan cgic_ema_plan;
+int cgic_ema_plan_create(const cgic_ema_entry *entries, int n, cgic_ema_plan **out);
+void cgic_ema_plan_destroy(cgic_ema_plan *plan);
+int cgic_ema_plan_info(const cgic_ema_plan *plan, int64_t *out);
+int cgic_ema_update(const cgic_ema_plan *plan, const float *decay, int32_t *num_updates, cgic_stream_t stream);
+int cgic_ema_copy(const cgic_ema_plan *plan, int direction, float *stash, cgic_stream_t stream);
 
 #ifdef __cplusplus
 }
