@@ -1,7 +1,8 @@
 // cgic_norm_bwd_plan.h -- what one call of cgic_spatial_norm_train / cgic_spatial_norm_backward does, decided before anything is
 // enqueued: every check of the call, the unit, the layout of the partial sums in the workspace, the order in which they are added
 // and the three grids.  Plain C++17 like cgic_norm_plan.h (no HIP include, pointers are plain addresses): norm_bwd_plan() is a pure
-// function of a NormBwdCall (tests/host/norm_bwd_plan_main.cpp).
+// function of a NormBwdCall (tests/host/norm_bwd_plan_main.cpp); cgic_norm_bwd.hip launches what it says.  The rules that the forward's
+// plan has too -- zq's geometry, the unit, the table of the inputs -- are cgic_norm_plan.h's functions.
 //
 // The backward is three launches ordered by the stream; no workgroup waits for another and nothing is added atomically:
 //   reduce   grid (b, channel block, pixel tile).  A tile is `threads_reduce` units of `unit` consecutive pixels of a row; a thread
@@ -39,12 +40,9 @@ struct NormBwdCall {
     bool plain;                     // cgic_group_norm_backward: no zq, no conv_y / conv_b, none of their gradients (those fields are not looked at)
 };
 
-struct NormBwdPlan {
+struct NormBwdPlan : NormZqGeom {      // (the nearest index, as in NormPlan)
     int unit;                       // consecutive pixels of a row per thread and access: 8 (halves only), 4, 2 or 1
     int64_t span, spans;            // elements of a group; B * groups
-    int ymul, ydiv, xmul, xdiv;     // the nearest index, as in NormPlan
-    unsigned int mg_w, mg_y, mg_x;
-    bool zq_vec;
     int chan_block;                 // channels per reduce workgroup
     int64_t chan_blocks;            // ceil(C / chan_block)
     int threads_reduce;             // 64, 128 or 256
@@ -62,27 +60,23 @@ struct NormBwdPlan {
     char why_text[224];
 };
 
-// the part that the shape alone decides: the checks of (dtype, B, C, H, W, groups), the channel block and the workspace
-// (cgic_spatial_norm_backward_workspace_bytes is this function; with `plain`, cgic_group_norm_backward_workspace_bytes: two sums
-// per channel and tile instead of twelve, no dz partials)
-inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t groups, NormBwdPlan *p, const char **why,
-                          bool plain = false)
+// the part that the shape alone decides: the checks of (dtype, B, C, H, W, groups) -- the forward's under the forward's name `nm`,
+// the others under <nm>_backward --, the channel block and the workspace (cgic_spatial_norm_backward_workspace_bytes is this
+// function; with `plain`, cgic_group_norm_backward_workspace_bytes: two sums per channel and tile instead of twelve, no dz partials)
+inline int norm_bwd_shape(const char *nm, bool plain, int in_dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t groups, NormBwdPlan *p,
+                          const char **why)
 {
     *p = NormBwdPlan{};
-    const auto refuse = [&](int code) {
-        if (plain) norm_as_group(p->why_text);
-        *why = p->why_text;
-        return code;
-    };
+    const auto refuse = [&](int code) { *why = p->why_text; return code; };
     NormPlan fwd;
     const char *fwd_why = "";
-    const int rc = norm_form(in_dtype, B, C, H, W, groups, &fwd, &fwd_why);
+    const int rc = norm_form(nm, in_dtype, B, C, H, W, groups, &fwd, &fwd_why);
     if (rc != CGIC_OK) {
         snprintf(p->why_text, sizeof(p->why_text), "%s", fwd_why);
         return refuse(rc);
     }
     if (B == 0) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: an empty batch");
+        snprintf(p->why_text, sizeof(p->why_text), "%s_backward: an empty batch", nm);
         return refuse(CGIC_ERR_INVALID);
     }
     p->span = fwd.span;
@@ -94,8 +88,8 @@ inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t
     p->chan_blocks = (C + cb - 1) / cb;
     p->tiles_max = (plane + kNormBwdThreads - 1) / kNormBwdThreads;
     if (B * p->chan_blocks * p->tiles_max >= ((int64_t)1 << 31) || B * C * kNormBwdSums >= ((int64_t)1 << 31)) {
-        snprintf(p->why_text, sizeof(p->why_text), "spatial_norm_backward: [%lld,%lld,%lld,%lld] is beyond a grid of 2^31 workgroups",
-                 (long long)B, (long long)C, (long long)H, (long long)W);
+        snprintf(p->why_text, sizeof(p->why_text), "%s_backward: [%lld,%lld,%lld,%lld] is beyond a grid of 2^31 workgroups", nm, (long long)B,
+                 (long long)C, (long long)H, (long long)W);
         return refuse(CGIC_ERR_UNSUPPORTED);
     }
     p->sums = plain ? 2 : kNormBwdSums;
@@ -106,20 +100,10 @@ inline int norm_bwd_shape(int in_dtype, int64_t B, int64_t C, int64_t H, int64_t
     return CGIC_OK;
 }
 
-struct NormRegion {
-    uintptr_t addr;
-    int64_t bytes;
-    int align;
-};
-inline bool norm_regions_overlap(const NormRegion &a, const NormRegion &b)
-{
-    return a.addr && b.addr && a.addr < b.addr + (uintptr_t)b.bytes && b.addr < a.addr + (uintptr_t)a.bytes;
-}
-
 // CGIC_OK and the plan, or the error code of the call and *why
 inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
 {
-    const int rc = norm_bwd_shape(c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why, c.plain);
+    int rc = norm_bwd_shape(norm_name(c.plain), c.plain, c.in_dtype, c.B, c.C, c.H, c.W, c.groups, p, why);
     if (rc != CGIC_OK) return rc;
     const char *nm = c.plain ? "group_norm_backward" : "spatial_norm_backward";
     const auto refuse = [&](int code) { *why = p->why_text; return code; };
@@ -131,36 +115,25 @@ inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
                      i ? "df_dtype" : "go_dtype", both[i], c.in_dtype);
             return refuse(both[i] == CGIC_DT_F16 || both[i] == CGIC_DT_BF16 ? CGIC_ERR_UNSUPPORTED : CGIC_ERR_INVALID);
         }
-    // ---- zq's grid
-    p->ymul = p->ydiv = p->xmul = p->xdiv = 1;     // (what the plain call, which has no zq, keeps)
-    if (!c.plain && (c.hq <= 0 || c.wq <= 0)) {
-        snprintf(p->why_text, sizeof(p->why_text), "%s: zq grid %lldx%lld", nm, (long long)c.hq, (long long)c.wq);
+    // ---- zq's grid, and dzq's threads in finish
+    rc = norm_zq_geom(c.H, c.W, c.hq, c.wq, c.zq, c.plain, p);
+    if (rc == CGIC_OK && !c.plain && c.B * kNormZq * c.hq * c.wq >= ((int64_t)1 << 38)) rc = CGIC_ERR_UNSUPPORTED;
+    if (rc != CGIC_OK) return refuse(norm_zq_refusal(p->why_text, nm, rc, c.H, c.W, c.hq, c.wq));
+    // ---- the pointers: every input, the outputs that are wanted
+    const int gb = norm_dtype_bytes(c.go_dtype), db = norm_dtype_bytes(c.df_dtype);
+    const int64_t numel = c.B * c.C * c.H * c.W, nzq = c.plain ? 0 : c.B * kNormZq * c.hq * c.wq, vec = c.C * 4, mat = c.C * kNormZq * 4;
+    const int kIn = kNormIn + 2, kOut = 8;
+    NormRegion in[kNormIn];
+    const bool all = norm_inputs(c, in);
+    const auto mod = [&](uintptr_t a) { return c.plain ? (uintptr_t)0 : a; };      // (the plain call has no zq and no conv parameters: none of their gradients)
+    const NormRegion r[kIn + kOut] = {
+        in[0], {c.go, numel * gb, gb}, in[1], {c.stats, p->spans * 8, 4}, in[2], in[3], in[4], in[5], in[6], in[7],
+        {c.df, numel * db, db}, {mod(c.dzq), nzq * 4, 4}, {c.dgn_weight, vec, 4}, {c.dgn_bias, vec, 4}, {mod(c.dwy), mat, 4},
+        {mod(c.dby), vec, 4}, {mod(c.dwb), mat, 4}, {mod(c.dbb), vec, 4}};
+    if (!all || !c.go || !c.stats) {
+        snprintf(p->why_text, sizeof(p->why_text), "%s: NULL input", nm);
         return refuse(CGIC_ERR_INVALID);
     }
-    if (!c.plain && (c.hq > (1 << 20) || c.wq > (1 << 20) || c.hq * c.wq >= ((int64_t)1 << 31) || c.B * kNormZq * c.hq * c.wq >= ((int64_t)1 << 38) ||
-        !norm_ratio(c.H, c.hq, &p->ymul, &p->ydiv) || !norm_ratio(c.W, c.wq, &p->xmul, &p->xdiv))) {
-        snprintf(p->why_text, sizeof(p->why_text), "%s: zq %lldx%lld under features %lldx%lld (each axis an integer ratio, up or down)", nm,
-                 (long long)c.hq, (long long)c.wq, (long long)c.H, (long long)c.W);
-        return refuse(CGIC_ERR_UNSUPPORTED);
-    }
-    // ---- the pointers: every input, the outputs that are wanted
-    const int ib = norm_dtype_bytes(c.in_dtype), gb = norm_dtype_bytes(c.go_dtype), db = norm_dtype_bytes(c.df_dtype);
-    const int64_t numel = c.B * c.C * c.H * c.W, nzq = c.plain ? 0 : c.B * kNormZq * c.hq * c.wq;
-    const int kIn = 10, kOut = 8;
-    NormRegion r[kIn + kOut] = {
-        {c.f, numel * ib, ib}, {c.go, numel * gb, gb}, {c.zq, nzq * 4, 4}, {c.stats, p->spans * 8, 4}, {c.gn_weight, c.C * 4, 4},
-        {c.gn_bias, c.C * 4, 4}, {c.wy, c.C * kNormZq * 4, 4}, {c.by, c.C * 4, 4}, {c.wb, c.C * kNormZq * 4, 4}, {c.bb, c.C * 4, 4},
-        {c.df, numel * db, db}, {c.dzq, nzq * 4, 4}, {c.dgn_weight, c.C * 4, 4}, {c.dgn_bias, c.C * 4, 4}, {c.dwy, c.C * kNormZq * 4, 4},
-        {c.dby, c.C * 4, 4}, {c.dwb, c.C * kNormZq * 4, 4}, {c.dbb, c.C * 4, 4}};
-    // the plain call: zq, the conv parameters and their gradients do not exist (address 0 overlaps nothing and is aligned)
-    const auto absent = [&](int i) { return c.plain && (i == 2 || (i >= 6 && i < kIn) || i == kIn + 1 || i >= kIn + 4); };
-    for (int i = 0; i < kIn + kOut; ++i)
-        if (absent(i)) r[i].addr = 0;
-    for (int i = 0; i < kIn; ++i)
-        if (!r[i].addr && !absent(i)) {
-            snprintf(p->why_text, sizeof(p->why_text), "%s: NULL input", nm);
-            return refuse(CGIC_ERR_INVALID);
-        }
     bool any = false;
     for (int i = kIn; i < kIn + kOut; ++i) any = any || r[i].addr;
     if (!any) {
@@ -199,22 +172,9 @@ inline int norm_bwd_plan(const NormBwdCall &c, NormBwdPlan *p, const char **why)
             snprintf(p->why_text, sizeof(p->why_text), "%s: the workspace overlaps a tensor of the call", nm);
             return refuse(CGIC_ERR_INVALID);
         }
-    // ---- the unit: 16 bytes of the feature type where the row width and the pointers of f, go and df allow, else fewer
-    int unit = 1;
-    for (int u = 16 / ib; u > 1; u >>= 1) {
-        const int gbytes = u * gb > 16 ? 16 : u * gb, dbytes = u * db > 16 ? 16 : u * db;
-        if (c.W % u == 0 && c.f % (uintptr_t)(u * ib) == 0 && c.go % (uintptr_t)gbytes == 0 && (!c.df || c.df % (uintptr_t)dbytes == 0)) {
-            unit = u;
-            break;
-        }
-    }
-    p->unit = unit;
-    p->mg_w = norm_magic(c.H * c.W, c.W);
-    p->mg_y = c.plain ? 0u : norm_magic(c.H > c.hq ? c.H : c.hq, p->ydiv);
-    p->mg_x = c.plain ? 0u : norm_magic(c.W > c.wq ? c.W : c.wq, p->xdiv);
-    p->zq_vec = !c.plain && p->xmul == 1 && p->xdiv == 1 && c.zq % 16 == 0;
+    p->unit = norm_unit(c.W, {r[0], r[1], r[kIn]});           // f, go and df
     // ---- the grids
-    const int64_t plane_units = c.H * c.W / unit;
+    const int64_t plane_units = c.H * c.W / p->unit;
     p->threads_reduce = plane_units <= 64 ? 64 : plane_units <= 128 ? 128 : kNormBwdThreads;
     p->tiles = (plane_units + p->threads_reduce - 1) / p->threads_reduce;       // (<= tiles_max: at most ceil(H * W / 256), or 1)
     p->grid_reduce = c.B * p->chan_blocks * p->tiles;
@@ -238,19 +198,18 @@ inline int norm_train_plan(const NormCall &c, uintptr_t stats, NormPlan *p, cons
     const int rc = norm_plan(c, p, why);
     if (rc != CGIC_OK || p->form == 0) return rc;
     const char *nm = c.plain ? "group_norm_train" : "spatial_norm_train";
-    const auto gone = [&](uintptr_t a) { return c.plain ? (uintptr_t)0 : a; };      // (the plain call has no zq and no conv parameters)
     const auto refuse = [&](int code) { *why = p->why_text; return code; };
     if (!stats || stats % 4) {
         snprintf(p->why_text, sizeof(p->why_text), "%s: stats is %s", nm, stats ? "not aligned to its 4-byte element" : "NULL");
         return refuse(CGIC_ERR_INVALID);
     }
-    const int ib = norm_dtype_bytes(c.in_dtype), ob = norm_dtype_bytes(c.out_dtype);
-    const int64_t numel = c.B * c.C * c.H * c.W;
+    const int ob = norm_dtype_bytes(c.out_dtype);
     const NormRegion st = {stats, p->spans * 8, 4};
-    const NormRegion r[10] = {{c.f, numel * ib, ib}, {gone(c.zq), c.B * kNormZq * c.hq * c.wq * 4, 4}, {c.gn_weight, c.C * 4, 4}, {c.gn_bias, c.C * 4, 4},
-                              {gone(c.wy), c.C * kNormZq * 4, 4}, {gone(c.by), c.C * 4, 4}, {gone(c.wb), c.C * kNormZq * 4, 4},
-                              {gone(c.bb), c.C * 4, 4}, {c.out, numel * ob, ob}, {p->workspace_needed ? c.workspace : 0, (int64_t)p->workspace_needed, 8}};
-    for (int i = 0; i < 10; ++i)
+    NormRegion r[kNormIn + 2];
+    norm_inputs(c, r);
+    r[kNormIn] = {c.out, c.B * c.C * c.H * c.W * ob, ob};
+    r[kNormIn + 1] = {p->workspace_needed ? c.workspace : 0, (int64_t)p->workspace_needed, 8};
+    for (int i = 0; i < kNormIn + 2; ++i)
         if (norm_regions_overlap(st, r[i])) {
             snprintf(p->why_text, sizeof(p->why_text), "%s: stats overlaps another tensor of the call", nm);
             return refuse(CGIC_ERR_INVALID);

@@ -1,4 +1,4 @@
-"""The decoder's SpatialNorm (CGIC/modules/vqvae/decoder.py:34-53) on the library's kernel (csrc/cgic_norm.hip):
+"""The decoder's SpatialNorm (CGIC/modules/vqvae/decoder.py:34-53) on the library's kernels (csrc/cgic_norm.hip, the backward: csrc/cgic_norm_bwd.hip):
 
     zq    = interpolate(zq, size=f.shape[-2:], mode="nearest")
     new_f = GroupNorm(32, eps=1e-6, affine)(f) * conv_y(zq) + conv_b(zq)            # conv_y, conv_b: 1x1, 4 -> C
@@ -166,7 +166,7 @@ def group_norm_backward_workspace_bytes(dtype, B, C, H, W, groups=32):
 
 def spatial_norm_backward(go, f, zq, stats, gn_weight, gn_bias, wy, by, wb, bb, groups=32, swish=False, need=GRADS, df_dtype=None, outs=None,
                           workspace=None):
-    """the gradients of spatial_norm_train's `out` (csrc/cgic_norm.hip: reduce, finish, apply -- three launches, every sum in
+    """the gradients of spatial_norm_train's `out` (csrc/cgic_norm_bwd.hip: reduce, finish, apply -- three launches, every sum in
     float64 in a fixed order, no atomics: repeated calls are bit-identical and an image's df and dzq do not depend on its batch).
     go [B,C,H,W]: the gradient of `out`, fp32 or f's half type; f, zq, the parameters, groups, swish: the forward's; stats: its
     second result.  need: the gradients that are wanted, names out of GRADS -- the others are neither computed nor stored.
@@ -260,28 +260,34 @@ def _(f, zq, gn_weight, gn_bias, wy, by, wb, bb, groups, eps, swish, half_out):
     return f.new_empty(f.shape, dtype=f.dtype if half_out else torch.float32), f.new_empty((f.shape[0] * groups, 2), dtype=torch.float32)
 
 
-def _train_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:8], output[1])
-    ctx.groups, ctx.swish = inputs[8], inputs[10]
+def _register_train_autograd(op, grads, backward, name, module):
+    """the autograd formula of a *_train op whose first len(grads) inputs are the tensors (f first), followed by groups, eps, swish,
+    half_out: the gradient of `out` through `backward` (spatial_norm_backward / group_norm_backward) for the inputs that need one"""
+    n = len(grads)
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:n], output[1])
+        ctx.groups, ctx.swish = inputs[n], inputs[n + 2]
+
+    def bwd(ctx, g_out, _g_stats):
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"cgic::{name}_train is once-differentiable: its backward (cgic_{name}_backward) has no autograd formula, "
+                               f"so a backward under create_graph=True (a double backward) is not available; {module}.backward_kernel = False "
+                               "takes torch's expression, which can be differentiated twice")
+        *inputs, stats = ctx.saved_tensors
+        need = tuple(g for g, want in zip(grads, ctx.needs_input_grad[:n]) if want)
+        if g_out is None or not need:
+            return (None,) * (n + 4)
+        f = inputs[0]
+        if g_out.dtype != torch.float32 and g_out.dtype != f.dtype:
+            g_out = g_out.float()
+        res = backward(g_out, stats=stats, **dict(zip(grads, inputs)), groups=ctx.groups, swish=ctx.swish, need=need)     # (the names are its parameters')
+        return (*(None if g is None else g.to(t.dtype) for g, t in zip(res, inputs)), None, None, None, None)
+
+    op.register_autograd(bwd, setup_context=setup)
 
 
-def _train_bwd(ctx, g_out, _g_stats):
-    if torch.is_grad_enabled():
-        raise RuntimeError("cgic::spatial_norm_train is once-differentiable: its backward (cgic_spatial_norm_backward) has no autograd formula, "
-                           "so a backward under create_graph=True (a double backward) is not available; SpatialNorm.backward_kernel = False "
-                           "takes torch's expression, which can be differentiated twice")
-    *inputs, stats = ctx.saved_tensors
-    need = tuple(n for n, want in zip(GRADS, ctx.needs_input_grad[:8]) if want)
-    if g_out is None or not need:
-        return (None,) * 12
-    f = inputs[0]
-    if g_out.dtype != torch.float32 and g_out.dtype != f.dtype:
-        g_out = g_out.float()
-    grads = spatial_norm_backward(g_out, f, inputs[1], stats, *inputs[2:], groups=ctx.groups, swish=ctx.swish, need=need)
-    return (*(None if g is None else g.to(t.dtype) for g, t in zip(grads, inputs)), None, None, None, None)
-
-
-spatial_norm_train_op.register_autograd(_train_bwd, setup_context=_train_setup)
+_register_train_autograd(spatial_norm_train_op, GRADS, spatial_norm_backward, "spatial_norm", "SpatialNorm")
 
 
 @torch.library.custom_op("cgic::group_norm", mutates_args=(), device_types="cuda")
@@ -310,28 +316,7 @@ def _(f, gn_weight, gn_bias, groups, eps, swish, half_out):
     return f.new_empty(f.shape, dtype=f.dtype if half_out else torch.float32), f.new_empty((f.shape[0] * groups, 2), dtype=torch.float32)
 
 
-def _gn_train_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:3], output[1])
-    ctx.groups, ctx.swish = inputs[3], inputs[5]
-
-
-def _gn_train_bwd(ctx, g_out, _g_stats):
-    if torch.is_grad_enabled():
-        raise RuntimeError("cgic::group_norm_train is once-differentiable: its backward (cgic_group_norm_backward) has no autograd formula, "
-                           "so a backward under create_graph=True (a double backward) is not available; GroupNorm.backward_kernel = False "
-                           "takes torch's expression, which can be differentiated twice")
-    *inputs, stats = ctx.saved_tensors
-    need = tuple(n for n, want in zip(GN_GRADS, ctx.needs_input_grad[:3]) if want)
-    if g_out is None or not need:
-        return (None,) * 7
-    f = inputs[0]
-    if g_out.dtype != torch.float32 and g_out.dtype != f.dtype:
-        g_out = g_out.float()
-    grads = group_norm_backward(g_out, f, stats, *inputs[1:], groups=ctx.groups, swish=ctx.swish, need=need)
-    return (*(None if g is None else g.to(t.dtype) for g, t in zip(grads, inputs)), None, None, None, None)
-
-
-group_norm_train_op.register_autograd(_gn_train_bwd, setup_context=_gn_train_setup)
+_register_train_autograd(group_norm_train_op, GN_GRADS, group_norm_backward, "group_norm", "GroupNorm")
 
 
 def one_launch(dtype, B, C, H, W, groups=32):

@@ -1,4 +1,4 @@
-"""GPU: the plain GroupNorm for training (csrc/cgic_norm.hip, ABI 21) -- group_norm_train and group_norm_backward -- against float64
+"""GPU: the plain GroupNorm for training (csrc/cgic_norm.hip, csrc/cgic_norm_bwd.hip, ABI 21) -- group_norm_train and group_norm_backward -- against float64
 autograd of GroupNorm (+ swish) on the CPU (tests/group_norm_ref.py).
 
 The bar is tests/test_spatial_norm_bwd.py's.  Per gradient tensor (f, gn_weight, gn_bias): g64 = the float64 gradient from the
@@ -32,17 +32,21 @@ def dev(x):
 _cache = {}
 
 
+def inputs(shape, B, dtype):
+    """(inputs on the CPU, go): drawn once, shared, never changed.  go holds values of `dtype`, as fp32"""
+    base = (shape, B, dtype)
+    if base not in _cache:
+        C, H, W = shape
+        rng = np.random.default_rng(4000 + C + 7 * H + W)
+        _cache[base] = (ref.make_inputs(rng, B, C, H, W, dtype), bref.make_go(rng, (B, C, H, W), dtype).float())
+    return _cache[base]
+
+
 def reference(shape, B, dtype, swish):
-    """(inputs on the CPU, go, {gradient: float64}, {gradient: E_ref}): computed once, shared, never changed.  go holds values of
-    `dtype`, as fp32"""
+    """(inputs on the CPU, go, {gradient: float64}, {gradient: E_ref}): computed once, shared, never changed"""
     key = (shape, B, dtype, swish)
     if key not in _cache:
-        C, H, W = shape
-        base = (shape, B, dtype)
-        if base not in _cache:
-            rng = np.random.default_rng(4000 + C + 7 * H + W)
-            _cache[base] = (ref.make_inputs(rng, B, C, H, W, dtype), bref.make_go(rng, (B, C, H, W), dtype).float())
-        x, go = _cache[base]
+        x, go = inputs(shape, B, dtype)
         _cache[key] = (x, go, *ref.reference_grads(x, go, swish))
     return _cache[key]
 
@@ -84,6 +88,33 @@ def test_every_type_pair_and_swish_against_the_bar(shape, B):
             if dt != f32:
                 half = backward(xd, god, stats, swish=swish, need=("f",))["f"]
                 assert half.dtype == dt and torch.equal(half, got["f"].to(dt))
+
+
+@pytest.mark.parametrize("B", [1, 4])
+@pytest.mark.parametrize("shape, zq_grid, dtype", [((32, 3, 5), (3, 5), f32), ((64, 6, 10), (6, 10), f32), ((32, 34, 68), (17, 17), f32),
+                                                   ((512, 16, 16), (16, 16), f16)], ids=["unit1", "unit2", "unit4-zq-up", "unit8-f16"])
+def test_the_bits_of_the_modulated_kernels_at_conv_y_1_and_conv_b_0(shape, zq_grid, dtype, B):
+    """what csrc/cgic_norm_bwd.hip promises of its two instantiations: on finite inputs group_norm_train + group_norm_backward give
+    the bits of spatial_norm_train + spatial_norm_backward with wy = wb = 0, by = 1, bb = 0 on any finite zq (n * 1 + 0 and gv * 1 are
+    exact) -- out, stats, df (fp32), dgn_weight and dgn_bias, at every unit, in both forms of the forward, with and without swish.
+    go has the features' type"""
+    C, H, W = shape
+    assert norm.one_launch(dtype, B, C, H, W) == (B == 4)
+    x, go = inputs(shape, B, dtype)
+    xd, god = dev(x), go.to(DEV).to(dtype)
+    zq = ref.make_zq(np.random.default_rng(4100 + C), B, *zq_grid).to(DEV)
+    assert bool(torch.isfinite(zq).all())
+    conv = (torch.zeros(C, 4, device=DEV), torch.ones(C, device=DEV), torch.zeros(C, 4, device=DEV), torch.zeros(C, device=DEV))    # wy, by, wb, bb
+    for swish in (False, True):
+        out, stats = train(xd, swish=swish)
+        mout, mstats = norm.spatial_norm_train(xd["f"], zq, xd["gn_w"], xd["gn_b"], *conv, swish=swish)
+        assert torch.equal(out, mout) and torch.equal(stats, mstats), (shape, B, swish)
+        got = backward(xd, god, stats, swish=swish, df_dtype=f32)
+        mod = dict(zip(norm.GRADS, norm.spatial_norm_backward(god, xd["f"], zq, mstats, xd["gn_w"], xd["gn_b"], *conv, swish=swish,
+                                                              need=("f", "gn_weight", "gn_bias"), df_dtype=f32)))
+        for k in ref.GRADS:
+            assert got[k].dtype == f32 and torch.equal(got[k], mod[NAMES[k]]), (shape, B, swish, k)
+        assert all(mod[k] is None for k in norm.GRADS if k not in norm.GN_GRADS)
 
 
 @pytest.mark.parametrize("dtype", [f32, f16])

@@ -1,4 +1,4 @@
-"""The plain GroupNorm of csrc/cgic_norm.hip (ABI 21) without a GPU.
+"""The plain GroupNorm of csrc/cgic_norm.hip and csrc/cgic_norm_bwd.hip (ABI 21) without a GPU.
 
 The plans.  cgic_group_norm / _train / _backward are the plans of csrc/cgic_norm_plan.h and cgic_norm_bwd_plan.h with their `plain`
 flag set.  tests/host/group_norm_plan_main.cpp is compiled with the host compiler alone -- once plainly, once with

@@ -1,4 +1,4 @@
-"""GPU: SpatialNorm for training (csrc/cgic_norm.hip, ABI 19) -- the forward that keeps the statistics and the backward -- against
+"""GPU: SpatialNorm for training (csrc/cgic_norm.hip, csrc/cgic_norm_bwd.hip, ABI 19) -- the forward that keeps the statistics and the backward -- against
 float64 autograd of the layer on the CPU (tests/spatial_norm_bwd_ref.py, which tests/test_spatial_norm_bwd_host.py holds to the real
 class's gradients).
 

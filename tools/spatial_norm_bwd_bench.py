@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time forward + backward of SpatialNorm on the library's training kernels (SpatialNorm.backward_kernel = True: csrc/cgic_norm.hip,
+"""Time forward + backward of SpatialNorm on the library's training kernels (SpatialNorm.backward_kernel = True: csrc/cgic_norm.hip, csrc/cgic_norm_bwd.hip,
 forward with statistics, then reduce / finish / apply) against the module's torch path, at the decoder's shapes.
 
     python tools/spatial_norm_bwd_bench.py [--B 8 1] [--calls 10] [--rounds 7] [--limit 300] [--only SUBSTRING]
