@@ -13,7 +13,7 @@ from .entropy import Entropy, entropy_maps, entropy_maps_u8, entropy_maps_tiles
 from .indices_coding import HuffmanCoding
 from .mask_coding import BinaryCoding
 from .codec import GrainCodec, CompressedBatch, mode_streams, STREAM_NAMES, decoder_mode
-from . import pipeline, highres, container, draw, ema, model, norm, resblock, ops, experimental
+from . import pipeline, highres, container, draw, ema, adam, model, norm, resblock, ops, experimental
 from .pipeline import HotPathPipeline, LaneStream, GraphLanes, capture_graph
 from .model import install, compress_batch, grain_merge, avg_pool, decoder_blend_medium, decoder_blend_fine
 from . import rate
@@ -22,6 +22,7 @@ from .norm import GroupNorm, group_norm, group_norm_backward, group_norm_train
 from .resblock import ResnetBlock
 from .attention import AttnBlock, attention, attention_backward
 from .ema import LitEma, EmaPlan
+from .adam import Adam, AdamPlan
 from .rate import RateTable, rate_table, grain_indices, gather_grain_indices, choose, default_candidates, compress_to_bpp
 from .rate import RateCurve, rate_curve, ratio_for_rank, router_ranks
 from .rate import BppRoute, budget_bytes, route_to_bpp
@@ -34,4 +35,4 @@ __all__ = ["VectorQuantize2", "VectorQuantizer", "TripleGrainFixedEntropyRouter"
            "HotPathPipeline", "LaneStream", "GraphLanes", "capture_graph", "decoder_mode", "install", "compress_batch", "grain_merge", "avg_pool", "decoder_blend_medium", "decoder_blend_fine", "rate", "RateTable", "rate_table", "grain_indices", "gather_grain_indices", "choose",
            "default_candidates", "compress_to_bpp", "RateCurve", "rate_curve", "ratio_for_rank", "router_ranks",
            "BppRoute", "budget_bytes", "route_to_bpp",
-           "TiledRateCurve", "rate_curve_tiled", "tiled_settings", "compress_tiled_to_bpp", "to_frames", "paste_tiles", "partition_tiles", "partition_map", "grain_map", "draw_triple_grain_256res", "draw", "highres", "container", "norm", "SpatialNorm", "spatial_norm", "spatial_norm_train", "spatial_norm_backward", "GroupNorm", "group_norm", "group_norm_train", "group_norm_backward", "resblock", "ResnetBlock", "AttnBlock", "attention", "attention_backward", "ema", "LitEma", "EmaPlan", "CgicError", "LIB_PATH"]
+           "TiledRateCurve", "rate_curve_tiled", "tiled_settings", "compress_tiled_to_bpp", "to_frames", "paste_tiles", "partition_tiles", "partition_map", "grain_map", "draw_triple_grain_256res", "draw", "highres", "container", "norm", "SpatialNorm", "spatial_norm", "spatial_norm_train", "spatial_norm_backward", "GroupNorm", "group_norm", "group_norm_train", "group_norm_backward", "resblock", "ResnetBlock", "AttnBlock", "attention", "attention_backward", "ema", "LitEma", "EmaPlan", "adam", "Adam", "AdamPlan", "CgicError", "LIB_PATH"]

@@ -95,6 +95,22 @@ class EmaEntry(C.Structure):
     _fields_ = [("shadow", _vp), ("param", _vp), ("n", _i64)]
 
 
+class AdamEntry(C.Structure):
+    """struct cgic_adam_entry (include/cgic_hip.h): one parameter of cgic_adam_plan_create with its optimiser state and shadow"""
+    _fields_ = [("param", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("shadow", _vp), ("n", _i64), ("ema_group", _i32), ("reserved", _i32)]
+
+
+class AdamEmaGroup(C.Structure):
+    """struct cgic_adam_ema_group (include/cgic_hip.h): the decay and num_updates buffers of one LitEma"""
+    _fields_ = [("decay", _vp), ("num_updates", _vp)]
+
+
+class AdamHyper(C.Structure):
+    """struct cgic_adam_hyper (include/cgic_hip.h): the hyperparameters of one cgic_adam_step, by value"""
+    _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64), ("clip_value", _f64), ("clip", _i32),
+                ("reserved", _i32), ("lr_dev", _vp)]
+
+
 # name -> (restype, argtypes); every function include/cgic_hip.h declares
 PROTOTYPES = {
     "cgic_last_error": (C.c_char_p, []),
@@ -214,6 +230,10 @@ PROTOTYPES = {
     "cgic_ema_plan_info": (_int, [_vp, C.POINTER(_i64)]),
     "cgic_ema_update": (_int, [_vp, _vp, _vp, _vp]),
     "cgic_ema_copy": (_int, [_vp, _int, _vp, _vp]),
+    "cgic_adam_plan_create": (_int, [C.POINTER(AdamEntry), _int, C.POINTER(AdamEmaGroup), _int, _vp, C.POINTER(_vp)]),
+    "cgic_adam_plan_destroy": (None, [_vp]),
+    "cgic_adam_plan_info": (_int, [_vp, C.POINTER(_i64)]),
+    "cgic_adam_step": (_int, [_vp, _vp, C.POINTER(AdamHyper), _vp]),
 }
 
 _lib = None

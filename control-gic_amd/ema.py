@@ -230,6 +230,7 @@ class LitEma(nn.Module):
         self._plan = None                   # the EmaPlan of forward / copy_to
         self._store_plan = None             # the EmaPlan of store / restore: this module's own, kept while the parameters stay put
         self._stash = None                  # (plan, flat buffer, indices in the parameter list) of the last store
+        self._fused_pending = None          # set by a cg.Adam this module is attached to: the ids of the parameters whose shadows its step updated
 
     @classmethod
     def adopt(cls, ema):
@@ -249,7 +250,7 @@ class LitEma(nn.Module):
 
     def __getstate__(self):
         d = self.__dict__.copy()            # (a plan is a handle of the library: a copy of the module builds its own)
-        d["_plan"] = d["_store_plan"] = d["_stash"] = None
+        d["_plan"] = d["_store_plan"] = d["_stash"] = d["_fused_pending"] = None
         return d
 
     # ---- the pairs of a model
@@ -287,8 +288,34 @@ class LitEma(nn.Module):
             self._plan = EmaPlan([t.detach() for t in ks], [t.detach() for t in kp])
         return self._plan
 
+    def _forward_behind_a_fused_step(self, model, rode):
+        """the forward that follows a step of a cg.Adam this module is attached to (adam.py: attach_ema): the pairs of the parameters
+        in `rode` were updated inside that step, which also moved num_updates.  What is left -- parameters of another optimiser, or on
+        torch's path there -- gets torch's expression on the decay of the SAME step, computed from the counter as the step left it"""
+        left = []
+        for key, p in model.named_parameters():
+            if not p.requires_grad:
+                if key in self.m_name2s_name:
+                    raise AssertionError(f"LitEma: {key} has a shadow but no longer requires a gradient")
+                continue
+            if id(p) not in rode:
+                left.append((self._buffers[self.m_name2s_name[key]], p))
+        if not left:
+            return
+        n = self.num_updates
+        counted = n >= 0
+        cand = (1 + n) / (10 + n)
+        omd = 1.0 - torch.where(counted & (cand < self.decay), cand, self.decay)
+        for s, p in left:
+            s = s if s.dtype == p.dtype and s.device == p.device else s.type_as(p)
+            s.sub_((s - p) * omd)
+
     def forward(self, model):
         with torch.no_grad():
+            rode = getattr(self, "_fused_pending", None)
+            if rode is not None:
+                self._fused_pending = None
+                return self._forward_behind_a_fused_step(model, rode)
             ks, kp, rest = self._pairs(model, need_scalars=True)
             if rest or not ks:
                 # torch's expression for these, on the decay of THIS call: taken before the kernel moves the counter

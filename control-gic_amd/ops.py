@@ -20,6 +20,7 @@ functions the module classes use (each entry point of libcgic_hip.so is bound on
     h_     = torch.ops.cgic.attention(q, k, v, int(C) ** -0.5, False)                            # AttnBlock's softmax(q^T k) v without the [B,N,N] matrix; defined in attention.py, next to its module
     h_, lse = torch.ops.cgic.attention_train(q, k, v, int(C) ** -0.5)                             # the same, differentiable: its backward is csrc/cgic_attn_bwd.hip, no [B,N,N] matrix there either
     torch.ops.cgic.ema_update(shadows, params, decay, num_updates)                                # LitEma.forward over all tensors in one launch (ema.py:25-44), in place; defined in ema.py, next to its module
+    torch.ops.cgic.adam_step(params, grads, m, v, steps, lr, b1, b2, eps, wd, clip, None, shadows, decay, num_updates)   # clip by value + Adam's step + LitEma over all tensors in one pass, in place; defined in adam.py, next to its class
 
 A code table travels through an op as an integer: the `cgic_table*` handle of include/cgic_hip.h (ops take tensors and
 scalars; the table is host-side state of the library, built once per frequency table).
@@ -31,6 +32,7 @@ import torch
 
 from . import _lib, codec as _codec, indices_coding as _coding, merge as _merge, quantize as _quantize
 from . import ema as _ema                    # noqa: F401  (registers torch.ops.cgic.ema_update)
+from . import adam as _adam                  # noqa: F401  (registers torch.ops.cgic.adam_step)
 from .entropy import entropy_maps as _entropy_maps, entropy_maps_u8 as _entropy_maps_u8
 from .quantize import _vq_forward, vq_backward as _vq_backward, vq_forward_route as _vq_forward_route
 from .router import TripleGrainFixedEntropyRouter

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CGIC_ABI_VERSION 22
+#define CGIC_ABI_VERSION 23
 
 #define CGIC_OK 0
 #define CGIC_ERR_INVALID (-1)     /* bad argument (shape, ratio, NULL pointer ...) */
@@ -1164,6 +1164,75 @@ void cgic_ema_plan_destroy(cgic_ema_plan *plan);
 int cgic_ema_plan_info(const cgic_ema_plan *plan, int64_t *out);
 int cgic_ema_update(const cgic_ema_plan *plan, const float *decay, int32_t *num_updates, cgic_stream_t stream);
 int cgic_ema_copy(const cgic_ema_plan *plan, int direction, float *stash, cgic_stream_t stream);
+
+/* Multi-tensor Adam (ABI 23): gradient clipping by value (clip_grad_value_), the step of torch.optim.Adam and LitEma's update over ALL
+ * tensors of a parameter group in one pass -- per element: read g, p, m, v, s, write p, m, v, s.  Built like the EMA plan above (the same
+ * chunks, the same grid, tables in one allocation); everything is fp32.
+ *
+ *   entries  host [n]: param, exp_avg, exp_avg_sq device fp32 [n_i], 4-byte aligned (NULL allowed where n_i == 0), n_i >= 0; shadow
+ *            device fp32 [n_i] with ema_group the index of its EMA group, or shadow NULL and ema_group -1.  Tensors must not overlap.
+ *   groups   host [ngroups], 0 <= ngroups <= 16: decay device float [1], num_updates device int32 [1] or NULL -- the two buffers of
+ *            one LitEma; each group's counter moves once per step by the rule of cgic_ema_update.
+ *   steps    device fp32 [n]: the step count of every entry, the caller's (torch's state["step"]); read and written by the prologue.
+ * cgic_adam_plan_create checks everything, computes the tables on the host and uploads them in one allocation on the current device,
+ * SYNCHRONOUSLY: not for use while a stream is capturing.  CGIC_ERR_INVALID: n < 0, a NULL list with a count > 0, an n_i < 0, a NULL
+ * address with n_i > 0, an address that is not 4-byte aligned, an ema_group outside -1 .. ngroups - 1, a shadow without a group or a
+ * group without a shadow, more than 16 groups, a NULL decay, NULL steps with n > 0, more chunks than an int32 index can hold.
+ * CGIC_ERR_NOMEM / CGIC_ERR_HIP as for the EMA plan.  cgic_adam_plan_destroy frees it (NULL: a no-op); the caller makes sure nothing
+ * that uses it is still in flight.
+ * cgic_adam_plan_info: out host int64 [12] = { entries, elements, chunks, elements of a full chunk, chunks whose param, exp_avg,
+ * exp_avg_sq and shadow are all 16-byte aligned (with a 16-byte aligned gradient they move 16 bytes per lane and access, the others
+ * 4), workgroups of the body, EMA groups, entries with a shadow, uploads of the gradient table so far, uploads that had to wait for a
+ * staging slot, bytes of the device tables, steps so far }.
+ *
+ * cgic_adam_step(plan, grads, hyper, stream):
+ *   grads   host [n] device fp32 [n_i] gradient of every entry, 4-byte aligned, or NULL: no gradient this step (for an entry of 0
+ *           elements any other address says that it has one: its step count moves, nothing is read).  The addresses are
+ *           compared with those of the previous call; when they differ the new table is uploaded in stream order from one of four
+ *           pinned staging slots of the plan (the host waits only when all four are still in flight); when they are equal nothing
+ *           extra is enqueued.  While `stream` is capturing a changed table is refused (CGIC_ERR_INVALID), nothing enqueued.
+ *   hyper   lr, beta1, beta2, eps, weight_decay, clip_value as doubles (torch's Python floats), clip != 0: clamp the gradient to
+ *           +-clip_value first, lr_dev: device float [1] that replaces lr when not NULL (read by the prologue: a captured step follows
+ *           a schedule).  CGIC_ERR_INVALID outside torch's ranges (lr, eps, weight_decay >= 0, betas in [0, 1)) or clip_value < 0.
+ * Two launches ordered by the stream, no read of device memory on the host:
+ *   prologue (one workgroup)  for every entry with a gradient: step += 1 (fp32); bias_correction1 = 1 - beta1^step and
+ *           bias_correction2 = 1 - beta2^step in float64, the power by square-and-multiply from the lowest bit of the step count (a
+ *           function of the count alone); step_size = lr / bias_correction1 and sqrt(bias_correction2), rounded to fp32, kept per
+ *           entry.  For every EMA group: the counter and one_minus_decay of cgic_ema_update.
+ *   body    per element, each operation rounded once in fp32, no fused multiply-add, torch's single-tensor operand order:
+ *             g = grad;  clip: g = min(max(g, -c), c), a NaN stays;  weight_decay != 0: g = g + wd * p
+ *             w = (float)(1 - beta1):  |w| < 0.5 ?  m = m + w * (g - m)  :  m = g - (g - m) * (1 - w)
+ *             v = v * beta2;  v = v + ((float)(1 - beta2) * g) * g
+ *             p = p + (-step_size) * (m / (sqrt(v) / bc2_sqrt + eps))
+ *             with a shadow:  s = s - (omd * (s - p))  on the new p
+ *           The gradient is not written.  An entry without a gradient keeps its step count, m, v and p; with a shadow it gets the last
+ *           line alone.  Division and square root are correctly rounded.
+ * The plan's tables are written by every call: calls on ONE plan must be ordered by their streams.  Every host argument is checked
+ * before anything is enqueued.  None of the four is available inside a launch group. */
+typedef struct cgic_adam_entry {
+    float *param;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *shadow;
+    int64_t n;
+    int32_t ema_group;
+    int32_t reserved;
+} cgic_adam_entry;
+typedef struct cgic_adam_ema_group {
+    const float *decay;
+    int32_t *num_updates;
+} cgic_adam_ema_group;
+typedef struct cgic_adam_hyper {
+    double lr, beta1, beta2, eps, weight_decay, clip_value;
+    int32_t clip;
+    int32_t reserved;
+    const float *lr_dev;
+} cgic_adam_hyper;
+typedef struct cgic_adam_plan cgic_adam_plan;
+int cgic_adam_plan_create(const cgic_adam_entry *entries, int n, const cgic_adam_ema_group *groups, int ngroups, float *steps, cgic_adam_plan **out);
+void cgic_adam_plan_destroy(cgic_adam_plan *plan);
+int cgic_adam_plan_info(const cgic_adam_plan *plan, int64_t *out);
+int cgic_adam_step(cgic_adam_plan *plan, const float *const *grads, const cgic_adam_hyper *hyper, cgic_stream_t stream);
 
 #ifdef __cplusplus
 }
